@@ -8,10 +8,15 @@ SceneDensify.cpp:758-1072) of its own synthetic pinhole scene, issued as one hcm
 (the reference likewise overlaps images, SceneDensify.cpp:3699).  Inputs (images, initial maps) are resident in HBM
 before the timed region starts; every unit has its own buffers and its own RNG stream, the synthetic scene content
 repeats every 4 units (rendering 32 distinct 1080p scenes on the host would take minutes).  The single-unit latency
-(B = 1) is reported next to it as "single_unit".
+(B = 1) is reported next to it as "single_unit" (with --full).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline fields (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = milliseconds per timed step, `config`, `kernel_ms` of the last step).  Everything else below is measured
+only with --full.  --dump-outputs DIR writes what the last timed step computed, as float32 .npy files: `depth`, `normal` (x, y, z)
+and `conf` of a fixed, seeded sample of (at most) 2^20 pixels over all reference images of the step (all ranks' with N > 1), 20 MB in all.
 
 With N > 1 every rank estimates its own reference image (independent units, no collective on the estimation
 path) and the packed {depth, normal, conf} maps are all-gathered over RCCL after each step, which is the
@@ -20,7 +25,7 @@ exchange FuseDepthMaps needs (SceneDensify.cpp:3381-3449).  Prints ONE JSON line
 Beside the contract fields the line carries: `roofline` = the bound that limits the sweep kernel, the VECTOR ALU: `achieved` = wave64
 VALU instructions per second (SQ_INSTS_VALU of one launch / its duration), `peak` = 1024 SIMDs x 2.4 GHz / 2 cycles, `frac` = the
 issue fraction, `useful_flop_frac` = the flops SURVEY.md 8d counts (1.6 kflop per evaluation and view) over the 157.3 TFLOP/s vector
-peak, `traffic` = HBM bytes per launch; the counters are measured NOW by rocprofv3 --pmc child runs of this same command, one pass per
+peak, `traffic` = HBM bytes per launch; the counters are measured NOW by rocprofv3 --pmc child runs of a plain run, one pass per
 counter set (`counter_source` says so, or names the committed profile used when rocprofv3 is not usable).  `roofline_convention` keeps
 the SURVEY.md 8d tap-gather figure (algorithmic bytes over the HBM peak; it passes 1.0 because the gather is served by L2 -- printed,
 not capped).  A batch of 16 or more images runs all its sweeps in ONE kernel launch: "per launch" then means per 8 sweeps
@@ -28,7 +33,7 @@ not capped).  A batch of 16 or more images runs all its sweeps in ONE kernel lau
 with `fuse.roofline`: the SURVEY.md 8d bytes over its wall time, bound "latency", the share of the cloud's copy to the host), `authors_config`
 (the reference authors' own settings -- 10 views, 8x8 taps, cross pattern 5 / 4 -- as a batch of 16: the TWO + PACK kernel instance, time per
 sweep and its VALU fractions from a rocprofv3 child run of `bench.py --authors-only`), `cpu_baseline` (the oracle on the host cores).
-The default run takes about three and a half minutes.
+A --full run takes about three and a half minutes.
 """
 import argparse
 import ctypes
@@ -70,6 +75,64 @@ def host_cores():
         except (OSError, ValueError, IndexError):
             continue
     return n
+
+
+class _Cameras:
+    """stands in for the synth.Scene of make_views: keeps each camera make_views places and renders nothing, so that the
+    views can be rendered in parallel (render_view) -- the same calls on the same scene, hence the same bits"""
+    def __init__(self, scene):
+        self.depth0, self.cams = scene.depth0, []
+
+    def render(self, K, R, C, w, h):
+        self.cams.append((K, R, C))
+        return None, None, None
+
+
+def render_view(scene, K, R, C, keep_depth):
+    gray, depth, _ = scene.render(K, R, C, W, H)
+    return gray, (depth if keep_depth else None)
+
+
+def make_scenes(seeds):
+    """synth.make_views(W, H, FOCAL, N_SRC, seed=s) + synth.sparse_points(views, 2000, seed=p) for every (s, p) of seeds,
+    the views of all scenes rendered in a pool of host processes (one view of 1080p is about a second of numpy)"""
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    synth = importlib.import_module("hc-mvs_amd.synth")
+    px = 10.0 / FOCAL                                     # make_views' own scene for its seed
+    scenes = [synth.Scene(s, min_wavelength=3.5 * px, max_wavelength=150 * px) for s, _ in seeds]
+    out = []
+    for sc, (s, _) in zip(scenes, seeds):
+        cams = _Cameras(sc)
+        out.append((synth.make_views(W, H, FOCAL, N_SRC, seed=s, scene=cams), cams.cams))
+    jobs = [(i, j) for i in range(len(seeds)) for j in range(N_SRC + 1)]
+    workers = max(1, min(len(jobs), host_cores(), int(os.environ.get("OMP_NUM_THREADS") or 16)))
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        futs = [ex.submit(render_view, scenes[i], *out[i][1][j], j == 0) for i, j in jobs]
+        for (i, j), f in zip(jobs, futs):
+            gray, depth = f.result()
+            out[i][0][j]["gray"] = gray
+            out[i][0][j]["depth"] = depth
+    return [(views, synth.sparse_points(views, 2000, seed=p)) for (views, _), (_, p) in zip(out, seeds)]
+
+
+def dump_outputs(maps, d):
+    """the last timed step's maps (maps[u] = unit u's packed depth HW | normal 3 HW | conf HW) at a fixed, seeded sample of
+    (at most) 2^20 distinct (unit, pixel) pairs, as d/depth.npy (n,), d/normal.npy (n, 3), d/conf.npy (n,), float32"""
+    import numpy as np
+    import torch
+    HW = H * W
+    n_units = maps.shape[0]
+    rng = np.random.RandomState(20261016)
+    idx = np.unique(rng.randint(0, n_units * HW, 1 << 20, dtype=np.int64))
+    u = torch.from_numpy(idx // HW).to(maps.device)
+    p = torch.from_numpy(idx % HW).to(maps.device)
+    depth = maps[u, p]
+    normal = torch.stack([maps[u, HW + 3 * p + k] for k in range(3)], 1)
+    conf = maps[u, 4 * HW + p]
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("depth", depth), ("normal", normal), ("conf", conf)):
+        np.save(os.path.join(d, name + ".npy"), a.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(n_threads):
@@ -340,6 +403,9 @@ def main():
     ap.add_argument("--authors-only", action="store_true", help="run only the authors_config workload (what its rocprofv3 child run executes)")
     ap.add_argument("--no-pmc", action="store_true", help="take roofline.traffic / the VALU counters from profiles/ instead of measuring them "
                                                           "in rocprofv3 --pmc child runs")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: single unit, rooflines and their "
+                                                        "counters, fuse, authors_config, cpu_baseline (the --no-* switches apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's maps to DIR/*.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -368,7 +434,6 @@ def main():
     assert args.gpus == world, "--gpus must equal WORLD_SIZE (launch with torch.distributed.run for N > 1)"
 
     binding = importlib.import_module("hc-mvs_amd.binding")  # imports torch first: one HIP runtime per process
-    synth = importlib.import_module("hc-mvs_amd.synth")
     D = importlib.import_module("hc-mvs_amd.distributed")
 
     # synthetic scenes: every rank gets its own batch of B units (weak scaling); unit b = views 100*b .. 100*b+8
@@ -383,13 +448,12 @@ def main():
     HW = H * W
     params = binding.default_params(adapthalfwin=AHW, n_estimation_iters=SWEEPS, it_external=0, n_external_iters=1,
                                     seed=1234)
-    items, inits, works, keep, scenes = [], [], [], [], {}
+    items, inits, works, keep = [], [], [], []
     allwork = torch.empty(B, 5 * HW, dtype=torch.float32, device=dev)  # the rank's packed maps: unit b -> allwork[b]
     gathered = torch.empty(world * B, 5 * HW, dtype=torch.float32, device=dev) if world > 1 else None
+    # 4 distinct scenes per rank; every unit still gets its own copy in HBM
+    scenes = dict(enumerate(make_scenes([(2 + rank * 4 + k, 5 + rank * 4 + k) for k in range(min(B, 4))])))
     for b_ in range(B):
-        if b_ % 4 not in scenes:  # 4 distinct scenes per rank; every unit still gets its own copy in HBM
-            vs = synth.make_views(W, H, FOCAL, N_SRC, seed=2 + rank * 4 + b_ % 4)
-            scenes[b_ % 4] = (vs, synth.sparse_points(vs, 2000, seed=5 + rank * 4 + b_ % 4))
         views, pts = scenes[b_ % 4]
         slab = torch.from_numpy(np.stack([v["gray"] for v in views])).to(dev)  # one allocation per unit
         keep.append(slab)
@@ -432,30 +496,23 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     st = ctx.stats()  # of the last step: HIP events recorded on the stream the kernels ran on
-    # single-unit latency, outside the timed region and without the exchange
-    def single():
-        works[0].copy_(inits[0])
-        ctx.estimate_batch_device(items[:1], params)
-        torch.cuda.synchronize()
-    single()
-    t1 = time.perf_counter(); single()
-    single_ms = (time.perf_counter() - t1) * 1e3
-    st1 = ctx.stats()  # the single unit's own kernel times and evaluation counts
+    if args.dump_outputs and rank == 0:
+        dump_outputs(gathered if world > 1 else allwork, args.dump_outputs)
+    if args.full:
+        # single-unit latency, outside the timed region and without the exchange
+        def single():
+            works[0].copy_(inits[0])
+            ctx.estimate_batch_device(items[:1], params)
+            torch.cuda.synchronize()
+        single()
+        t1 = time.perf_counter(); single()
+        single_ms = (time.perf_counter() - t1) * 1e3
+        st1 = ctx.stats()  # the single unit's own kernel times and evaluation counts
 
     if rank == 0:
         P = (W - 14) * (H - 14)
-        taps_a = 0  # pass A scores every pixel of every unit once
-        for b_ in range(B):
-            gra = ctx.gradient_map(100 * (b_ % 4))[7:H - 7, 7:W - 7]  # same content every 4 units
-            taps_a += int(np.where(gra > 100, 36, (AHW + 1) ** 2).astype(np.int64).sum())
-        tap_evals_sweeps = int(st.tap_evals) - taps_a
-        # algorithmic bytes of ONE sweep launch (SURVEY.md 8d tap-gather convention): every bilinear sample
-        # counts its 4 texels (16 B) per source view, plus the 24 B of per-pixel state read and 20 B written
-        # a batch of 16 or more images runs all its sweeps in ONE kernel launch (hcmvs_api.cpp): "per launch" is then per 8 sweeps
         spl = SWEEPS // max(1, st.n_sweep_launches)                # sweeps per sweep-kernel launch
         ms_launch = st.ms_sweeps / max(1, st.n_sweep_launches)      # average duration of a sweep-kernel launch (HIP events on its stream)
-        bytes_sweep = (tap_evals_sweeps / SWEEPS * N_SRC * 16.0 + B * P * (24.0 + 20.0)) * spl
-        achieved = bytes_sweep / (ms_launch * 1e-3) / 1e9
         out = {
             "metric": "PatchMatch Mpix/s (1080p, 8 views, 7x7, 8 iter)",
             "value": round(world * B * W * H * args.steps / dt / 1e6, 4),
@@ -471,69 +528,80 @@ def main():
                        "exchange": ("%s all-gather of 20 B/px maps per step" % ("RCCL" if backend == "nccl" else backend + " (rehearsal, not a measurement)")) if world > 1 else "none",
                        "evals_per_pixel_sweep": round((st.evals / (B * P) - 1) / SWEEPS, 3)},
             "per_gpu": round(B * W * H * args.steps / dt / 1e6, 4),
-            "single_unit": {"ms": round(single_ms, 2), "Mpix/s": round(W * H / single_ms / 1e3, 3)},
             "kernel_ms": {"score_pass": round(st.ms_score, 3), "sweep_avg": round(st.ms_sweep_avg, 3), "sweep_launches": int(st.n_sweep_launches),
                           "sweep_launch_avg": round(ms_launch, 3), "sweeps_total": round(st.ms_sweeps, 3), "end": round(st.ms_end, 3),
                           "estimate_total": round(st.ms_total, 3)},
+        }
+        if args.full:
+            taps_a = 0  # pass A scores every pixel of every unit once
+            for b_ in range(B):
+                gra = ctx.gradient_map(100 * (b_ % 4))[7:H - 7, 7:W - 7]  # same content every 4 units
+                taps_a += int(np.where(gra > 100, 36, (AHW + 1) ** 2).astype(np.int64).sum())
+            tap_evals_sweeps = int(st.tap_evals) - taps_a
+            # algorithmic bytes of ONE sweep launch (SURVEY.md 8d tap-gather convention): every bilinear sample
+            # counts its 4 texels (16 B) per source view, plus the 24 B of per-pixel state read and 20 B written
+            # a batch of 16 or more images runs all its sweeps in ONE kernel launch (hcmvs_api.cpp): "per launch" is then per 8 sweeps
+            bytes_sweep = (tap_evals_sweeps / SWEEPS * N_SRC * 16.0 + B * P * (24.0 + 20.0)) * spl
+            achieved = bytes_sweep / (ms_launch * 1e-3) / 1e9
+            out["single_unit"] = {"ms": round(single_ms, 2), "Mpix/s": round(W * H / single_ms / 1e3, 3)}
             # SURVEY.md 8d convention, kept for continuity: tap-gather ALGORITHMIC bytes (every bilinear sample counts its 4 texels)
             # over the HBM peak.  The gather is served by L2, so the fraction can pass 1: it says how many taps per second are
             # sampled, not what limits the kernel -- that is `roofline` below (the vector ALU).
-            "roofline_convention": {"kernel": "sweep_kernel", "bound": "hbm", "achieved": round(achieved, 1),
-                                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                                    "compulsory_bytes_per_launch": int(B * P * (4 * N_SRC + 4 + 40)) * spl,
-                                    "algorithmic_bytes_per_launch": int(bytes_sweep), "sweeps_per_launch": spl,
-                                    "avg_launch_ms": round(ms_launch, 3),
-                                    "convention": "SURVEY.md 8d: algorithmic tap-gather bytes (4 texels per bilinear sample) over the HBM peak"},
-        }
-        # the counters of the sweep kernel: measured now in rocprofv3 --pmc child runs of this command (FETCH_SIZE / WRITE_SIZE are
-        # reported in KiB); the committed measurement of the same command only when that is not possible
-        live = live_pmc(B) if world == 1 and not args.no_pmc else None
-        if live:
-            traffic = int((live["FETCH_SIZE"] + live["WRITE_SIZE"]) * 1024)
-            vi, vb = int(live["SQ_INSTS_VALU"]), int(live.get("SQ_ACTIVE_INST_VALU", 0)) or None
-            source = "rocprofv3 --pmc child runs of this command, now (SQ_INSTS_VALU + SQ_ACTIVE_INST_VALU, FETCH_SIZE, WRITE_SIZE: one pass per set)"
-        else:
-            traffic, vi, vb = pmc_value(B, "hbm_bytes", spl), pmc_value(B, "valu_insts", spl), pmc_value(B, "valu_busy_quadcycles", spl)
-            source = "profiles/%s (committed rocprofv3 --pmc measurement of this command)" % PMC_FILE
-        t_launch = ms_launch * 1e-3
-        evals_launch = (st.evals - B * P) / SWEEPS * spl             # ScorePixel evaluations of one sweep-kernel launch (each covers all views)
-        useful_flops = evals_launch * N_SRC * FLOP_PER_EVAL_VIEW
-        roof = {"kernel": "sweep_kernel<8,1> (batched row worker; %d sweeps per launch)" % spl, "bound": "valu",
-                "achieved": round(vi / t_launch, 1) if vi else None, "peak": VALU_PEAK_INSTS, "unit": "wave64 VALU instructions/s",
-                "frac": round(vi / t_launch / VALU_PEAK_INSTS, 4) if vi else None,
-                "useful_flop_frac": round(useful_flops / t_launch / FP32_VECTOR_PEAK, 4),
-                "useful_TFLOPs": round(useful_flops / t_launch / 1e12, 2),
-                "traffic": traffic, "avg_launch_ms": round(ms_launch, 3), "sweeps_per_launch": spl, "counter_source": source,
-                "peak_definition": "1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (plain f32 rate, MI355X_MICROARCH.md); useful flops = "
-                                   "evaluations x views x 1.6 kflop (SURVEY.md 8d) over the 157.3 TFLOP/s vector fp32 peak"}
-        if traffic:
-            roof["hbm_frac"] = round(traffic / t_launch / 1e9 / HBM_PEAK_GBS, 5)
-        if vi:
-            simd_cycles = N_SIMD * CLOCK_HZ * t_launch
-            roof["insts_per_launch"] = vi
-            roof["insts_per_pixel_sweep"] = round(vi / (B * P * spl), 1)
-            # the same instruction count priced at what this mix costs: measured on this chip (profiles/r02_valu_issue_bench.jsonl)
-            # fma/mul 2.3-2.8 cycles, logic 3.0, DPP / cvt / mul24 / readlane / f64 4.2-4.7, rcp 8.2 -> about 3 cycles per
-            # instruction; and rocprof's own busy counter (SQ_ACTIVE_INST_VALU, 4-cycle units)
-            roof["pipe_frac_at_3_cycles"] = round(vi * 3 / simd_cycles, 4)
-            roof["busy_frac_rocprof_4_cycles"] = round(vb * 4 / simd_cycles, 4) if vb else None
-        out["roofline"] = roof
-        out["roofline_convention"]["copy_bandwidth_measured_GBs"] = copy_bandwidth(dev)
-        # the same roofline figure for ONE image alone (SURVEY.md 8d's literal `t` = one complete estimate): latency-bound by
-        # the (W + H) x T_pixel critical path of its row wavefront
-        taps_a1 = int(np.where(ctx.gradient_map(0)[7:H - 7, 7:W - 7] > 100, 36, (AHW + 1) ** 2).astype(np.int64).sum())
-        bytes_1 = (int(st1.tap_evals) - taps_a1) / SWEEPS * N_SRC * 16.0 + P * 44.0
-        out["roofline_single_unit"] = {"kernel": "sweep_kernel<8,3> (one image alone: 3 waves per row, the rows handed out in stretches of 256 columns; hcmvs_api.cpp waves-per-row policy)",
-                                       "bound": "latency of the row wavefront; the figure is in the SURVEY.md 8d convention (hbm)",
-                                       "achieved": round(bytes_1 / (st1.ms_sweep_avg * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": round(bytes_1 / (st1.ms_sweep_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                       "avg_launch_ms": round(st1.ms_sweep_avg, 3), "estimate_ms": round(st1.ms_total, 2)}
-        if world == 1 and not args.no_fuse:
-            out["fuse"] = fuse_throughput(ctx, scenes[0][0], scenes[0][1], dev)
-        if world == 1 and not args.no_authors:
-            out["authors_config"] = authors_config(ctx, dev, pmc=not args.no_pmc)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(host_cores())   # every host core this process may use
+            out["roofline_convention"] = {"kernel": "sweep_kernel", "bound": "hbm", "achieved": round(achieved, 1),
+                                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                                          "compulsory_bytes_per_launch": int(B * P * (4 * N_SRC + 4 + 40)) * spl,
+                                          "algorithmic_bytes_per_launch": int(bytes_sweep), "sweeps_per_launch": spl,
+                                          "avg_launch_ms": round(ms_launch, 3),
+                                          "convention": "SURVEY.md 8d: algorithmic tap-gather bytes (4 texels per bilinear sample) over the HBM peak"}
+            # the counters of the sweep kernel: measured now in rocprofv3 --pmc child runs of this command (FETCH_SIZE / WRITE_SIZE are
+            # reported in KiB); the committed measurement of the same command only when that is not possible
+            live = live_pmc(B) if world == 1 and not args.no_pmc else None
+            if live:
+                traffic = int((live["FETCH_SIZE"] + live["WRITE_SIZE"]) * 1024)
+                vi, vb = int(live["SQ_INSTS_VALU"]), int(live.get("SQ_ACTIVE_INST_VALU", 0)) or None
+                source = "rocprofv3 --pmc child runs of this command, now (SQ_INSTS_VALU + SQ_ACTIVE_INST_VALU, FETCH_SIZE, WRITE_SIZE: one pass per set)"
+            else:
+                traffic, vi, vb = pmc_value(B, "hbm_bytes", spl), pmc_value(B, "valu_insts", spl), pmc_value(B, "valu_busy_quadcycles", spl)
+                source = "profiles/%s (committed rocprofv3 --pmc measurement of this command)" % PMC_FILE
+            t_launch = ms_launch * 1e-3
+            evals_launch = (st.evals - B * P) / SWEEPS * spl             # ScorePixel evaluations of one sweep-kernel launch (each covers all views)
+            useful_flops = evals_launch * N_SRC * FLOP_PER_EVAL_VIEW
+            roof = {"kernel": "sweep_kernel<8,1> (batched row worker; %d sweeps per launch)" % spl, "bound": "valu",
+                    "achieved": round(vi / t_launch, 1) if vi else None, "peak": VALU_PEAK_INSTS, "unit": "wave64 VALU instructions/s",
+                    "frac": round(vi / t_launch / VALU_PEAK_INSTS, 4) if vi else None,
+                    "useful_flop_frac": round(useful_flops / t_launch / FP32_VECTOR_PEAK, 4),
+                    "useful_TFLOPs": round(useful_flops / t_launch / 1e12, 2),
+                    "traffic": traffic, "avg_launch_ms": round(ms_launch, 3), "sweeps_per_launch": spl, "counter_source": source,
+                    "peak_definition": "1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (plain f32 rate, MI355X_MICROARCH.md); useful flops = "
+                                       "evaluations x views x 1.6 kflop (SURVEY.md 8d) over the 157.3 TFLOP/s vector fp32 peak"}
+            if traffic:
+                roof["hbm_frac"] = round(traffic / t_launch / 1e9 / HBM_PEAK_GBS, 5)
+            if vi:
+                simd_cycles = N_SIMD * CLOCK_HZ * t_launch
+                roof["insts_per_launch"] = vi
+                roof["insts_per_pixel_sweep"] = round(vi / (B * P * spl), 1)
+                # the same instruction count priced at what this mix costs: measured on this chip (profiles/r02_valu_issue_bench.jsonl)
+                # fma/mul 2.3-2.8 cycles, logic 3.0, DPP / cvt / mul24 / readlane / f64 4.2-4.7, rcp 8.2 -> about 3 cycles per
+                # instruction; and rocprof's own busy counter (SQ_ACTIVE_INST_VALU, 4-cycle units)
+                roof["pipe_frac_at_3_cycles"] = round(vi * 3 / simd_cycles, 4)
+                roof["busy_frac_rocprof_4_cycles"] = round(vb * 4 / simd_cycles, 4) if vb else None
+            out["roofline"] = roof
+            out["roofline_convention"]["copy_bandwidth_measured_GBs"] = copy_bandwidth(dev)
+            # the same roofline figure for ONE image alone (SURVEY.md 8d's literal `t` = one complete estimate): latency-bound by
+            # the (W + H) x T_pixel critical path of its row wavefront
+            taps_a1 = int(np.where(ctx.gradient_map(0)[7:H - 7, 7:W - 7] > 100, 36, (AHW + 1) ** 2).astype(np.int64).sum())
+            bytes_1 = (int(st1.tap_evals) - taps_a1) / SWEEPS * N_SRC * 16.0 + P * 44.0
+            out["roofline_single_unit"] = {"kernel": "sweep_kernel<8,3> (one image alone: 3 waves per row, the rows handed out in stretches of 256 columns; hcmvs_api.cpp waves-per-row policy)",
+                                           "bound": "latency of the row wavefront; the figure is in the SURVEY.md 8d convention (hbm)",
+                                           "achieved": round(bytes_1 / (st1.ms_sweep_avg * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                           "frac": round(bytes_1 / (st1.ms_sweep_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                           "avg_launch_ms": round(st1.ms_sweep_avg, 3), "estimate_ms": round(st1.ms_total, 2)}
+            if world == 1 and not args.no_fuse:
+                out["fuse"] = fuse_throughput(ctx, scenes[0][0], scenes[0][1], dev)
+            if world == 1 and not args.no_authors:
+                out["authors_config"] = authors_config(ctx, dev, pmc=not args.no_pmc)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(host_cores())   # every host core this process may use
         print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:

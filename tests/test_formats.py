@@ -1,28 +1,51 @@
 """File formats against the reference's own serializer: oracle/_ref/interface_probe is compiled from the reference's
-self-contained Interface.h (where it lies under /root/reference) -- the one part of the reference that builds here."""
+self-contained Interface.h -- the one part of the reference that builds without third-party libraries.  Where the reference
+is not at hand (the probe cannot be built), the tests read what the probe wrote and printed for the same inputs, recorded
+under tests/golden/ by tests/golden/make_format_golden.py; where it is, they run the probe and hold it to those records."""
 import importlib
 import os
 import subprocess
 
 import numpy as np
-import pytest
 
 mvsio = importlib.import_module("hc-mvs_amd.mvsio")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE = os.path.join(ROOT, "oracle", "_ref", "interface_probe")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _probe():
+    """the probe's path, or None when the reference is not present to build it from"""
     if not os.path.exists(PROBE):
         subprocess.call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL)
-    if not os.path.exists(PROBE):
-        pytest.skip("reference Interface.h probe not built (no /root/reference here)")
-    return PROBE
+    return PROBE if os.path.exists(PROBE) else None
+
+
+def _gold(name, mode="rb"):
+    with open(os.path.join(GOLD, name), mode) as f:
+        return f.read()
+
+
+def write_our_scene(p):
+    """the deterministic scene our writer hands to the reference's reader"""
+    rng = np.random.RandomState(0)
+    cams = [dict(name="c%d" % i, width=640, height=480, K=[[500 + i, 0, 319.5], [0, 500, 239.5], [0, 0, 1]], R=np.eye(3),
+                 C=[0, 0, 0]) for i in range(2)]
+    poses = [dict(R=np.eye(3), C=rng.normal(size=3)) for _ in range(2)]
+    images = [dict(name="a%d.ppm" % i, platformID=0, cameraID=i, poseID=i, ID=i) for i in range(2)]
+    verts = [dict(X=rng.normal(size=3).astype(np.float32), views=[(0, 0.0), (1, 0.5)]) for _ in range(5)]
+    cols = rng.randint(0, 255, (5, 3)).astype(np.uint8)
+    mvsio.write_mvs(p, [dict(name="pl", cameras=cams, poses=poses)], images, verts, cols)
+    return poses, verts, cols
 
 
 def test_reference_writes_we_read(tmp_path):
-    p = str(tmp_path / "ref.mvs")
-    subprocess.check_call([_probe(), "write", p, "3", "4"])
+    p = os.path.join(GOLD, "interface_probe_write_3_4.mvs")      # the reference's serializer output, recorded
+    probe = _probe()
+    if probe:
+        p = str(tmp_path / "ref.mvs")
+        subprocess.check_call([probe, "write", p, "3", "4"])
+        assert open(p, "rb").read() == _gold("interface_probe_write_3_4.mvs"), "the recorded fixture is stale"
     s = mvsio.read_mvs(p)
     assert s["version"] == 5 and len(s["platforms"]) == 1 and len(s["images"]) == 3 and len(s["vertices"]) == 4
     cam = s["platforms"][0]["cameras"][1]
@@ -38,15 +61,11 @@ def test_reference_writes_we_read(tmp_path):
 
 def test_we_write_reference_reads(tmp_path):
     p = str(tmp_path / "ours.mvs")
-    rng = np.random.RandomState(0)
-    cams = [dict(name="c%d" % i, width=640, height=480, K=[[500 + i, 0, 319.5], [0, 500, 239.5], [0, 0, 1]], R=np.eye(3),
-                 C=[0, 0, 0]) for i in range(2)]
-    poses = [dict(R=np.eye(3), C=rng.normal(size=3)) for _ in range(2)]
-    images = [dict(name="a%d.ppm" % i, platformID=0, cameraID=i, poseID=i, ID=i) for i in range(2)]
-    verts = [dict(X=rng.normal(size=3).astype(np.float32), views=[(0, 0.0), (1, 0.5)]) for _ in range(5)]
-    cols = rng.randint(0, 255, (5, 3)).astype(np.uint8)
-    mvsio.write_mvs(p, [dict(name="pl", cameras=cams, poses=poses)], images, verts, cols)
-    dump = subprocess.check_output([_probe(), "dump", p]).decode().splitlines()
+    poses, verts, cols = write_our_scene(p)
+    # the recorded dump is what the reference's reader made of these very bytes
+    assert open(p, "rb").read() == _gold("interface_probe_ours.mvs"), "our writer's bytes differ from the file the reference read"
+    probe = _probe()
+    dump = (subprocess.check_output([probe, "dump", p]).decode() if probe else _gold("interface_probe_ours_dump.txt", "r")).splitlines()
     assert dump[0] == "version 5" and "platform pl cameras 2 poses 2" in dump
     assert any(l.startswith("camera c1 640 480 K 501 0 319.5") for l in dump)
     assert "image a1.ppm 0 1 1 1" in dump and "vertices 5" in dump and "colors 5" in dump
@@ -58,7 +77,8 @@ def test_we_write_reference_reads(tmp_path):
 
 
 def test_dr_header_matches_reference_layout(tmp_path):
-    out = subprocess.check_output([_probe(), "sizes"]).decode()
+    probe = _probe()
+    out = subprocess.check_output([probe, "sizes"]).decode() if probe else _gold("interface_probe_sizes.txt", "r")
     assert "sizeof(HeaderDepthDataRaw) 28" in out and "0x5244" in out  # 'DR'
     p = str(tmp_path / "depth0000.dmap")
     d = np.random.RandomState(1).uniform(1, 5, (6, 8)).astype(np.float32)
