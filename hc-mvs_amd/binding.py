@@ -43,6 +43,11 @@ class Cloud(C.Structure):
                 ("view_weights", C.POINTER(C.c_float)), ("n_points", C.c_uint64), ("n_depths", C.c_uint64), ("n_view_entries", C.c_uint64)]
 
 
+class VisibilityStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("skipped_pairs", C.c_uint64), ("fallback_pairs", C.c_uint64), ("candidates", C.c_uint64),
+                ("hits", C.c_uint64), ("device_bytes", C.c_uint64), ("ms_device", C.c_float)]
+
+
 class HcmvsError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("hcmvs error %d: %s" % (code, msg))
@@ -58,7 +63,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
-           "hcmvs_estimate_point_normals", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up"]
+           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -142,6 +147,8 @@ def lib():
         L.hcmvs_postfilter_sequence.argtypes = [vp, u32p, C.c_int32, u32p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, u64p]
         L.hcmvs_estimate_point_colors.argtypes = [vp, C.c_uint64, fp, u32p, u32p, u8p]
         L.hcmvs_estimate_point_normals.argtypes = [vp, C.c_uint64, fp, u32p, u32p, C.c_int32, fp]
+        L.hcmvs_point_cloud_filter.argtypes = [vp, C.c_uint64, fp, u32p, u32p, C.c_uint32, C.POINTER(C.c_int32), dp, dp, dp, C.c_int32,
+                                               C.POINTER(C.c_int32), u32p, u64p, C.POINTER(VisibilityStats)]
         L.hcmvs_resize_area_up.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
         _lib = L
     return _lib
@@ -386,6 +393,29 @@ class Context:
         self._chk(lib().hcmvs_estimate_point_normals(self._h, len(x), _f(x), nv.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                      vi.ctypes.data_as(C.POINTER(C.c_uint32)), n_neighbors, _f(out)))
         return out
+
+    def point_cloud_filter(self, xyz, n_views, view_ids, cameras, th_remove=-1):
+        """Scene::PointCloudFilter on the device: cameras = one dict per image (K, R, C at width x height; width 0 or a missing K =
+        uncalibrated).  Returns (visibility int32 per point, kept uint32 indices in the reference's output order); the counters of the
+        call are left in self.visibility_stats"""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nv = np.ascontiguousarray(n_views, np.uint32); vi = np.ascontiguousarray(view_ids, np.uint32)
+        m = len(cameras)
+        wh = np.zeros((max(m, 1), 2), np.int32); K = np.zeros((max(m, 1), 9)); R = np.zeros((max(m, 1), 9)); Cc = np.zeros((max(m, 1), 3))
+        for j, cam in enumerate(cameras):
+            if cam is None or cam.get("K") is None or not cam.get("width"):
+                continue
+            wh[j] = cam["width"], cam["height"]
+            K[j] = np.asarray(cam["K"], np.float64).ravel(); R[j] = np.asarray(cam["R"], np.float64).ravel(); Cc[j] = np.asarray(cam["C"], np.float64)
+        vis = np.empty(len(x), np.int32); kept = np.empty(max(len(x), 1), np.uint32)
+        nk = C.c_uint64(); st = VisibilityStats()
+        u32 = C.POINTER(C.c_uint32); dp = C.POINTER(C.c_double)
+        self._chk(lib().hcmvs_point_cloud_filter(self._h, len(x), _f(x), nv.ctypes.data_as(u32), vi.ctypes.data_as(u32), m,
+                                                 wh.ctypes.data_as(C.POINTER(C.c_int32)), K.ctypes.data_as(dp), R.ctypes.data_as(dp),
+                                                 Cc.ctypes.data_as(dp), int(th_remove), vis.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 kept.ctypes.data_as(u32), C.byref(nk), C.byref(st)))
+        self.visibility_stats = {k: getattr(st, k) for k, _ in VisibilityStats._fields_}
+        return vis, kept[:nk.value].copy()
 
     def postfilter(self, vid, order, n_min_views_fuse=2, depth_diff_threshold=0.01, normal_diff_deg=25.0, gap_size=7):
         """RemoveSmallSegments (fork version) + GapInterpolation on the registered device maps of view vid; returns pixels filled"""

@@ -12,6 +12,7 @@
 #include "pf_chain.h"
 #include "tri_init.h"
 #include "cloud_kernels.h"
+#include "vis_kernels.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -1406,6 +1407,35 @@ int hcmvs_estimate_point_normals(hcmvs_ctx* c, uint64_t n, const float* xyz, con
 	std::string err;
 	const int rc = hcmvs::pca_normals_device(n, xyz, first.data(), centres.data(), (size_t)maxId + 1, k, normal, c->stream, err);
 	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
+	return HCMVS_OK;
+}
+
+int hcmvs_point_cloud_filter(hcmvs_ctx* c, uint64_t n, const float* xyz, const uint32_t* n_views, const uint32_t* view_ids, uint32_t n_images,
+                             const int32_t* wh, const double* K, const double* R, const double* C, int32_t th_remove, int32_t* visibility,
+                             uint32_t* kept, uint64_t* n_kept, hcmvs_visibility_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (!n_kept || (n && (!xyz || !n_views || !view_ids || !kept)) || (n_images && (!wh || !K || !R || !C)))
+		return fail(c, HCMVS_ERR_INVALID, "point_cloud_filter: null argument");
+	if (n >= 0xFFFFFFFFull) return fail(c, HCMVS_ERR_INVALID, "point_cloud_filter: 2^32 - 1 points or more");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	std::vector<int32_t> vis(n);
+	hcmvs::VisCounters st;
+	std::string err;
+	const int rc = hcmvs::point_cloud_visibility_device(n, xyz, n_views, view_ids, n_images, wh, K, R, C, vis.data(), st, c->stream, err);
+	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
+	// RFOREACH + PointCloud::RemovePoint -> cList::RemoveAt (List.h:1070-1077): the last point moves into the hole.  Position i still holds
+	// point i when the loop reaches it, so the permutation is order[i] = order[--size] for every removed i, from the back
+	uint64_t size = n;
+	for (uint64_t i = 0; i < n; ++i) kept[i] = (uint32_t)i;
+	for (uint64_t i = n; i-- > 0;)
+		if (vis[i] <= th_remove) kept[i] = kept[--size];
+	*n_kept = size;
+	if (visibility && n) memcpy(visibility, vis.data(), n * 4);
+	if (stats) {
+		stats->pairs = st.pairs; stats->skipped_pairs = st.skipped; stats->fallback_pairs = st.fallback; stats->candidates = st.candidates;
+		stats->hits = st.hits; stats->device_bytes = st.deviceBytes; stats->ms_device = st.ms;
+	}
 	return HCMVS_OK;
 }
 

@@ -6,7 +6,8 @@
  * (Scene.cpp:545-678, SceneDensify.cpp:336-397), runs the PatchMatch estimate for the requested outer iterations
  * (Scene::DenseReconstruction, SceneDensify.cpp:3532-3574, 3684), writes raw 'DR' depth maps
  * (DepthMap.cpp:2781-2846), fuses them (SceneDensify.cpp:3265-3495) and saves `<out>.ply` + `<out>.mvs`
- * (DensifyPointCloud.cpp:447-449).
+ * (DensifyPointCloud.cpp:447-449).  With --filter-point-cloud < 0 it only filters the cloud of the input scene by visibility
+ * (Scene::PointCloudFilter, DensifyPointCloud.cpp:399-414) and saves `<out>_filtered.mvs` + `.ply`.
  *
  * Deliberately narrower than the reference ("defined subset"): images are read from binary
  * PPM/PGM files (no PNG/JPEG codecs here); the initial maps come from the Delaunay triangulation of the sparse points
@@ -112,7 +113,9 @@ struct MvsPose { double R[9], C[3]; };
 struct MvsPlatform { std::string name; std::vector<MvsCamera> cams; std::vector<MvsPose> poses; };
 struct MvsImage { std::string name; uint32_t platformID, cameraID, poseID, ID; };
 
-bool load_mvs(const std::string& path, std::vector<MvsPlatform>& platforms, std::vector<MvsImage>& images, std::vector<Vertex>& verts) {
+// normals / colors (optional): the vertices' normals (3 f32) and colours (B,G,R) that follow the vertices (Interface.h:607-609)
+bool load_mvs(const std::string& path, std::vector<MvsPlatform>& platforms, std::vector<MvsImage>& images, std::vector<Vertex>& verts,
+              std::vector<float>* normals = nullptr, std::vector<uint8_t>* colors = nullptr) {
 	Reader r;
 	r.f.open(path, std::ios::binary);
 	if (!r.f) return false;
@@ -147,6 +150,16 @@ bool load_mvs(const std::string& path, std::vector<MvsPlatform>& platforms, std:
 		r.f.read((char*)v.X, 12);
 		v.views.resize(r.get<uint64_t>());
 		for (auto& w : v.views) { w.first = r.get<uint32_t>(); w.second = r.get<float>(); }
+	}
+	if (normals && colors) {
+		const uint64_t nn = r.get<uint64_t>();
+		if (!r.f || nn > verts.size()) return false;
+		normals->resize(3 * nn);
+		r.f.read((char*)normals->data(), (std::streamsize)(12 * nn));
+		const uint64_t nc = r.get<uint64_t>();
+		if (!r.f || nc > verts.size()) return false;
+		colors->resize(3 * nc);
+		r.f.read((char*)colors->data(), (std::streamsize)(3 * nc));
 	}
 	return (bool)r.f;
 }
@@ -327,6 +340,18 @@ void mat3mul(const double* a, const double* b, double* c) {
 void w2c(const Camera& c, const float* X, double* o) {
 	const double d[3] = {X[0] - c.C[0], X[1] - c.C[1], X[2] - c.C[2]};
 	for (int i = 0; i < 3; ++i) o[i] = c.R[i * 3] * d[0] + c.R[i * 3 + 1] * d[1] + c.R[i * 3 + 2] * d[2];
+}
+// the camera of an image at the size w x h: Interface.h:451-459 pose composition (R = Rcam Rpose, C = Rpose^T Ccam + Cpose) and
+// Scene.cpp:83-91 + Camera.h:167-180 (GetK): K normalised by max(w,h) of the camera, scaled to w x h
+void image_camera(const MvsCamera& c, const MvsPose& q, int w, int h, Camera& cam) {
+	mat3mul(c.R, q.R, cam.R);
+	for (int k = 0; k < 3; ++k) cam.C[k] = q.R[0 * 3 + k] * c.C[0] + q.R[1 * 3 + k] * c.C[1] + q.R[2 * 3 + k] * c.C[2] + q.C[k];
+	const double s = (double)std::max(w, h) / (c.w && c.h ? (double)std::max(c.w, c.h) : 1.0);
+	memcpy(cam.K, c.K, sizeof cam.K);
+	cam.K[1] = 0;
+	cam.K[0] *= s; cam.K[4] *= s;
+	if (c.K[2] == 0 && c.K[5] == 0) { cam.K[2] = 0.5 * (w - 1); cam.K[5] = 0.5 * (h - 1); }
+	else { cam.K[2] *= s; cam.K[5] *= s; }
 }
 bool project(const Camera& c, const float* X, float& u, float& v, double& z) {
 	double p[3];
@@ -570,6 +595,112 @@ struct Saver {
 	static constexpr size_t kMaxQueuedBytes = (size_t)12 << 30; // host memory the copier may run ahead of the writers
 };
 
+// --filter-point-cloud < 0 (DensifyPointCloud.cpp:399-414): Scene::Load, Scene::PointCloudFilter(th) on the first device of --devices,
+// then <output base>_filtered.mvs / .ply; no densify runs.  The cameras are taken at their own resolution and no image is opened, except
+// the header of an image whose camera has no resolution (Scene::LoadInterface reads the size from the image then).
+int run_point_cloud_filter(const Options& o, int th) {
+	const double tStart = now_s();
+	std::vector<MvsPlatform> platforms; std::vector<MvsImage> mimages; std::vector<Vertex> verts;
+	std::vector<float> normals; std::vector<uint8_t> colors;
+	if (!load_mvs(o.input, platforms, mimages, verts, &normals, &colors)) { fprintf(stderr, "error: can not load '%s'\n", o.input.c_str()); return EXIT_FAILURE; }
+	if (verts.empty()) { fprintf(stderr, "error: empty initial point-cloud\n"); return EXIT_FAILURE; }
+	const size_t n = verts.size(), m = mimages.size();
+	std::vector<int32_t> wh(2 * std::max<size_t>(m, 1), 0);
+	std::vector<double> K(9 * std::max<size_t>(m, 1), 0.0), R(9 * std::max<size_t>(m, 1), 0.0), C(3 * std::max<size_t>(m, 1), 0.0);
+	for (size_t i = 0; i < m; ++i) {
+		const MvsImage& mi = mimages[i];
+		if (mi.poseID == 0xFFFFFFFFu || mi.platformID >= platforms.size()) continue; // uncalibrated: its pairs are skipped
+		const MvsPlatform& p = platforms[mi.platformID];
+		if (mi.cameraID >= p.cams.size() || mi.poseID >= p.poses.size()) continue;
+		const MvsCamera& c = p.cams[mi.cameraID];
+		int w = (int)c.w, h = (int)c.h;
+		if (!w || !h) {
+			const std::string path = mi.name[0] == '/' ? mi.name : dirname_of(o.input) + "/" + mi.name;
+			if (!pnm_size(path, w, h)) { fprintf(stderr, "error: failed loading image '%s' (binary PPM/PGM expected)\n", path.c_str()); return EXIT_FAILURE; }
+		}
+		Camera cam;
+		image_camera(c, p.poses[mi.poseID], w, h, cam);
+		wh[2 * i] = w; wh[2 * i + 1] = h;
+		memcpy(&K[9 * i], cam.K, 72); memcpy(&R[9 * i], cam.R, 72); memcpy(&C[3 * i], cam.C, 24);
+	}
+	std::vector<float> xyz(3 * n);
+	std::vector<uint32_t> nv(n), ids;
+	std::vector<float> wts;
+	std::vector<size_t> first(n + 1, 0);
+	for (size_t i = 0; i < n; ++i) {
+		memcpy(&xyz[3 * i], verts[i].X, 12);
+		nv[i] = (uint32_t)verts[i].views.size();
+		first[i + 1] = first[i] + nv[i];
+		for (const auto& v : verts[i].views) { ids.push_back(v.first); wts.push_back(v.second); }
+	}
+	if (ids.empty()) ids.push_back(0);
+	hcmvs_ctx* ctx = nullptr;
+	if (hcmvs_create(o.devices[0], &ctx) != HCMVS_OK) { fprintf(stderr, "error: device %d is not a usable MI355X (there is no CPU path)\n", o.devices[0]); return EXIT_FAILURE; }
+	std::vector<int32_t> vis(n);
+	std::vector<uint32_t> kept(n);
+	uint64_t nKept = 0;
+	hcmvs_visibility_stats st;
+	if (hcmvs_point_cloud_filter(ctx, n, xyz.data(), nv.data(), ids.data(), (uint32_t)m, wh.data(), K.data(), R.data(), C.data(), th, vis.data(), kept.data(),
+	                             &nKept, &st) != HCMVS_OK) {
+		fprintf(stderr, "error: point-cloud filter failed: %s\n", hcmvs_last_error(ctx));
+		hcmvs_destroy(ctx);
+		return EXIT_FAILURE;
+	}
+	hcmvs_destroy(ctx);
+	const bool hasN = normals.size() == 3 * n, hasC = colors.size() == 3 * n; // RemovePoint moves what exists (PointCloud.cpp:54-69)
+	if (o.verbosity > 2) {
+		// the histogram of the non-positive visibilities and the removed points, reverse index order (SceneDensify.cpp:4284-4308)
+		std::vector<unsigned> counts;
+		for (int32_t v : vis) {
+			if (v > 0) continue;
+			if (counts.size() <= (size_t)-(int64_t)v) counts.resize((size_t)-(int64_t)v + 1, 0);
+			++counts[(size_t)-(int64_t)v];
+		}
+		printf("Visibility lengths (%zu points):", n);
+		for (size_t c = 0; c < counts.size(); ++c)
+			if (counts[c]) printf("\n\t%3zu - %9u", c, counts[c]);
+		printf("\n");
+		size_t nOut = 0;
+		for (int32_t v : vis) nOut += v <= th;
+		RawArray<float> ox(3 * nOut), on(0);
+		RawArray<uint8_t> oc(hasC ? 3 * nOut : 0);
+		size_t k = 0;
+		for (size_t i = n; i-- > 0;)
+			if (vis[i] <= th) {
+				memcpy(ox.data() + 3 * k, &xyz[3 * i], 12);
+				if (hasC) memcpy(oc.data() + 3 * k, &colors[3 * i], 3);
+				++k;
+			}
+		const std::string outliers = o.workdir + "/scene_dense_outliers.ply";
+		if (!save_ply(outliers, ox, on, oc)) { fprintf(stderr, "error: can not write '%s'\n", outliers.c_str()); return EXIT_FAILURE; }
+		printf("Point visibility checks: %llu pairs (%llu skipped: unknown or uncalibrated image), %llu exact-path pairs, %.1f candidates per pair, "
+		       "%llu votes, %.1f MiB device memory, %.2f ms device time\n", (unsigned long long)st.pairs, (unsigned long long)st.skipped_pairs,
+		       (unsigned long long)st.fallback_pairs, st.pairs ? (double)st.candidates / (double)st.pairs : 0.0, (unsigned long long)st.hits,
+		       st.device_bytes / 1048576.0, st.ms_device);
+	}
+	// the kept cloud in the reference's order; views, weights, normals and colours move with their point
+	size_t nEntries = 0;
+	for (uint64_t k = 0; k < nKept; ++k) nEntries += nv[kept[k]];
+	RawArray<float> kx(3 * nKept), kn(hasN ? 3 * nKept : 0), kw(nEntries);
+	RawArray<uint8_t> kc(hasC ? 3 * nKept : 0);
+	RawArray<uint32_t> knv(nKept), kids(nEntries);
+	size_t e = 0;
+	for (uint64_t k = 0; k < nKept; ++k) {
+		const size_t i = kept[k];
+		memcpy(kx.data() + 3 * k, &xyz[3 * i], 12);
+		if (hasN) memcpy(kn.data() + 3 * k, &normals[3 * i], 12);
+		if (hasC) memcpy(kc.data() + 3 * k, &colors[3 * i], 3);
+		knv.data()[k] = nv[i];
+		for (size_t v = first[i]; v < first[i + 1]; ++v, ++e) { kids.data()[e] = ids[v]; kw.data()[e] = wts[v]; }
+	}
+	const std::string base = o.output.substr(0, o.output.rfind('.')) + "_filtered";
+	if (!save_mvs(base + ".mvs", platforms, mimages, kx, kn, kc, knv, kids, kw)) { fprintf(stderr, "error: can not write '%s.mvs'\n", base.c_str()); return EXIT_FAILURE; }
+	if (!save_ply(base + ".ply", kx, kn, kc)) { fprintf(stderr, "error: can not write '%s.ply'\n", base.c_str()); return EXIT_FAILURE; }
+	if (o.verbosity > 1)
+		printf("Point-cloud filtered: %llu/%zu points (%d%%) (%.2f s)\n", (unsigned long long)nKept, n, (int)std::lround(100.0 * (double)nKept / (double)n), now_s() - tStart);
+	return EXIT_SUCCESS;
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -637,19 +768,19 @@ int main(int argc, char** argv) {
 	for (const char* k : {"--n-opticalflow", "--n-viewspread", "--use-semantic", "--n-usegeoconsistency", "--n-usepartconsistency"})
 		if (kv.count(k) && atoi(kv[k].c_str()) != 0 && o.verbosity > 1)
 			fprintf(stderr, "note: %s is not available in this build (defined subset); treated as 0\n", k);
-	if (kv.count("--filter-point-cloud") && atoi(kv["--filter-point-cloud"].c_str()) < 0) {
-		fprintf(stderr, "error: --filter-point-cloud < 0 (visibility filter of an existing cloud, DensifyPointCloud.cpp:406-414) is not available\n");
-		return EXIT_FAILURE;
-	}
+	const int thFilterPointCloud = kv.count("--filter-point-cloud") ? atoi(kv["--filter-point-cloud"].c_str()) : 0; // >= 0: no effect, as in the reference
 	if (kv.count("--sample-mesh") && atof(kv["--sample-mesh"].c_str()) != 0) { fprintf(stderr, "error: --sample-mesh is not available\n"); return EXIT_FAILURE; }
 	if (o.input.empty() || kv.count("--help")) {
 		fprintf(stderr, "usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
-		                "[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n");
+		                "[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n"
+		                "       DensifyPointCloud -i dense.mvs [-o out.mvs] --filter-point-cloud <negative threshold>   (visibility filter of the cloud only:\n"
+		                "       writes <out>_filtered.mvs and <out>_filtered.ply)\n");
 		return EXIT_FAILURE;
 	}
-	if (o.fusionMode < 0) { fprintf(stderr, "error: SGM fusion modes are not available\n"); return EXIT_FAILURE; }
 	if (o.workdir.empty()) o.workdir = dirname_of(o.input);
 	if (o.output.empty()) o.output = o.input.substr(0, o.input.rfind('.')) + "_dense.mvs";
+	if (thFilterPointCloud < 0) return run_point_cloud_filter(o, thFilterPointCloud);
+	if (o.fusionMode < 0) { fprintf(stderr, "error: SGM fusion modes are not available\n"); return EXIT_FAILURE; }
 	if (o.batch < 1) o.batch = 1;
 	if (o.batch > HCMVS_MAX_BATCH) o.batch = HCMVS_MAX_BATCH;
 	if (o.estimationItersExternal < 1) o.estimationItersExternal = 1;
@@ -681,16 +812,7 @@ int main(int argc, char** argv) {
 		if (!pnm_size(paths[i], fw, fh)) { fprintf(stderr, "error: failed loading image '%s' (binary PPM/PGM expected)\n", paths[i].c_str()); return EXIT_FAILURE; }
 		// SceneDensify.cpp:3612-3615: one INTER_AREA resize to the resolution level's size, within [min-resolution, max-resolution]
 		working_size(fw, fh, (unsigned)std::max(0, o.resolutionLevel), (unsigned)std::max(1, o.minResolution), (unsigned)std::max(1, o.maxResolution), im.w, im.h);
-		// Interface.h:451-459 pose composition; K rescaled to the working resolution (Scene.cpp:83-91, Camera.h:167-180)
-		mat3mul(c.R, q.R, im.cam.R);
-		for (int k = 0; k < 3; ++k) im.cam.C[k] = q.R[0 * 3 + k] * c.C[0] + q.R[1 * 3 + k] * c.C[1] + q.R[2 * 3 + k] * c.C[2] + q.C[k];
-		// Scene.cpp:83-91 + Camera.h:167-180 (GetK): K normalised by max(w,h) of the camera, scaled to the working size
-		const double s = (double)std::max(im.w, im.h) / (c.w && c.h ? (double)std::max(c.w, c.h) : 1.0);
-		memcpy(im.cam.K, c.K, sizeof im.cam.K);
-		im.cam.K[1] = 0;
-		im.cam.K[0] *= s; im.cam.K[4] *= s;
-		if (c.K[2] == 0 && c.K[5] == 0) { im.cam.K[2] = 0.5 * (im.w - 1); im.cam.K[5] = 0.5 * (im.h - 1); }
-		else { im.cam.K[2] *= s; im.cam.K[5] *= s; }
+		image_camera(c, q, im.w, im.h, im.cam); // K rescaled to the working resolution
 		im.valid = true;
 		++nValid;
 	}

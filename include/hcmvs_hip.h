@@ -284,6 +284,28 @@ int hcmvs_estimate_point_colors(hcmvs_ctx* ctx, uint64_t n_points, const float* 
 int hcmvs_estimate_point_normals(hcmvs_ctx* ctx, uint64_t n_points, const float* xyz, const uint32_t* n_views, const uint32_t* view_ids,
                                  int32_t n_neighbors, float* normal);
 
+/* counters of the last hcmvs_point_cloud_filter call */
+typedef struct {
+	uint64_t pairs;          /* (point, view) pairs evaluated */
+	uint64_t skipped_pairs;  /* view entries naming an image >= n_images or an uncalibrated one: skipped */
+	uint64_t fallback_pairs; /* pairs that took the exact path over all points (X behind the camera, outside the binned domain) */
+	uint64_t candidates;     /* cone tests run */
+	uint64_t hits;           /* votes cast: VISIBLE and not depth-similar (one int32 atomic each) */
+	uint64_t device_bytes;   /* device memory the call allocated */
+	float ms_device;         /* device time from the first kernel to the last (HIP events) */
+} hcmvs_visibility_stats;
+/* Scene::PointCloudFilter (SceneDensify.cpp:4188-4320; DensifyPointCloud --filter-point-cloud < 0): the visibility of every point is
+ * summed over the cones of all (point X, view j of X) pairs -- apex the camera centre of j, axis through X, half-angle
+ * float(ComputeFOV(0) / width), height 1.02 |X - C| -- where every point P inside the cone that is not within 1 % of X's distance gains
+ * |views(P)| when behind X and loses |views(X)| when in front; points with visibility <= th_remove are removed by the reference's reverse
+ * swap-with-last loop (PointCloud::RemovePoint).  Computed on the device, exactly (integer sums; float32 arithmetic with the association
+ * stated in DESIGN.md section 5).  Points as CSR (as in hcmvs_cloud, fewer than 2^32 - 1); per image: wh (width, height; width 0 =
+ * uncalibrated, its pairs are skipped), K and R (9 f64 each, at that width x height), C (3 f64).  Out: visibility (n int32) or NULL,
+ * kept (n uint32): the indices of the kept points in the reference's output order, *n_kept of them; stats or NULL. */
+int hcmvs_point_cloud_filter(hcmvs_ctx* ctx, uint64_t n_points, const float* xyz, const uint32_t* n_views, const uint32_t* view_ids,
+                             uint32_t n_images, const int32_t* wh, const double* K, const double* R, const double* C, int32_t th_remove,
+                             int32_t* visibility_or_null, uint32_t* kept, uint64_t* n_kept, hcmvs_visibility_stats* stats_or_null);
+
 #ifdef __cplusplus
 }
 #endif
