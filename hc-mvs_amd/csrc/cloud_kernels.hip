@@ -200,21 +200,20 @@ __global__ void positions_kernel(unsigned long long n, const uint32_t* idx, uint
 } // namespace
 
 int pca_normals_device(unsigned long long n, const float* hXyz, const uint32_t* hFirstView, const double* hViewC, size_t nViews, int k,
-                       float* hNormal, hipStream_t s, std::string& err) {
+                       float* hNormal, DevBuf& scratch, hipStream_t s, std::string& err) {
 	if (n == 0) return 0;
 	if (k > kMaxK) { err = "estimate_point_normals: k above 32"; return 1; }
 	if (n >= 0x7FFFFFFFull) { err = "estimate_point_normals: more than 2^31 - 1 points"; return 1; }
 	size_t sortBytes = 0;
 	(void)hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
 	                                         (uint32_t*)nullptr, (int)n);
-	size_t off = 0;
-	auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	Carve carve;
 	const size_t oXyz = carve(n * 12), oKeys = carve(n * 8), oKeys2 = carve(n * 8), oIdx = carve(n * 4), oIdx2 = carve(n * 4), oSorted = carve(n * 16),
 	             oPos = carve(n * 4), oFirst = carve(n * 4), oC = carve(nViews * 24), oN = carve(n * 12), oBox = carve(64),
 	             oSort = carve(sortBytes);
-	char* b = nullptr;
-	if (hipMalloc(&b, off) != hipSuccess) { err = "estimate_point_normals: out of device memory"; return 2; }
-	auto fail = [&](const char* what) { err = what; (void)hipFree(b); return 2; };
+	if (scratch.reserve(carve.size, s) != hipSuccess) { err = "estimate_point_normals: out of device memory"; return 2; }
+	char* b = scratch.get();
+	auto fail = [&](const char* what) { err = what; return 2; };
 	float* dXyz = (float*)(b + oXyz);
 	unsigned long long *keys = (unsigned long long*)(b + oKeys), *keys2 = (unsigned long long*)(b + oKeys2);
 	uint32_t *idx = (uint32_t*)(b + oIdx), *idx2 = (uint32_t*)(b + oIdx2), *first = (uint32_t*)(b + oFirst);
@@ -249,7 +248,6 @@ int pca_normals_device(unsigned long long n, const float* hXyz, const uint32_t* 
 	else hipLaunchKernelGGL(pca_normals_kernel<32>, kGrid, kBlock, 0, s, n, sorted, keys2, posOf, g, k, first, dC, dN);
 	if (hipGetLastError() != hipSuccess) return fail("estimate_point_normals: launch failed");
 	if (hipMemcpyAsync(hNormal, dN, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("estimate_point_normals: device failure");
-	(void)hipFree(b);
 	return 0;
 }
 

@@ -1,0 +1,64 @@
+/* hc-mvs_amd/csrc/dev_buf.h -- the one owner of the library's device memory: a grow-only buffer, the out-of-memory hook, the carving
+ * of one allocation into pieces */
+#ifndef HCMVS_DEV_BUF_H
+#define HCMVS_DEV_BUF_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+namespace hcmvs {
+
+// Gives device memory back when an allocation fails; returns whether it freed anything (the allocation is then tried once more)
+struct Reclaimer {
+	virtual bool reclaim() = 0;
+protected:
+	~Reclaimer() = default;
+};
+
+// A device allocation, freed when the buffer goes.  reserve() only grows: a larger request waits for the stream (work in flight
+// may still use the old allocation), frees it and allocates exactly the bytes asked for -- the contents are not kept.
+class DevBuf {
+public:
+	DevBuf() = default;
+	explicit DevBuf(Reclaimer* r) : rec_(r) {}
+	DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_), rec_(o.rec_) { o.p_ = nullptr; o.cap_ = 0; }
+	DevBuf& operator=(DevBuf&& o) noexcept {
+		if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; rec_ = o.rec_; o.p_ = nullptr; o.cap_ = 0; }
+		return *this;
+	}
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { reset(); }
+
+	hipError_t reserve(size_t bytes, hipStream_t s) {
+		if (bytes <= cap_) return hipSuccess;
+		if (p_) {
+			const hipError_t e = hipStreamSynchronize(s);
+			if (e != hipSuccess) return e;
+		}
+		reset();
+		hipError_t e = hipMalloc(&p_, bytes);
+		if (e != hipSuccess && rec_) { (void)hipGetLastError(); if (rec_->reclaim()) e = hipMalloc(&p_, bytes); }
+		if (e != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return e; }
+		cap_ = bytes;
+		return hipSuccess;
+	}
+	void reset() {
+		if (p_) (void)hipFree(p_);
+		p_ = nullptr; cap_ = 0;
+	}
+	template <class T = char> T* get() const { return (T*)p_; }
+	size_t capacity() const { return cap_; }
+
+private:
+	void* p_ = nullptr;
+	size_t cap_ = 0;
+	Reclaimer* rec_ = nullptr;
+};
+
+// Offsets of the pieces of one allocation, each rounded up to 256 bytes; size is what the allocation needs
+struct Carve {
+	size_t size = 0;
+	size_t operator()(size_t bytes) { const size_t o = size; size += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+} // namespace hcmvs
+#endif

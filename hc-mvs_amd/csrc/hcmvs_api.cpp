@@ -13,6 +13,7 @@
 #include "tri_init.h"
 #include "cloud_kernels.h"
 #include "vis_kernels.h"
+#include "dev_buf.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -31,25 +32,29 @@ namespace {
 constexpr int kMaxBatch = HCMVS_MAX_BATCH; // reference images estimated by one call
 
 struct View {
+	View() = default;
+	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r) {}
 	int w = 0, h = 0;
-	float* gray = nullptr;   // device
-	uint8_t* bgr = nullptr;  // device or null
-	uint8_t* gra = nullptr;  // device gradient map (lazy)
-	float4* quads = nullptr; // device 2 x 2 footprint layout of the gray image, built when the view first serves as a source view
-	bool owned = false;
+	float* gray = nullptr;   // device: the caller's (hcmvs_set_view_device) or grayMem
+	uint8_t* bgr = nullptr;  // device or null: the caller's or bgrMem
+	DevBuf grayMem, bgrMem;  // the copies of hcmvs_upload_view
+	DevBuf gra;              // gradient map, u8 (lazy)
+	DevBuf quads;            // float4: 2 x 2 footprint layout of the gray image, built when the view first serves as a source view
 	double K[9], R[9], C[3];
-	// estimated maps registered for filter / fuse
+	// estimated maps registered for filter / fuse: the caller's (hcmvs_set_depthmap_device) or the copies in *Mem
 	float *mDepth = nullptr, *mNormal = nullptr, *mConf = nullptr;
-	bool mapsOwned = false;
+	DevBuf depthMem, normalMem, confMem;
 	float dMin = 0.f, dMax = 0.f;
-	uint32_t* dNeighbors = nullptr;
+	DevBuf dNeighbors; // uint32_t
 	std::vector<uint32_t> neighbors;
 };
 
 } // namespace
 
 
-struct hcmvs_ctx {
+// Every device buffer of the context gives the post-filter chain's state back when memory is short (the chain allocates it again, or
+// falls back to fusions from scratch, the next time it runs) -- except that state itself.
+struct hcmvs_ctx final : Reclaimer {
 	int device = 0;
 	hipStream_t ownStream = nullptr;
 	hipStream_t stream = nullptr;
@@ -57,23 +62,22 @@ struct hcmvs_ctx {
 	std::map<uint32_t, View> views;
 	// working buffers of the batch items (grown on demand)
 	struct Slot {
-		size_t capPixels = 0; float4* dn = nullptr; float* conf = nullptr; float* tmpDepth = nullptr;
-		size_t capRows = 0; int32_t* progress = nullptr;
-		size_t capSlab = 0; char* srcSlab = nullptr; // compact copy of an item's source images when they are > 4 GiB apart
+		explicit Slot(Reclaimer* r) : dn(r), conf(r), tmpDepth(r), progress(r), srcSlab(r) {}
+		DevBuf dn, conf, tmpDepth; // float4, float, float per pixel
+		DevBuf progress;           // int32_t, kProgressStride per row
+		DevBuf srcSlab;            // compact copy of an item's source images when they are > 4 GiB apart
 	};
 	std::vector<Slot> slots;
-	size_t capPixels = 0;
-	uint8_t* tmpU8 = nullptr; // gradient-map staging
+	DevBuf tmpU8{this}; // gradient-map staging
 	// host-path staging
-	size_t capStage = 0;
-	float *sDepth = nullptr, *sNormal = nullptr, *sConf = nullptr;
-	DevView* dViews = nullptr;           // [kMaxBatch][kMaxViews]
+	DevBuf sDepth{this}, sNormal{this}, sConf{this};
+	DevBuf dViews{this};                  // DevView [kMaxBatch][kMaxViews]
 	std::vector<DevView> hViews;          // host copy handed to hipMemcpyAsync (must outlive the call)
-	EstConst* dItems = nullptr;           // [kMaxBatch]
+	DevBuf dItems{this};                  // EstConst [kMaxBatch]
 	std::vector<EstConst> hItems;
-	int32_t* sync = nullptr;              // [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
+	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
 	int sweepPerLaunch = 0;               // HCMVS_SWEEP_LAUNCHES: 0 automatic (one launch for all sweeps from 16 images on), 1 per-sweep, 2 one
-	unsigned long long* evals = nullptr;
+	DevBuf evals{this};                   // unsigned long long [4]
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	int lastSweeps = 0, lastSweepLaunches = 0;
 	bool haveStats = false;
@@ -82,16 +86,23 @@ struct hcmvs_ctx {
 	int fuseOrder = 0; // hcmvs_set_fuse_order
 	int xcdAffinity = 1; // rows of an image prefer the workgroups of one XCD (HCMVS_XCD_AFFINITY=0 turns it off)
 	// filter / fuse scratch
-	DevMap* dMaps = nullptr; size_t capMaps = 0;
-	unsigned long long* counters = nullptr;
-	void* fuseScratch = nullptr; size_t capFuseScratch = 0;
-	char* passScratch = nullptr; size_t capPass = 0; // per-pass tables of the fusion (hcmvs_fuse_cloud, hcmvs_postfilter_sequence)
-	char* pfState = nullptr; size_t capPf = 0;       // the post-filter chain's state kept from fusion to fusion (pf_kernels.hip)
+	DevBuf dMaps{this};       // DevMap per view id
+	DevBuf counters{this};    // unsigned long long [8]
+	DevBuf fuseScratch{this};
+	DevBuf passScratch{this}; // per-pass tables of the fusion (hcmvs_fuse_cloud, hcmvs_postfilter_sequence)
+	DevBuf pfState;           // the post-filter chain's state kept from fusion to fusion (pf_kernels.hip); never reserved with the reclaimer
 	bool errPending = false; // an estimate was enqueued since the error word was last read
 	int nCU = 0;          // compute units of the device: 4 SIMDs x 3 sweep workers each (the waves-per-row policy)
 	hipEvent_t upEv[2] = {nullptr, nullptr};
 	char* pinned = nullptr; size_t capPinned = 0; // page-locked staging of the host-buffer uploads (a pageable hipMemcpy crawls at ~1.3 GB/s here)
 	int wavesPerRow = 0; // 0 = automatic: 3 waves per row for one image, 2 for two (latency), 1 when >= 3 images fill the chip
+
+	bool reclaim() override {
+		if (!pfState.capacity()) return false;
+		(void)hipStreamSynchronize(stream);
+		pfState.reset();
+		return true;
+	}
 };
 
 static int fail(hcmvs_ctx* c, int code, const char* fmt, ...) {
@@ -184,14 +195,14 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	hcmvs_ctx* c = new hcmvs_ctx();
 	c->device = device;
 	c->nCU = prop.multiProcessorCount;
-	if (hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) { delete c; return HCMVS_ERR_NO_DEVICE; }
+	if (hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
 	c->stream = c->ownStream;
 	for (auto& e : c->ev)
-		if (hipEventCreate(&e) != hipSuccess) { delete c; return HCMVS_ERR_NO_DEVICE; }
+		if (hipEventCreate(&e) != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
 	c->hViews.resize((size_t)kMaxBatch * kMaxViews); c->hItems.resize(kMaxBatch);
-	if (hipMalloc(&c->dViews, sizeof(DevView) * kMaxViews * kMaxBatch) != hipSuccess || hipMalloc(&c->evals, 32) != hipSuccess ||
-	    hipMalloc(&c->dItems, sizeof(EstConst) * kMaxBatch) != hipSuccess || hipMalloc(&c->sync, 64 + sizeof(int32_t) * 2 * kMaxBatch) != hipSuccess) {
-		delete c;
+	if (c->dViews.reserve(sizeof(DevView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(32, c->stream) != hipSuccess ||
+	    c->dItems.reserve(sizeof(EstConst) * kMaxBatch, c->stream) != hipSuccess || c->sync.reserve(64 + sizeof(int32_t) * 2 * kMaxBatch, c->stream) != hipSuccess) {
+		hcmvs_destroy(c);
 		return HCMVS_ERR_NO_DEVICE;
 	}
 	const char* lag = getenv("HCMVS_SWEEP_LAG");
@@ -209,30 +220,10 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	return HCMVS_OK;
 }
 
-static void free_maps(View& v) {
-	if (v.mapsOwned) for (void* p : {(void*)v.mDepth, (void*)v.mNormal, (void*)v.mConf}) if (p) (void)hipFree(p);
-	v.mDepth = v.mNormal = v.mConf = nullptr; v.mapsOwned = false;
-}
-static void free_view(View& v) {
-	if (v.owned) { if (v.gray) (void)hipFree(v.gray); if (v.bgr) (void)hipFree(v.bgr); }
-	if (v.gra) (void)hipFree(v.gra);
-	if (v.quads) (void)hipFree(v.quads);
-	if (v.dNeighbors) (void)hipFree(v.dNeighbors);
-	free_maps(v);
-	v = View();
-}
-
 void hcmvs_destroy(hcmvs_ctx* c) {
 	if (!c) return;
 	(void)hipSetDevice(c->device);
-	(void)hipStreamSynchronize(c->stream);
-	for (auto& kv : c->views) free_view(kv.second);
-	for (auto& sl : c->slots) for (void* p : {(void*)sl.dn, (void*)sl.conf, (void*)sl.tmpDepth, (void*)sl.progress, (void*)sl.srcSlab}) if (p) (void)hipFree(p);
-	for (void* p : {(void*)c->tmpU8, (void*)c->sDepth, (void*)c->sNormal, (void*)c->sConf, (void*)c->dViews, (void*)c->dItems, (void*)c->sync,
-	                (void*)c->evals, (void*)c->dMaps, (void*)c->counters, c->fuseScratch})
-		if (p) (void)hipFree(p);
-	if (c->passScratch) (void)hipFree(c->passScratch);
-	if (c->pfState) (void)hipFree(c->pfState);
+	(void)hipStreamSynchronize(c->stream); // the stream is idle: the device buffers go with the context
 	for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	for (auto& e : c->upEv) if (e) (void)hipEventDestroy(e);
@@ -248,7 +239,7 @@ const char* hcmvs_last_error(const hcmvs_ctx* c) { return c ? c->err.c_str() : "
 static int check_sweep_error(hcmvs_ctx* c) {
 	if (!c->errPending) return HCMVS_OK;
 	int32_t flags[2] = {0, 0};
-	HIPCHK(c, hipMemcpy(flags, c->sync, sizeof flags, hipMemcpyDeviceToHost));
+	HIPCHK(c, hipMemcpy(flags, c->sync.get(), sizeof flags, hipMemcpyDeviceToHost));
 	c->errPending = false;
 	if (flags[1] != 0) return fail(c, HCMVS_ERR_TIMEOUT, "sweep worker timed out waiting for its predecessor row; the maps of the last estimate are incomplete");
 	return HCMVS_OK;
@@ -315,18 +306,20 @@ static int set_view(hcmvs_ctx* c, uint32_t id, int w, int h, const float* gray, 
 		return fail(c, HCMVS_ERR_INVALID, "upload_view: bad arguments (id %u, %dx%d)", id, w, h);
 	HIPCHK(c, hipSetDevice(c->device));
 	auto it = c->views.find(id);
-	if (it != c->views.end()) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_view(it->second); }
-	View v;
-	v.w = w; v.h = h; v.owned = copy;
+	if (it != c->views.end()) { HIPCHK(c, hipStreamSynchronize(c->stream)); it->second = View(c); } // the old buffers go before the new ones come
+	View v(c);
+	v.w = w; v.h = h;
 	const size_t n = (size_t)w * h;
 	if (copy) {
 		if (gray) {
-			HIPCHK(c, hipMalloc(&v.gray, n * sizeof(float)));
+			HIPCHK(c, v.grayMem.reserve(n * sizeof(float), c->stream));
+			v.gray = v.grayMem.get<float>();
 			const int rc = upload_staged(c, v.gray, gray, n * sizeof(float));
 			if (rc) return rc;
 		}
 		if (bgr) {
-			HIPCHK(c, hipMalloc(&v.bgr, n * 3));
+			HIPCHK(c, v.bgrMem.reserve(n * 3, c->stream));
+			v.bgr = v.bgrMem.get<uint8_t>();
 			const int rc = upload_staged(c, v.bgr, bgr, n * 3);
 			if (rc) return rc;
 		} // (upload_staged has synchronised: the caller may free its host buffers on return)
@@ -335,7 +328,7 @@ static int set_view(hcmvs_ctx* c, uint32_t id, int w, int h, const float* gray, 
 		v.bgr = const_cast<uint8_t*>(bgr);
 	}
 	memcpy(v.K, K, sizeof v.K); memcpy(v.R, R, sizeof v.R); memcpy(v.C, C, sizeof v.C);
-	c->views[id] = v;
+	c->views[id] = std::move(v);
 	return HCMVS_OK;
 }
 
@@ -352,24 +345,25 @@ int hcmvs_rescale_view(hcmvs_ctx* c, uint32_t src_id, uint32_t dst_id, float sca
 	auto it = c->views.find(src_id);
 	if (it == c->views.end() || dst_id >= 65536 || dst_id == src_id) return fail(c, HCMVS_ERR_INVALID, "rescale_view: bad view ids %u -> %u", src_id, dst_id);
 	if (!(scale > 0.f) || fabsf(scale - 1.f) < 0.15f) return fail(c, HCMVS_ERR_INVALID, "rescale_view: scale %g is within 15 %% of 1 (DepthMap.h:234: not resampled)", scale);
-	const View src = it->second;
+	const View& src = it->second;
 	if (!src.gray) return fail(c, HCMVS_ERR_INVALID, "rescale_view: view %u has no gray image (fuse-only view)", src_id);
 	// cv::resize with dsize empty: Size(saturate_cast<int>(w * fx), saturate_cast<int>(h * fy)), saturate_cast<int>(double) = cvRound
 	const int nw = (int)lrint((double)src.w * (double)scale), nh = (int)lrint((double)src.h * (double)scale);
 	if (nw < 2 * kHalfWindow + 2 || nh < 2 * kHalfWindow + 2 || nw > 32768 || nh > 32768) return fail(c, HCMVS_ERR_INVALID, "rescale_view: %dx%d x %g gives an unusable size", src.w, src.h, scale);
 	HIPCHK(c, hipSetDevice(c->device));
 	auto old = c->views.find(dst_id);
-	if (old != c->views.end()) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_view(old->second); c->views.erase(old); }
-	View v;
-	v.w = nw; v.h = nh; v.owned = true;
-	HIPCHK(c, hipMalloc(&v.gray, (size_t)nw * nh * sizeof(float)));
+	if (old != c->views.end()) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->views.erase(old); }
+	View v(c);
+	v.w = nw; v.h = nh;
+	HIPCHK(c, v.grayMem.reserve((size_t)nw * nh * sizeof(float), c->stream));
+	v.gray = v.grayMem.get<float>();
 	hcmvs::launch_resize_gray(src.gray, src.w, src.h, v.gray, nw, nh, scale, c->stream);
 	HIPCHK(c, hipGetLastError());
 	// Image::GetCamera(platforms, size): K normalised by max(w, h) of the image, scaled to max(w', h') (Camera.h:167-180)
 	const double f = (double)std::max(nw, nh) / (double)std::max(src.w, src.h);
 	memcpy(v.K, src.K, sizeof v.K); memcpy(v.R, src.R, sizeof v.R); memcpy(v.C, src.C, sizeof v.C);
 	v.K[0] *= f; v.K[4] *= f; v.K[2] *= f; v.K[5] *= f;
-	c->views[dst_id] = v;
+	c->views[dst_id] = std::move(v);
 	return HCMVS_OK;
 }
 int hcmvs_get_view_info(hcmvs_ctx* c, uint32_t id, int32_t* w, int32_t* h, double K[9]) {
@@ -397,62 +391,38 @@ int hcmvs_release_view(hcmvs_ctx* c, uint32_t id) {
 	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "release_view: unknown view %u", id);
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	free_view(it->second);
 	c->views.erase(it);
 	return HCMVS_OK;
 }
 
 static int ensure_slot(hcmvs_ctx* c, int i, size_t n, int rows) {
-	if ((int)c->slots.size() <= i) c->slots.resize((size_t)i + 1);
+	while ((int)c->slots.size() <= i) c->slots.emplace_back(c);
 	hcmvs_ctx::Slot& sl = c->slots[i];
-	if (n > sl.capPixels) {
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		for (void* p : {(void*)sl.dn, (void*)sl.conf, (void*)sl.tmpDepth}) if (p) (void)hipFree(p);
-		sl.dn = nullptr; sl.conf = nullptr; sl.tmpDepth = nullptr; sl.capPixels = 0;
-		HIPCHK(c, hipMalloc(&sl.dn, n * sizeof(float4)));
-		HIPCHK(c, hipMalloc(&sl.conf, n * sizeof(float)));
-		HIPCHK(c, hipMalloc(&sl.tmpDepth, n * sizeof(float)));
-		sl.capPixels = n;
-	}
-	if ((size_t)rows > sl.capRows) {
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		if (sl.progress) (void)hipFree(sl.progress);
-		sl.progress = nullptr; sl.capRows = 0;
-		HIPCHK(c, hipMalloc(&sl.progress, (size_t)rows * kProgressStride * sizeof(int32_t)));
-		sl.capRows = (size_t)rows;
-	}
-	return HCMVS_OK;
-}
-static int ensure_u8(hcmvs_ctx* c, size_t n) {
-	if (n > c->capPixels) {
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		if (c->tmpU8) (void)hipFree(c->tmpU8);
-		c->tmpU8 = nullptr; c->capPixels = 0;
-		HIPCHK(c, hipMalloc(&c->tmpU8, n));
-		c->capPixels = n;
-	}
+	HIPCHK(c, sl.dn.reserve(n * sizeof(float4), c->stream));
+	HIPCHK(c, sl.conf.reserve(n * sizeof(float), c->stream));
+	HIPCHK(c, sl.tmpDepth.reserve(n * sizeof(float), c->stream));
+	HIPCHK(c, sl.progress.reserve((size_t)rows * kProgressStride * sizeof(int32_t), c->stream));
 	return HCMVS_OK;
 }
 
 // SceneDensify.cpp:581-595 InitGraMap, computed once per view on the device
 static int ensure_gradient(hcmvs_ctx* c, View& v) {
-	if (v.gra) return HCMVS_OK;
+	if (v.gra.capacity()) return HCMVS_OK;
 	const int n = v.w * v.h;
-	int rc = ensure_u8(c, (size_t)n);
-	if (rc) return rc;
-	HIPCHK(c, hipMalloc(&v.gra, (size_t)n));
-	if (v.bgr) launch_bgr_to_u8(v.bgr, c->tmpU8, n, c->stream);
-	else launch_gray_to_u8(v.gray, c->tmpU8, n, c->stream);
-	launch_gradient_map(c->tmpU8, v.gra, v.w, v.h, c->stream);
+	HIPCHK(c, c->tmpU8.reserve((size_t)n, c->stream));
+	HIPCHK(c, v.gra.reserve((size_t)n, c->stream));
+	if (v.bgr) launch_bgr_to_u8(v.bgr, c->tmpU8.get<uint8_t>(), n, c->stream);
+	else launch_gray_to_u8(v.gray, c->tmpU8.get<uint8_t>(), n, c->stream);
+	launch_gradient_map(c->tmpU8.get<uint8_t>(), v.gra.get<uint8_t>(), v.w, v.h, c->stream);
 	HIPCHK(c, hipGetLastError());
 	return HCMVS_OK;
 }
 
 // the layout the scorer samples a source view from (pm_kernels.hip quad_kernel), built once per view
 static int ensure_quads(hcmvs_ctx* c, View& v) {
-	if (v.quads) return HCMVS_OK;
-	HIPCHK(c, hipMalloc(&v.quads, (size_t)v.w * v.h * sizeof(float4)));
-	launch_quads(v.gray, v.quads, v.w, v.h, c->stream);
+	if (v.quads.capacity()) return HCMVS_OK;
+	HIPCHK(c, v.quads.reserve((size_t)v.w * v.h * sizeof(float4), c->stream));
+	launch_quads(v.gray, v.quads.get<float4>(), v.w, v.h, c->stream);
 	HIPCHK(c, hipGetLastError());
 	return HCMVS_OK;
 }
@@ -464,7 +434,7 @@ int hcmvs_get_gradient_map(hcmvs_ctx* c, uint32_t id, uint8_t* out) {
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc = ensure_gradient(c, it->second);
 	if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(out, it->second.gra, (size_t)it->second.w * it->second.h, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(out, it->second.gra.get(), (size_t)it->second.w * it->second.h, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return HCMVS_OK;
 }
@@ -491,7 +461,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	if (ref.w < 2 * k.border + 2 || ref.h < 2 * k.border + 2) return fail(c, HCMVS_ERR_INVALID, "estimate: view %u (%dx%d) has no pixel inside the %d px border", it.ref_id, ref.w, ref.h, k.border);
 	k.adapthalfwin = p->adapthalfwin; k.nRandomIters = p->n_random_iters; k.itExternal = p->it_external;
 	k.propHalfwin = p->propagate_halfwin; k.propStep = p->propagate_step;
-	k.ref = ref.gray; k.gra = ref.gra; k.views = c->dViews + (size_t)slot * kMaxViews;
+	k.ref = ref.gray; k.gra = ref.gra.get<uint8_t>(); k.views = c->dViews.get<DevView>() + (size_t)slot * kMaxViews;
 	double Hr[9];
 	mat3_inv(ref.K, Hr);
 	for (int i = 0; i < 9; ++i) k.Hr[i] = (float)Hr[i];
@@ -514,7 +484,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 		mat3_mul(Hl, Hr, A);
 		for (int i = 0; i < 9; ++i) hv[v].A[i] = (float)A[i];
 		hv[v].w = s.w; hv[v].h = s.h;
-		const uintptr_t b = (uintptr_t)s.quads, e = b + (size_t)s.w * s.h * sizeof(float4);
+		const uintptr_t b = (uintptr_t)s.quads.get(), e = b + (size_t)s.w * s.h * sizeof(float4);
 		if (b < lo) lo = b;
 		if (e > hi) hi = e;
 	}
@@ -523,28 +493,18 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	// compact slab owned by the context.
 	if (hi - lo < 0xFFFF0000ull) {
 		k.imgBase = (const char*)lo;
-		for (int v = 0; v < n_src; ++v) hv[v].byteOff = (uint32_t)((uintptr_t)c->views.find(it.src_ids[v])->second.quads - lo);
+		for (int v = 0; v < n_src; ++v) hv[v].byteOff = (uint32_t)((uintptr_t)c->views.find(it.src_ids[v])->second.quads.get() - lo);
 	} else {
-		size_t total = 0;
-		for (int v = 0; v < n_src; ++v) { const View& s = c->views.find(it.src_ids[v])->second; total += ((size_t)s.w * s.h * sizeof(float4) + 255) & ~(size_t)255; }
-		if (total >= 0xFFFF0000ull) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
-		hcmvs_ctx::Slot& sl = c->slots[slot];
-		if (total > sl.capSlab) {
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			if (sl.srcSlab) (void)hipFree(sl.srcSlab);
-			sl.srcSlab = nullptr; sl.capSlab = 0;
-			HIPCHK(c, hipMalloc(&sl.srcSlab, total));
-			sl.capSlab = total;
-		}
-		size_t off = 0;
+		Carve slab;
+		for (int v = 0; v < n_src; ++v) { const View& s = c->views.find(it.src_ids[v])->second; hv[v].byteOff = (uint32_t)slab((size_t)s.w * s.h * sizeof(float4)); }
+		if (slab.size >= 0xFFFF0000ull) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
+		DevBuf& srcSlab = c->slots[slot].srcSlab;
+		HIPCHK(c, srcSlab.reserve(slab.size, c->stream));
 		for (int v = 0; v < n_src; ++v) {
 			const View& s = c->views.find(it.src_ids[v])->second;
-			const size_t bytes = (size_t)s.w * s.h * sizeof(float4);
-			HIPCHK(c, hipMemcpyAsync(sl.srcSlab + off, s.quads, bytes, hipMemcpyDeviceToDevice, c->stream));
-			hv[v].byteOff = (uint32_t)off;
-			off += (bytes + 255) & ~(size_t)255;
+			HIPCHK(c, hipMemcpyAsync(srcSlab.get() + hv[v].byteOff, s.quads.get(), (size_t)s.w * s.h * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 		}
-		k.imgBase = sl.srcSlab;
+		k.imgBase = srcSlab.get();
 	}
 	k.dMin = it.d_min; k.dMax = it.d_max; k.dMinSqr = sqrtf(it.d_min); k.dMaxSqr = sqrtf(it.d_max);
 	k.smoothBonusDepth = 1.f - p->random_smooth_bonus;
@@ -561,7 +521,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	k.depthRatio = p->random_depth_ratio;
 	k.pfScale = 1.f - p->photometric_flow;
 	k.seed = p->seed + it.seed_offset;
-	k.dn = c->slots[slot].dn; k.conf = c->slots[slot].conf; k.progress = c->slots[slot].progress;
+	k.dn = c->slots[slot].dn.get<float4>(); k.conf = c->slots[slot].conf.get<float>(); k.progress = c->slots[slot].progress.get<int32_t>();
 	k.hintDepth = nullptr; k.hintNormal = nullptr; k.hintIter = -1;
 	if (it.d_hint_depth && it.d_hint_normal && p->it_external == p->n_external_iters - 1) { // restore/libs/MVS/DepthMap.cpp:1527
 		k.hintDepth = it.d_hint_depth; k.hintNormal = it.d_hint_normal; k.hintIter = p->n_estimation_iters - 1;
@@ -589,24 +549,25 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 	}
 	hipStream_t s = c->stream;
 	// same stream => the previous call's kernels are done with these tables before the copies land
-	HIPCHK(c, hipMemcpyAsync(c->dViews, c->hViews.data(), sizeof(DevView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemcpyAsync(c->dItems, c->hItems.data(), sizeof(EstConst) * n_items, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemsetAsync(c->evals, 0, 32, s));
-	HIPCHK(c, hipMemsetAsync(c->sync, 0, 64 + sizeof(int32_t) * 2 * kMaxBatch, s));
+	HIPCHK(c, hipMemcpyAsync(c->dViews.get(), c->hViews.data(), sizeof(DevView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemcpyAsync(c->dItems.get(), c->hItems.data(), sizeof(EstConst) * n_items, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 32, s));
+	HIPCHK(c, hipMemsetAsync(c->sync.get(), 0, 64 + sizeof(int32_t) * 2 * kMaxBatch, s));
 
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
 	for (int i = 0; i < n_items; ++i) {
 		const EstConst& k = c->hItems[i];
 		const float* depthIn = items[i].d_depth;
 		if (p->median_blur) { // SceneDensify.cpp:859
-			launch_median3(items[i].d_depth, c->slots[i].tmpDepth, k.W, k.H, s);
-			depthIn = c->slots[i].tmpDepth;
+			launch_median3(items[i].d_depth, c->slots[i].tmpDepth.get<float>(), k.W, k.H, s);
+			depthIn = c->slots[i].tmpDepth.get<float>();
 		}
-		launch_score_pass(k, depthIn, items[i].d_normal, c->evals, s);
+		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s);
 	}
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
 	SweepSync sy;
-	sy.ticket = c->sync + 16; sy.rowsDone = c->sync + 16 + kMaxBatch; sy.error = c->sync + 1; sy.evals = c->evals;
+	int32_t* sync = c->sync.get<int32_t>();
+	sy.ticket = sync + 16; sy.rowsDone = sync + 16 + kMaxBatch; sy.error = sync + 1; sy.evals = c->evals.get<unsigned long long>();
 	// A batch whose rows fill the chip four times over (12 images of 1080p or more) runs all its sweeps in ONE launch (round 4): the images go
 	// through their sweeps independently of each other, without a chip-wide drain and refill between two sweeps (+5 % at 12, +7 % at 16 images,
 	// +2.6 ... 3.5 % at 32; profiles/r04_launch_modes.txt).  Fewer images are bound by the latency of their row wavefronts, not by the
@@ -636,9 +597,9 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 			int count = perSweep ? 1 : nSweeps - first;
 			bool hint = false;
 			if (hintLast) { if (first == nSweeps - 1) hint = true; else if (first + count == nSweeps) --count; } // the hint sweep runs alone
-			HIPCHK(c, hipMemsetAsync(c->sync + 16, 0, sizeof(int32_t) * 2 * kMaxBatch, s)); // tickets + rowsDone; the error word stays sticky
+			HIPCHK(c, hipMemsetAsync(sync + 16, 0, sizeof(int32_t) * 2 * kMaxBatch, s)); // tickets + rowsDone; the error word stays sticky
 			for (int i = 0; i < n_items; ++i)
-				HIPCHK(c, hipMemsetAsync(c->slots[i].progress, 0, (size_t)(c->hItems[i].H - 2 * c->hItems[i].border) * kProgressStride * sizeof(int32_t), s));
+				HIPCHK(c, hipMemsetAsync(c->slots[i].progress.get(), 0, (size_t)(c->hItems[i].H - 2 * c->hItems[i].border) * kProgressStride * sizeof(int32_t), s));
 			// A launch of ONE sweep with more waves than the chip holds workers (and less than four times as many rows: from there on all
 			// sweeps run in one launch) hands out stretches of 256 columns instead of whole rows: a worker's slot comes free after 256 pixels.
 			// With whole rows the rows beyond the resident set begin only when row 0 has reached its end -- 8 images: 107.2 -> 100.3 ms per
@@ -655,7 +616,7 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 					tickets += rows * ((cols + segLen - 1) / segLen);
 				}
 			}
-			launch_sweep(c->dItems, n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
+			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
 			first += count; ++nLaunches;
 		}
 		c->lastSweepLaunches = nLaunches;
@@ -687,7 +648,7 @@ int hcmvs_get_stats(hcmvs_ctx* c, hcmvs_stats* out) {
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	unsigned long long ev[4] = {0, 0, 0, 0};
-	HIPCHK(c, hipMemcpy(ev, c->evals, 32, hipMemcpyDeviceToHost));
+	HIPCHK(c, hipMemcpy(ev, c->evals.get(), 32, hipMemcpyDeviceToHost));
 	out->evals = ev[0];
 	out->evals_issued = ev[1];
 	out->tap_evals = ev[2];
@@ -710,24 +671,19 @@ int hcmvs_estimate(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* src_ids, int32
 	if (rit == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "estimate: unknown reference view %u", ref_id);
 	HIPCHK(c, hipSetDevice(c->device));
 	const size_t n = (size_t)rit->second.w * rit->second.h;
-	if (n > c->capStage) {
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		for (void* q : {(void*)c->sDepth, (void*)c->sNormal, (void*)c->sConf}) if (q) (void)hipFree(q);
-		c->sDepth = c->sNormal = c->sConf = nullptr; c->capStage = 0;
-		HIPCHK(c, hipMalloc(&c->sDepth, n * 4));
-		HIPCHK(c, hipMalloc(&c->sNormal, n * 12));
-		HIPCHK(c, hipMalloc(&c->sConf, n * 4));
-		c->capStage = n;
-	}
 	hipStream_t s = c->stream;
-	HIPCHK(c, hipMemcpyAsync(c->sDepth, depth, n * 4, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemcpyAsync(c->sNormal, normal, n * 12, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemcpyAsync(c->sConf, conf, n * 4, hipMemcpyHostToDevice, s));
-	int rc = hcmvs_estimate_device(c, ref_id, src_ids, n_src, p, d_min, d_max, c->sDepth, c->sNormal, c->sConf);
+	HIPCHK(c, c->sDepth.reserve(n * 4, s));
+	HIPCHK(c, c->sNormal.reserve(n * 12, s));
+	HIPCHK(c, c->sConf.reserve(n * 4, s));
+	float *sDepth = c->sDepth.get<float>(), *sNormal = c->sNormal.get<float>(), *sConf = c->sConf.get<float>();
+	HIPCHK(c, hipMemcpyAsync(sDepth, depth, n * 4, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemcpyAsync(sNormal, normal, n * 12, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemcpyAsync(sConf, conf, n * 4, hipMemcpyHostToDevice, s));
+	int rc = hcmvs_estimate_device(c, ref_id, src_ids, n_src, p, d_min, d_max, sDepth, sNormal, sConf);
 	if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(depth, c->sDepth, n * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipMemcpyAsync(normal, c->sNormal, n * 12, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipMemcpyAsync(conf, c->sConf, n * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipMemcpyAsync(depth, sDepth, n * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipMemcpyAsync(normal, sNormal, n * 12, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipMemcpyAsync(conf, sConf, n * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipStreamSynchronize(s));
 	hcmvs_stats st;
 	return hcmvs_get_stats(c, &st); // surfaces a sweep timeout as an error
@@ -842,20 +798,22 @@ static int set_maps(hcmvs_ctx* c, uint32_t id, const float* depth, const float* 
 	View& v = it->second;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	free_maps(v);
+	v.mDepth = v.mNormal = v.mConf = nullptr;
+	v.depthMem.reset(); v.normalMem.reset(); v.confMem.reset(); // the old maps go before the new ones come
 	const size_t n = (size_t)v.w * v.h;
 	if (copy) {
-		HIPCHK(c, hipMalloc(&v.mDepth, n * 4));
-		HIPCHK(c, hipMalloc(&v.mConf, n * 4));
+		HIPCHK(c, v.depthMem.reserve(n * 4, c->stream));
+		HIPCHK(c, v.confMem.reserve(n * 4, c->stream));
+		v.mDepth = v.depthMem.get<float>(); v.mConf = v.confMem.get<float>();
 		int rc = upload_staged(c, v.mDepth, depth, n * 4);
 		if (!rc) rc = upload_staged(c, v.mConf, conf, n * 4);
 		if (rc) return rc;
 		if (normal) {
-			HIPCHK(c, hipMalloc(&v.mNormal, n * 12));
+			HIPCHK(c, v.normalMem.reserve(n * 12, c->stream));
+			v.mNormal = v.normalMem.get<float>();
 			rc = upload_staged(c, v.mNormal, normal, n * 12);
 			if (rc) return rc;
 		}
-		v.mapsOwned = true;
 	} else {
 		v.mDepth = const_cast<float*>(depth); v.mNormal = const_cast<float*>(normal); v.mConf = const_cast<float*>(conf);
 	}
@@ -888,11 +846,11 @@ int hcmvs_set_neighbors(hcmvs_ctx* c, uint32_t id, const uint32_t* ids, int32_t 
 	View& v = it->second;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	if (v.dNeighbors) { (void)hipFree(v.dNeighbors); v.dNeighbors = nullptr; }
+	v.dNeighbors.reset();
 	v.neighbors.assign(ids, ids + n);
 	if (n > 0) {
-		HIPCHK(c, hipMalloc(&v.dNeighbors, (size_t)n * 4));
-		HIPCHK(c, hipMemcpy(v.dNeighbors, ids, (size_t)n * 4, hipMemcpyHostToDevice));
+		HIPCHK(c, v.dNeighbors.reserve((size_t)n * 4, c->stream));
+		HIPCHK(c, hipMemcpy(v.dNeighbors.get(), ids, (size_t)n * 4, hipMemcpyHostToDevice));
 	}
 	return HCMVS_OK;
 }
@@ -908,7 +866,7 @@ static void fill_devmap(uint32_t id, const View& v, DevMap& m) {
 		m.P[i * 4 + 3] = v.K[i * 3] * t[0] + v.K[i * 3 + 1] * t[1] + v.K[i * 3 + 2] * t[2];
 	}
 	m.depth = v.mDepth; m.normal = v.mNormal; m.conf = v.mConf; m.bgr = v.bgr;
-	m.neighbors = v.dNeighbors; m.dMin = v.dMin; m.dMax = v.dMax;
+	m.neighbors = v.dNeighbors.get<uint32_t>(); m.dMin = v.dMin; m.dMax = v.dMax;
 }
 // device table indexed by image id (views without maps have depth == null)
 static int build_map_table(hcmvs_ctx* c, std::vector<DevMap>& host) {
@@ -917,35 +875,9 @@ static int build_map_table(hcmvs_ctx* c, std::vector<DevMap>& host) {
 	host.assign((size_t)maxId + 1, DevMap());
 	for (auto& m : host) memset(&m, 0, sizeof m);
 	for (auto& kv : c->views) fill_devmap(kv.first, kv.second, host[kv.first]);
-	if (host.size() > c->capMaps) {
-		if (c->dMaps) (void)hipFree(c->dMaps);
-		c->dMaps = nullptr; c->capMaps = 0;
-		HIPCHK(c, hipMalloc(&c->dMaps, host.size() * sizeof(DevMap)));
-		c->capMaps = host.size();
-	}
-	HIPCHK(c, hipMemcpy(c->dMaps, host.data(), host.size() * sizeof(DevMap), hipMemcpyHostToDevice));
-	if (!c->counters) HIPCHK(c, hipMalloc(&c->counters, 8 * sizeof(unsigned long long)));
-	return HCMVS_OK;
-}
-// hipMalloc that gives the post-filter chain's state back to the device when memory is short (the chain allocates it again, or falls
-// back to fusions from scratch, the next time it runs)
-static hipError_t malloc_or_release_chain(hcmvs_ctx* c, void** p, size_t bytes) {
-	hipError_t e = hipMalloc(p, bytes);
-	if (e != hipSuccess && c->pfState) {
-		(void)hipGetLastError();
-		(void)hipStreamSynchronize(c->stream);
-		(void)hipFree(c->pfState);
-		c->pfState = nullptr; c->capPf = 0;
-		e = hipMalloc(p, bytes);
-	}
-	return e;
-}
-static int ensure_scratch(hcmvs_ctx* c, size_t bytes) {
-	if (bytes <= c->capFuseScratch) return HCMVS_OK;
-	if (c->fuseScratch) (void)hipFree(c->fuseScratch);
-	c->fuseScratch = nullptr; c->capFuseScratch = 0;
-	HIPCHK(c, malloc_or_release_chain(c, &c->fuseScratch, bytes));
-	c->capFuseScratch = bytes;
+	HIPCHK(c, c->dMaps.reserve(host.size() * sizeof(DevMap), c->stream));
+	HIPCHK(c, hipMemcpy(c->dMaps.get(), host.data(), host.size() * sizeof(DevMap), hipMemcpyHostToDevice));
+	HIPCHK(c, c->counters.reserve(8 * sizeof(unsigned long long), c->stream));
 	return HCMVS_OK;
 }
 
@@ -970,23 +902,22 @@ int hcmvs_filter(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* nbr, int32_t N, 
 	const size_t area = (size_t)ref.w * ref.h;
 	// scratch: keys [N*area u64] | neighbour table | new depth | new conf
 	const size_t offNb = area * N * 8, offD = offNb + ((sizeof(DevMap) * N + 255) & ~(size_t)255), offC = offD + area * 4;
-	rc = ensure_scratch(c, offC + area * 4);
-	if (rc) return rc;
-	char* base = (char*)c->fuseScratch;
+	HIPCHK(c, c->fuseScratch.reserve(offC + area * 4, c->stream));
+	char* base = c->fuseScratch.get();
 	unsigned long long* keys = (unsigned long long*)base;
 	DevMap* dNbs = (DevMap*)(base + offNb);
 	float* dD = (float*)(base + offD); float* dC = (float*)(base + offC);
 	hipStream_t s = c->stream;
 	HIPCHK(c, hipMemcpyAsync(dNbs, nbs.data(), sizeof(DevMap) * N, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemsetAsync(c->counters, 0, 64, s));
+	HIPCHK(c, hipMemsetAsync(c->counters.get(), 0, 64, s));
 	launch_fill_u64(keys, ~0ull, area * N, s);
 	for (int n = 0; n < N; ++n) launch_filter_splat(ref, nbs[n], keys + area * n, s);
-	launch_filter_vote(ref, dNbs, N, keys, adjust, n_min_views, n_min_views_adjust, depth_diff_threshold, dD, dC, c->counters, s);
+	launch_filter_vote(ref, dNbs, N, keys, adjust, n_min_views, n_min_views_adjust, depth_diff_threshold, dD, dC, c->counters.get<unsigned long long>(), s);
 	HIPCHK(c, hipGetLastError());
 	HIPCHK(c, hipMemcpyAsync(out_depth, dD, area * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipMemcpyAsync(out_conf, dC, area * 4, hipMemcpyDeviceToHost, s));
 	unsigned long long cnt[2] = {0, 0};
-	HIPCHK(c, hipMemcpyAsync(cnt, c->counters, 16, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipMemcpyAsync(cnt, c->counters.get(), 16, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipStreamSynchronize(s));
 	if (n_processed) *n_processed = cnt[0];
 	if (n_discarded) *n_discarded = cnt[1];
@@ -1026,7 +957,7 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 		if (host[order[i]].nNeighbors > kFuseMaxViews - 1) return fail(c, HCMVS_ERR_INVALID, "fuse: view %u has too many neighbours", order[i]);
 	}
 	hipStream_t s = c->stream;
-	launch_unclaim(c->dMaps, (int)host.size(), s); // no claim mark may be left over from a fusion that failed half way
+	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // no claim mark may be left over from a fusion that failed half way
 	int maxNb = 1;
 	size_t stride = maxArea; // pixels reserved per neighbour map in the per-target tables
 	for (int i = 0; i < n_order; ++i) maxNb = std::max(maxNb, (int)host[order[i]].nNeighbors);
@@ -1035,31 +966,24 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 	if (stride >= ((size_t)1 << 29)) return fail(c, HCMVS_ERR_CAPACITY, "fuse: maps of %zu pixels exceed the target tables (2^29 pixels)", stride);
 	if (tblElems > 0x7FFFFFFFull) return fail(c, HCMVS_ERR_CAPACITY, "fuse: %d neighbours of %zu pixels exceed the per-pass tables", maxNb, stride);
 	const size_t scanBytes = (fuse_scan_temp_bytes((int)maxArea) + 255) & ~(size_t)255;
-	size_t off = 0;
-	auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	Carve carve;
 	// the device cloud (context scratch) ...
 	const size_t oCX = carve(wantCloud ? capacity * 12 : 0), oCN = carve(normal ? capacity * 12 : 0), oCB = carve(bgr ? capacity * 3 : 0),
 	             oCV = carve(n_views || viewCapacity ? capacity * 4 : 0), oCVI = carve(viewCapacity * 4), oCVW = carve(viewCapacity * 4);
-	rc = ensure_scratch(c, std::max(off, (size_t)256));
-	if (rc) return rc;
-	char* cb = (char*)c->fuseScratch;
+	HIPCHK(c, c->fuseScratch.reserve(std::max(carve.size, (size_t)256), s));
+	char* cb = c->fuseScratch.get();
 	float* cX = (float*)(cb + oCX); float* cN = normal ? (float*)(cb + oCN) : nullptr; uint8_t* cB = bgr ? (uint8_t*)(cb + oCB) : nullptr;
 	uint32_t* cV = n_views || viewCapacity ? (uint32_t*)(cb + oCV) : nullptr;
 	uint32_t* cVI = viewCapacity ? (uint32_t*)(cb + oCVI) : nullptr; float* cVW = viewCapacity ? (float*)(cb + oCVW) : nullptr;
 	// ... and the per-pass tables (sized for the largest image)
-	off = 0;
+	carve = Carve();
 	const size_t oPending = carve(maxArea * 4), oSettle = carve(fuse_settle_bytes(maxArea)), oTgt = carve(maxArea * 4 * (size_t)maxNb),
 	             oHead = carve(tblElems * 4), oNext = carve(maxArea * 4 * (size_t)maxNb), oCtl = carve(kCtlBytes), oCounters = carve(64), oStatus = carve(64), oTotals = carve(64),
 	             oMerged = carve(maxArea * 4), oFlag = carve(maxArea), oFlag32 = carve(maxArea * 4), oPos = carve(maxArea * 4), oScan = carve(scanBytes),
 	             oXyz = carve(maxArea * 12), oNrm = carve(maxArea * 12), oBgr = carve(maxArea * 3), oNv = carve(maxArea * 4),
 	             oPV = carve(viewCapacity ? maxArea * 4 * (size_t)(maxNb + 1) : 0), oPW = carve(viewCapacity ? maxArea * 4 * (size_t)(maxNb + 1) : 0),
 	             oVoff = carve(viewCapacity ? maxArea * 4 : 0);
-	if (c->capPass < off) {
-		if (c->passScratch) (void)hipFree(c->passScratch);
-		c->passScratch = nullptr; c->capPass = 0;
-		HIPCHK(c, malloc_or_release_chain(c, (void**)&c->passScratch, off));
-		c->capPass = off;
-	}
+	HIPCHK(c, c->passScratch.reserve(carve.size, s));
 	const int vstride = maxNb + 1;
 	const float normalError = cosf(normal_diff_deg * normalweight * (3.14159274101257324f / 180.f)); // SceneDensify.cpp:3310
 	const float thDepth = depth_diff_threshold * depthweight;                                       // SceneDensify.cpp:3400
@@ -1069,7 +993,7 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 	// order of the sequential loop, SceneDensify.cpp:3302).  What the host would have to know in between stays on the device: the
 	// running point / view-entry totals an image's compaction starts from (fuse_advance_kernel), and the word that says a cloud or
 	// view-list capacity was exceeded.
-	char* b = c->passScratch;
+	char* b = c->passScratch.get();
 	uint32_t* pendingList = (uint32_t*)(b + oPending); uint32_t* ctl = (uint32_t*)(b + oCtl);
 	unsigned long long* counters = (unsigned long long*)(b + oCounters);
 	uint32_t* status = (uint32_t*)(b + oStatus);
@@ -1092,8 +1016,8 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 		HIPCHK(c, hipMemsetAsync(counters, 0, 64, s));
 		HIPCHK(c, hipMemsetAsync(ctl, 0, kCtlBytes, s));
 		HIPCHK(c, hipMemsetAsync(head, 0xFF, (size_t)A.nNeighbors * stride * 4, s)); // empty bidder lists
-		launch_fuse_begin(A, c->dMaps, tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
-		launch_fuse_pass(A, c->dMaps, tb, pendingList, b + oSettle, ctl, pxyz, cN ? pnrm : nullptr, cB ? pbgr : nullptr, pnv, flag, pviews, pweights, vstride,
+		launch_fuse_begin(A, c->dMaps.get<DevMap>(), tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
+		launch_fuse_pass(A, c->dMaps.get<DevMap>(), tb, pendingList, b + oSettle, ctl, pxyz, cN ? pnrm : nullptr, cB ? pbgr : nullptr, pnv, flag, pviews, pweights, vstride,
 		                 merged, n_min_views_fuse, c->fuseOrder, counters, status, wantCloud, s);
 		if (wantCloud)
 			launch_fuse_compact(n, flag, flag32, pos, b + oScan, scanBytes, pxyz, pnrm, pbgr, pnv, 0, capacity, cX, cN, cB, cV, pviews, pweights, vstride,
@@ -1110,7 +1034,7 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 			fprintf(stderr, "; %.0f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tPass).count());
 		}
 	}
-	launch_unclaim(c->dMaps, (int)host.size(), s); // the claim marks come off the depth maps
+	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // the claim marks come off the depth maps
 	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
 	unsigned long long tot[3] = {0, 0, 0};
@@ -1172,8 +1096,8 @@ static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>&
 	std::vector<int> orderIndex(host.size(), -1);
 	for (int i = 0; i < n_order; ++i) { if (orderIndex[order[i]] >= 0) return -1; orderIndex[order[i]] = i; }
 	// layout of the state
-	size_t off = 0, maxArea = 0, maxIdArea = 0;
-	auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	size_t maxArea = 0, maxIdArea = 0;
+	Carve carve;
 	struct Lay { size_t own, chg, val, tgt, head, next, acc, mm, fm, stamp, touch, stride; };
 	std::vector<Lay> lay(host.size());
 	for (size_t id = 0; id < host.size(); ++id) {
@@ -1200,17 +1124,16 @@ static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>&
 	const size_t oAny = carve(host.size() * 4);
 	const size_t oTable = carve(host.size() * sizeof(PfImage)), oScratch = carve(pf_pass_scratch_bytes(maxArea)), oCtl = carve(kCtlBytes), oCounters = carve(64),
 	             oStatus = carve(64), oDF = carve(maxIdArea * 4), oDF2 = carve(maxIdArea * 4), oNF = carve(maxIdArea * 12);
-	if (c->capPf < off) {
+	const size_t off = carve.size, held = c->pfState.capacity();
+	if (held < off) {
 		size_t freeB = 0, totalB = 0;
 		if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return -1;
-		if (off > freeB + c->capPf || off > (freeB + c->capPf) / 10 * 9) { (void)hipGetLastError(); return -1; } // does not fit (with a margin): fuse from scratch
-		if (c->pfState) (void)hipFree(c->pfState);
-		c->pfState = nullptr; c->capPf = 0;
-		if (hipMalloc(&c->pfState, off) != hipSuccess) { (void)hipGetLastError(); return -1; }
-		c->capPf = off;
+		if (off > freeB + held || off > (freeB + held) / 10 * 9) { (void)hipGetLastError(); return -1; } // does not fit (with a margin): fuse from scratch
+		if (c->pfState.reserve(off, c->stream) != hipSuccess) return -1;
 	}
 	if (getenv("HCMVS_FUSE_DEBUG")) fprintf(stderr, "postfilter: chain of %d images, fusions computed incrementally (%.1f MB of state kept between them)\n", n_ids, off / 1048576.0);
-	char* b = c->pfState;
+	// from here on nothing may allocate through the reclaimer: it would free pfState under the pointers below
+	char* b = c->pfState.get();
 	hipStream_t s = c->stream;
 	std::vector<PfImage> pf(host.size());
 	memset(pf.data(), 0, pf.size() * sizeof(PfImage));
@@ -1243,11 +1166,11 @@ static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>&
 	HIPCHK(c, hipMemsetAsync(counters, 0, 64, s));
 	const float normalError = cosf(normal_diff_deg * (3.14159274101257324f / 180.f)); // plain thresholds (SceneDensify.cpp:2083, 2177)
 	for (int k = 0; k < n_ids; ++k) {
-		if (k > 0) launch_pf_roll(c->dMaps, dPf, (int)host.size(), (uint32_t*)(b + oAny), s);
+		if (k > 0) launch_pf_roll(c->dMaps.get<DevMap>(), dPf, (int)host.size(), (uint32_t*)(b + oAny), s);
 		for (int oi = 0; oi < n_order; ++oi)
-			launch_pf_pass(host[order[oi]], oi, c->dMaps, dPf, pf[order[oi]], k == 0, depth_diff_threshold, normalError, n_min_views_fuse, (uint32_t)k, b + oScratch, ctl, status, s);
+			launch_pf_pass(host[order[oi]], oi, c->dMaps.get<DevMap>(), dPf, pf[order[oi]], k == 0, depth_diff_threshold, normalError, n_min_views_fuse, (uint32_t)k, b + oScratch, ctl, status, s);
 		View& v = c->views.find(ids[k])->second;
-		launch_pf_filter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, pf[ids[k]], v.gra, dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
+		launch_pf_filter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, pf[ids[k]], v.gra.get<uint8_t>(), dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
 	}
 	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
@@ -1293,22 +1216,16 @@ int hcmvs_postfilter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, 
 	// a chain of two or more images: every fusion after the first is computed incrementally when the state fits the device
 	// (HCMVS_PF_FULL=1: every fusion from scratch, the path of rounds 1-3, kept as the fall-back and for comparison)
 	if (n_ids >= 2 && !getenv("HCMVS_PF_FULL")) {
-		launch_unclaim(c->dMaps, (int)host.size(), c->stream); // no claim mark may be left over from a fusion that failed half way
+		launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), c->stream); // no claim mark may be left over from a fusion that failed half way
 		rc = postfilter_chain_incremental(c, host, ids, n_ids, order, n_order, n_min_views_fuse, depth_diff_threshold, normal_diff_deg, gap_size, n_filled);
 		if (rc >= 0) return rc;
 	}
-	size_t off = 0;
-	auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	Carve carve;
 	const size_t oPending = carve(maxArea * 4), oSettle = carve(fuse_settle_bytes(maxArea)), oTgt = carve(maxArea * 4 * (size_t)maxNb),
 	             oHead = carve(tblElems * 4), oNext = carve(maxArea * 4 * (size_t)maxNb), oCtl = carve(kCtlBytes), oCounters = carve(64), oStatus = carve(64),
 	             oMerged = carve(maxArea * 4), oFlag = carve(maxArea), oNv = carve(maxArea * 4), oDF = carve(maxIdArea * 4), oDF2 = carve(maxIdArea * 4), oNF = carve(maxIdArea * 12);
-	if (c->capPass < off) {
-		if (c->passScratch) (void)hipFree(c->passScratch);
-		c->passScratch = nullptr; c->capPass = 0;
-		HIPCHK(c, malloc_or_release_chain(c, (void**)&c->passScratch, off));
-		c->capPass = off;
-	}
-	char* b = c->passScratch;
+	HIPCHK(c, c->passScratch.reserve(carve.size, c->stream));
+	char* b = c->passScratch.get();
 	uint32_t* pendingList = (uint32_t*)(b + oPending); uint32_t* ctl = (uint32_t*)(b + oCtl);
 	unsigned long long* counters = (unsigned long long*)(b + oCounters);
 	uint32_t* status = (uint32_t*)(b + oStatus);
@@ -1320,7 +1237,7 @@ int hcmvs_postfilter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, 
 	const float thDepth = depth_diff_threshold;
 	const FuseTables tb = fuse_tables(targets, head, next, stride);
 	hipStream_t s = c->stream;
-	launch_unclaim(c->dMaps, (int)host.size(), s); // no claim mark may be left over from a fusion or post-filter that failed half way
+	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // no claim mark may be left over from a fusion or post-filter that failed half way
 	HIPCHK(c, hipMemsetAsync(status, 0, 64, s));
 	HIPCHK(c, hipMemsetAsync(counters, 0, 64, s)); // counters[5]: pixels filled, summed over the sequence
 	for (int k = 0; k < n_ids; ++k) {
@@ -1329,13 +1246,13 @@ int hcmvs_postfilter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, 
 			const DevMap& A = host[order[oi]];
 			HIPCHK(c, hipMemsetAsync(ctl, 0, kCtlBytes, s));
 			HIPCHK(c, hipMemsetAsync(head, 0xFF, (size_t)A.nNeighbors * stride * 4, s)); // empty bidder lists
-			launch_fuse_begin(A, c->dMaps, tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
+			launch_fuse_begin(A, c->dMaps.get<DevMap>(), tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
 			// the fork's RemoveSmallSegments visits the pixels in raster order (SceneDensify.cpp:2130-2131), whatever hcmvs_set_fuse_order says
 			// about FuseDepthMaps
-			launch_fuse_pass(A, c->dMaps, tb, pendingList, b + oSettle, ctl, nullptr, nullptr, nullptr, pnv, flag, nullptr, nullptr, maxNb + 1, merged, n_min_views_fuse,
+			launch_fuse_pass(A, c->dMaps.get<DevMap>(), tb, pendingList, b + oSettle, ctl, nullptr, nullptr, nullptr, pnv, flag, nullptr, nullptr, maxNb + 1, merged, n_min_views_fuse,
 			                 0, counters, status, false, s);
 		}
-		launch_postfilter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, c->dMaps, (int)host.size(), v.gra, dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
+		launch_postfilter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, c->dMaps.get<DevMap>(), (int)host.size(), v.gra.get<uint8_t>(), dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
 	}
 	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
@@ -1344,7 +1261,7 @@ int hcmvs_postfilter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, 
 	HIPCHK(c, hipMemcpyAsync(cnt, counters, 48, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipStreamSynchronize(s));
 	if (st[0] != 0) {
-		launch_unclaim(c->dMaps, (int)host.size(), s); // an estimate or a saved map must never see a claim mark (negative depth)
+		launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // an estimate or a saved map must never see a claim mark (negative depth)
 		(void)hipStreamSynchronize(s);
 		return fail(c, HCMVS_ERR_TIMEOUT, "postfilter: the settle iteration of a fusion pass gave up; the registered depth maps are left partially fused");
 	}
@@ -1370,18 +1287,16 @@ int hcmvs_estimate_point_colors(hcmvs_ctx* c, uint64_t n, const float* xyz, cons
 	for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + n_views[i];
 	for (unsigned long long k = 0; k < off[n]; ++k)
 		if (view_ids[k] >= host.size() || !c->views.count(view_ids[k])) return fail(c, HCMVS_ERR_INVALID, "estimate_point_colors: unknown view %u", view_ids[k]);
-	float* dX = nullptr; unsigned long long* dOff = nullptr; uint32_t* dV = nullptr; uint8_t* dC = nullptr;
-	auto freeAll = [&]() { for (void* p : {(void*)dX, (void*)dOff, (void*)dV, (void*)dC}) if (p) (void)hipFree(p); };
-	if (hipMalloc(&dX, n * 12) != hipSuccess || hipMalloc(&dOff, (n + 1) * 8) != hipSuccess || hipMalloc(&dV, std::max<unsigned long long>(off[n], 1) * 4) != hipSuccess ||
-	    hipMalloc(&dC, n * 3) != hipSuccess) { freeAll(); return fail(c, HCMVS_ERR_HIP, "estimate_point_colors: out of device memory"); }
 	hipStream_t s = c->stream;
-	(void)hipMemcpyAsync(dX, xyz, n * 12, hipMemcpyHostToDevice, s);
-	(void)hipMemcpyAsync(dOff, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s);
-	(void)hipMemcpyAsync(dV, view_ids, off[n] * 4, hipMemcpyHostToDevice, s);
-	launch_point_colors(n, dX, dOff, dV, c->dMaps, dC, s);
-	const hipError_t e1 = hipMemcpyAsync(bgr, dC, n * 3, hipMemcpyDeviceToHost, s);
+	DevBuf dX(c), dOff(c), dV(c), dC(c); // freed on return
+	if (dX.reserve(n * 12, s) != hipSuccess || dOff.reserve((n + 1) * 8, s) != hipSuccess || dV.reserve(std::max<unsigned long long>(off[n], 1) * 4, s) != hipSuccess ||
+	    dC.reserve(n * 3, s) != hipSuccess) return fail(c, HCMVS_ERR_HIP, "estimate_point_colors: out of device memory");
+	(void)hipMemcpyAsync(dX.get(), xyz, n * 12, hipMemcpyHostToDevice, s);
+	(void)hipMemcpyAsync(dOff.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s);
+	(void)hipMemcpyAsync(dV.get(), view_ids, off[n] * 4, hipMemcpyHostToDevice, s);
+	launch_point_colors(n, dX.get<float>(), dOff.get<unsigned long long>(), dV.get<uint32_t>(), c->dMaps.get<DevMap>(), dC.get<uint8_t>(), s);
+	const hipError_t e1 = hipMemcpyAsync(bgr, dC.get(), n * 3, hipMemcpyDeviceToHost, s);
 	const hipError_t e2 = hipStreamSynchronize(s);
-	freeAll();
 	if (e1 != hipSuccess || e2 != hipSuccess || hipGetLastError() != hipSuccess) return fail(c, HCMVS_ERR_HIP, "estimate_point_colors: device failure");
 	return HCMVS_OK;
 }
@@ -1405,7 +1320,8 @@ int hcmvs_estimate_point_normals(hcmvs_ctx* c, uint64_t n, const float* xyz, con
 		off += n_views[i];
 	}
 	std::string err;
-	const int rc = hcmvs::pca_normals_device(n, xyz, first.data(), centres.data(), (size_t)maxId + 1, k, normal, c->stream, err);
+	DevBuf scratch(c); // freed on return
+	const int rc = hcmvs::pca_normals_device(n, xyz, first.data(), centres.data(), (size_t)maxId + 1, k, normal, scratch, c->stream, err);
 	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
 	return HCMVS_OK;
 }
@@ -1422,7 +1338,8 @@ int hcmvs_point_cloud_filter(hcmvs_ctx* c, uint64_t n, const float* xyz, const u
 	std::vector<int32_t> vis(n);
 	hcmvs::VisCounters st;
 	std::string err;
-	const int rc = hcmvs::point_cloud_visibility_device(n, xyz, n_views, view_ids, n_images, wh, K, R, C, vis.data(), st, c->stream, err);
+	DevBuf scratch(c); // freed on return
+	const int rc = hcmvs::point_cloud_visibility_device(n, xyz, n_views, view_ids, n_images, wh, K, R, C, vis.data(), st, scratch, c->stream, err);
 	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
 	// RFOREACH + PointCloud::RemovePoint -> cList::RemoveAt (List.h:1070-1077): the last point moves into the hole.  Position i still holds
 	// point i when the loop reaches it, so the permutation is order[i] = order[--size] for every removed i, from the back

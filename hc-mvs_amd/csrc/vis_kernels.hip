@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void fallback_kernel(const uint32_t* fbList, u
 
 int point_cloud_visibility_device(unsigned long long n, const float* hXyz, const uint32_t* hNViews, const uint32_t* hViewIds, uint32_t nImages,
                                   const int32_t* wh, const double* K, const double* R, const double* C, int32_t* hVis, VisCounters& st,
-                                  hipStream_t s, std::string& err) {
+                                  DevBuf& scratch, hipStream_t s, std::string& err) {
 	st = VisCounters();
 	if (n == 0) return 0;
 	if (n >= 0xFFFFFFFFull) { err = "point_cloud_filter: 2^32 - 1 points or more"; return 1; }
@@ -222,20 +222,18 @@ int point_cloud_visibility_device(unsigned long long n, const float* hXyz, const
 	}
 	size_t scanBytes = 0;
 	(void)hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(maxCells + 1));
-	size_t off = 0;
-	auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	Carve carve;
 	const size_t oXyz = carve(n * 12), oNv = carve(n * 4), oVis = carve(n * 4), oKeys = carve(n * 4), oBinned = carve(n * 16),
 	             oPairs = carve(pairs.size() * 4), oFb = carve(maxPairs * 4), oOffsets = carve((maxCells + 1) * 4), oCounts = carve((maxCells + 1) * 4),
 	             oCounters = carve(64), oScan = carve(scanBytes);
-	char* b = nullptr;
-	if (hipMalloc(&b, off) != hipSuccess) { (void)hipGetLastError(); err = "point_cloud_filter: out of device memory"; return 2; }
-	st.deviceBytes = off;
+	if (scratch.reserve(carve.size, s) != hipSuccess) { err = "point_cloud_filter: out of device memory"; return 2; }
+	char* b = scratch.get();
+	st.deviceBytes = carve.size;
 	hipEvent_t ev[2] = {nullptr, nullptr};
 	auto fail = [&](const char* what) {
 		err = what;
-		(void)hipStreamSynchronize(s);
+		(void)hipStreamSynchronize(s); // (the caller frees scratch on return)
 		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-		(void)hipFree(b);
 		return 2;
 	};
 	if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) return fail("point_cloud_filter: event creation failed");
@@ -277,7 +275,6 @@ int point_cloud_visibility_device(unsigned long long n, const float* hXyz, const
 	st.candidates = hc[0]; st.hits = hc[1]; st.fallback = hc[2];
 	(void)hipEventElapsedTime(&st.ms, ev[0], ev[1]);
 	for (auto& e : ev) (void)hipEventDestroy(e);
-	(void)hipFree(b);
 	return 0;
 }
 
