@@ -63,7 +63,8 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
-           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up"]
+           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
+           "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -122,6 +123,10 @@ def lib():
         L.hcmvs_get_view_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
         L.hcmvs_get_view_gray.argtypes = [vp, C.c_uint32, fp]
         L.hcmvs_get_gradient_map.argtypes = [vp, C.c_uint32, u8p]
+        i32p = C.POINTER(C.c_int32)
+        L.hcmvs_set_ignore_mask.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint16), C.c_int32, C.c_int32, i32p, C.c_int32]
+        L.hcmvs_set_ignore_mask_device.argtypes = [vp, C.c_uint32, vp, C.c_int32, C.c_int32, i32p, C.c_int32]
+        L.hcmvs_get_ignore_mask.argtypes = [vp, C.c_uint32, u8p]
         L.hcmvs_estimate.argtypes = [vp, C.c_uint32, u32p, C.c_int32, C.POINTER(Params), C.c_float, C.c_float, fp, fp, fp]
         L.hcmvs_estimate_device.argtypes = [vp, C.c_uint32, u32p, C.c_int32, C.POINTER(Params), C.c_float, C.c_float,
                                             vp, vp, vp]
@@ -244,6 +249,32 @@ class Context:
         h, w = self.shapes[vid]
         out = np.empty((h, w), np.uint8)
         self._chk(lib().hcmvs_get_gradient_map(self._h, vid, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def set_ignore_mask(self, vid, labels, ignore):
+        """--ignore-mask-label for reference view vid: labels is a 16-bit label image of any size (None removes the mask); pixels whose
+        label (resampled INTER_NEAREST to the view's size) is one of `ignore` are left out of every estimate of the view"""
+        ig = np.ascontiguousarray(list(ignore) if labels is not None else [], np.int64)
+        ig = np.clip(ig, -1, 1 << 20).astype(np.int32)  # (atoi values beyond int32 match nothing either)
+        igp = ig.ctypes.data_as(C.POINTER(C.c_int32)) if len(ig) else None
+        if labels is None:
+            self._chk(lib().hcmvs_set_ignore_mask(self._h, vid, None, 0, 0, None, 0))
+            return
+        lab = np.ascontiguousarray(labels, np.uint16)
+        assert lab.ndim == 2
+        self._chk(lib().hcmvs_set_ignore_mask(self._h, vid, lab.ctypes.data_as(C.POINTER(C.c_uint16)), lab.shape[1], lab.shape[0], igp, len(ig)))
+
+    def set_ignore_mask_device(self, vid, d_labels_ptr, lw, lh, ignore):
+        """the same with the label image (u16, lh x lw) in device memory"""
+        ig = np.clip(np.ascontiguousarray(list(ignore), np.int64), -1, 1 << 20).astype(np.int32)
+        igp = ig.ctypes.data_as(C.POINTER(C.c_int32)) if len(ig) else None
+        self._chk(lib().hcmvs_set_ignore_mask_device(self._h, vid, C.c_void_p(d_labels_ptr), lw, lh, igp, len(ig)))
+
+    def ignore_mask(self, vid):
+        """the keep-mask of view vid as the estimate uses it: (h, w) u8, 1 = estimated, 0 = ignored (all 1 without a mask)"""
+        h, w = self.shapes[vid]
+        out = np.empty((h, w), np.uint8)
+        self._chk(lib().hcmvs_get_ignore_mask(self._h, vid, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
     def splat_init(self, vid, points_xyz):

@@ -33,12 +33,13 @@ constexpr int kMaxBatch = HCMVS_MAX_BATCH; // reference images estimated by one 
 
 struct View {
 	View() = default;
-	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r) {}
+	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), keep(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r) {}
 	int w = 0, h = 0;
 	float* gray = nullptr;   // device: the caller's (hcmvs_set_view_device) or grayMem
 	uint8_t* bgr = nullptr;  // device or null: the caller's or bgrMem
 	DevBuf grayMem, bgrMem;  // the copies of hcmvs_upload_view
 	DevBuf gra;              // gradient map, u8 (lazy)
+	DevBuf keep;             // keep-mask of --ignore-mask-label, u8 per pixel (hcmvs_set_ignore_mask); empty = no mask
 	DevBuf quads;            // float4: 2 x 2 footprint layout of the gray image, built when the view first serves as a source view
 	double K[9], R[9], C[3];
 	// estimated maps registered for filter / fuse: the caller's (hcmvs_set_depthmap_device) or the copies in *Mem
@@ -69,6 +70,7 @@ struct hcmvs_ctx final : Reclaimer {
 	};
 	std::vector<Slot> slots;
 	DevBuf tmpU8{this}; // gradient-map staging
+	DevBuf maskStage{this}; // hcmvs_set_ignore_mask: the label image and the ignored labels on their way in
 	// host-path staging
 	DevBuf sDepth{this}, sNormal{this}, sConf{this};
 	DevBuf dViews{this};                  // DevView [kMaxBatch][kMaxViews]
@@ -157,7 +159,10 @@ static inline float fd2r(float d) { return d * (3.14159274101257324f / 180.f); }
 #ifdef HCMVS_STAMPS
 namespace hcmvs { void debug_read_stamps(unsigned long long* out, int reset); }
 #endif
-namespace hcmvs { void launch_resize_gray(const float* src, int sw, int sh, float* dst, int dw, int dh, float scaleParam, hipStream_t s); } // img_kernels.hip
+namespace hcmvs { // img_kernels.hip
+void launch_resize_gray(const float* src, int sw, int sh, float* dst, int dw, int dh, float scaleParam, hipStream_t s);
+void launch_ignore_mask(const uint16_t* labels, int lw, int lh, const int32_t* ignore, int nIgnore, uint8_t* keep, int W, int H, hipStream_t s);
+}
 
 extern "C" {
 
@@ -439,6 +444,64 @@ int hcmvs_get_gradient_map(hcmvs_ctx* c, uint32_t id, uint8_t* out) {
 	return HCMVS_OK;
 }
 
+// --ignore-mask-label (DepthEstimator::ImportIgnoreMask, DepthMap.cpp:319-348): the keep-mask of view `id` as a reference view, from a
+// 16-bit label image of any size, on the host or (device) in device memory.  labels == null removes the mask.
+static int set_ignore_mask(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, const int32_t* ignore, int32_t nIgnore,
+                           bool device) {
+	if (!c) return HCMVS_ERR_INVALID;
+	auto it = c->views.find(id);
+	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "set_ignore_mask: unknown view %u", id);
+	View& v = it->second;
+	HIPCHK(c, hipSetDevice(c->device));
+	if (!labels) { // (an estimate in flight may still read the old mask)
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		v.keep.reset();
+		return HCMVS_OK;
+	}
+	if (lw < 1 || lh < 1 || lw > 65536 || lh > 65536 || nIgnore < 0 || (nIgnore > 0 && !ignore))
+		return fail(c, HCMVS_ERR_INVALID, "set_ignore_mask: bad arguments (view %u, label image %dx%d, %d labels)", id, lw, lh, nIgnore);
+	// mask(r,c) == atoi(label) compares a 16-bit value with an int: labels outside 0 .. 65535 never match
+	std::vector<int32_t> lab;
+	for (int i = 0; i < nIgnore; ++i)
+		if (ignore[i] >= 0 && ignore[i] <= 65535 && std::find(lab.begin(), lab.end(), ignore[i]) == lab.end()) lab.push_back(ignore[i]);
+	const size_t imgBytes = (size_t)lw * lh * sizeof(uint16_t);
+	Carve cv;
+	const size_t oImg = device ? 0 : cv(imgBytes), oLab = cv(sizeof(int32_t) * (lab.size() + 1));
+	HIPCHK(c, c->maskStage.reserve(cv.size, c->stream));
+	HIPCHK(c, v.keep.reserve((size_t)v.w * v.h, c->stream));
+	const uint16_t* dLabels = labels;
+	if (!device) {
+		const int rc = upload_staged(c, c->maskStage.get() + oImg, labels, imgBytes);
+		if (rc) return rc;
+		dLabels = (const uint16_t*)(c->maskStage.get() + oImg);
+	}
+	int32_t* dIgnore = (int32_t*)(c->maskStage.get() + oLab);
+	if (!lab.empty()) HIPCHK(c, hipMemcpyAsync(dIgnore, lab.data(), sizeof(int32_t) * lab.size(), hipMemcpyHostToDevice, c->stream));
+	launch_ignore_mask(dLabels, lw, lh, dIgnore, (int)lab.size(), v.keep.get<uint8_t>(), v.w, v.h, c->stream);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // (lab and the staging go on being used by the next call)
+	return HCMVS_OK;
+}
+
+int hcmvs_set_ignore_mask(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, const int32_t* ignore, int32_t n_ignore) {
+	return set_ignore_mask(c, id, labels, lw, lh, ignore, n_ignore, false);
+}
+int hcmvs_set_ignore_mask_device(hcmvs_ctx* c, uint32_t id, const uint16_t* d_labels, int32_t lw, int32_t lh, const int32_t* ignore,
+                                 int32_t n_ignore) {
+	return set_ignore_mask(c, id, d_labels, lw, lh, ignore, n_ignore, true);
+}
+int hcmvs_get_ignore_mask(hcmvs_ctx* c, uint32_t id, uint8_t* keep) {
+	if (!c || !keep) return HCMVS_ERR_INVALID;
+	auto it = c->views.find(id);
+	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "get_ignore_mask: unknown view %u", id);
+	const View& v = it->second;
+	if (!v.keep.capacity()) { memset(keep, 1, (size_t)v.w * v.h); return HCMVS_OK; } // no mask: every pixel is estimated
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipMemcpyAsync(keep, v.keep.get(), (size_t)v.w * v.h, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return HCMVS_OK;
+}
+
 // per-item constants: DepthMap.cpp:386-439, DepthMap.h:412-444
 static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const hcmvs_params* p, EstConst& k) {
 	if (!it.src_ids || !it.d_depth || !it.d_normal || !it.d_conf) return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
@@ -526,6 +589,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	if (it.d_hint_depth && it.d_hint_normal && p->it_external == p->n_external_iters - 1) { // restore/libs/MVS/DepthMap.cpp:1527
 		k.hintDepth = it.d_hint_depth; k.hintNormal = it.d_hint_normal; k.hintIter = p->n_estimation_iters - 1;
 	}
+	k.keep = ref.keep.capacity() ? ref.keep.get<uint8_t>() : nullptr; // the reference view's mask only (source views ignore theirs)
 	return HCMVS_OK;
 }
 
@@ -558,6 +622,9 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 	for (int i = 0; i < n_items; ++i) {
 		const EstConst& k = c->hItems[i];
 		const float* depthIn = items[i].d_depth;
+		// ApplyIgnoreMask on the initial maps, then the median (SceneDensify.cpp:776-860): an ignored pixel may come out of the median
+		// with a positive depth (five or more valid neighbours) -- kept, with its zero normal, as the reference does
+		if (k.keep) launch_apply_mask(k.keep, items[i].d_depth, items[i].d_normal, k.W * k.H, s);
 		if (p->median_blur) { // SceneDensify.cpp:859
 			launch_median3(items[i].d_depth, c->slots[i].tmpDepth.get<float>(), k.W, k.H, s);
 			depthIn = c->slots[i].tmpDepth.get<float>();
@@ -578,6 +645,8 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		const int nSweeps = p->n_estimation_iters;
 		bool hintLast = false;
 		for (int i = 0; i < n_items; ++i) hintLast = hintLast || (c->hItems[i].hintDepth && c->hItems[i].hintIter == nSweeps - 1);
+		bool mask = false; // some item has a keep-mask: the sweep instance that skips ignored pixels
+		for (int i = 0; i < n_items; ++i) mask = mask || c->hItems[i].keep;
 		// Waves per row, by how the batch's rows compare with the workers the chip holds at once (12 per CU; measured on 1080p images,
 		// profiles/r04_launch_modes.txt): a batch of few rows is bound by the latency of one pixel along the (W + H) critical path of its row
 		// wavefronts, and the scoring of a pixel's hypotheses divides among the waves of a row -- three waves for one image (1066 rows), two
@@ -616,7 +685,7 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 					tickets += rows * ((cols + segLen - 1) / segLen);
 				}
 			}
-			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
+			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, mask, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
 			first += count; ++nLaunches;
 		}
 		c->lastSweepLaunches = nLaunches;

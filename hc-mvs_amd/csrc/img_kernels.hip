@@ -1,5 +1,6 @@
 /*
- * hc-mvs_amd/csrc/img_kernels.hip -- image resampling on the device for the rescaled-neighbour path.
+ * hc-mvs_amd/csrc/img_kernels.hip -- image resampling on the device: the rescaled-neighbour path and the label images of
+ * --ignore-mask-label (INTER_NEAREST, at the end of this file).
  *
  * Reference: DepthData::ViewData::ScaleImage (frame_main/libs/MVS/DepthMap.h:233-238): a source view whose average
  * footprint scale differs from the reference image's by 15 % or more is resampled with
@@ -115,6 +116,28 @@ void launch_resize_gray(const float* src, int sw, int sh, float* dst, int dw, in
 		hipLaunchKernelGGL(resize_area_fast_kernel, grid, block, 0, s, src, sw, sh, dst, dw, dh, iscale);
 	else
 		hipLaunchKernelGGL(resize_area_kernel, grid, block, 0, s, src, sw, sh, dst, dw, dh, scale);
+}
+
+// --ignore-mask-label (DepthEstimator::ImportIgnoreMask, DepthMap.cpp:319-348): the 16-bit label image resampled to the depth map's
+// size with cv::resize INTER_NEAREST -- OpenCV's resizeNN: ifx = 1 / (dw / sw) in double, sx = min(cvFloor(x * ifx), sw - 1), the
+// same for rows -- and keep = 0 where the label equals one of the ignored labels (the host passes only those within 0 .. 65535: an
+// atoi value outside can never equal a 16-bit label)
+__global__ void ignore_mask_kernel(const uint16_t* __restrict__ labels, int lw, int lh, const int32_t* __restrict__ ignore, int nIgnore,
+                                   uint8_t* __restrict__ keep, int W, int H, double ifx, double ify) {
+	const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+	if (x >= W || y >= H) return;
+	int sx = (int)floor((double)x * ifx), sy = (int)floor((double)y * ify);
+	sx = sx < lw - 1 ? sx : lw - 1;
+	sy = sy < lh - 1 ? sy : lh - 1;
+	const int v = labels[(size_t)sy * lw + sx];
+	uint8_t k = 1;
+	for (int i = 0; i < nIgnore; ++i) k = v == ignore[i] ? 0 : k;
+	keep[(size_t)y * W + x] = k;
+}
+void launch_ignore_mask(const uint16_t* labels, int lw, int lh, const int32_t* ignore, int nIgnore, uint8_t* keep, int W, int H, hipStream_t s) {
+	const dim3 block(64, 4), grid((W + 63) / 64, (H + 3) / 4);
+	const double ifx = 1.0 / ((double)W / (double)lw), ify = 1.0 / ((double)H / (double)lh); // inv_scale_x = dsize.width / ssize.width
+	hipLaunchKernelGGL(ignore_mask_kernel, grid, block, 0, s, labels, lw, lh, ignore, nIgnore, keep, W, H, ifx, ify);
 }
 
 } // namespace hcmvs

@@ -54,6 +54,9 @@ struct EstConst {
 	const float* hintDepth;
 	const float* hintNormal;
 	int32_t hintIter;
+	// --ignore-mask-label (DepthMap.cpp:319-381): per pixel 1 = estimated, 0 = ignored (left out of the visiting order of every pass:
+	// the pixel keeps what ApplyIgnoreMask and the median left it); null when the reference view has no mask
+	const uint8_t* keep;
 };
 
 struct SweepSync {
@@ -72,10 +75,11 @@ void launch_gray_to_u8(const float* gray, uint8_t* out, int n, hipStream_t s);
 void launch_bgr_to_u8(const uint8_t* bgr, uint8_t* out, int n, hipStream_t s);
 void launch_gradient_map(const uint8_t* g8, uint8_t* gra, int W, int H, hipStream_t s);
 void launch_median3(const float* in, float* out, int W, int H, hipStream_t s);
+void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, hipStream_t s); // DepthData::ApplyIgnoreMask
 void launch_quads(const float* gray, float4* out, int W, int H, hipStream_t s); // 2 x 2 footprint layout of a source view
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
                        hipStream_t s);
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, const SweepSync& sync, int iter, int nSweeps,
+void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter, int nSweeps,
                   int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s); // segLen > 0: tickets are stretches of segLen columns of a row
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s);
 

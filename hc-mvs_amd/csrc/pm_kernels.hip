@@ -1389,7 +1389,8 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 #ifndef HCMVS_OCC
 #define HCMVS_OCC 3 // waves per SIMD the register allocation of the 5..8-view sweep worker is held to (diagnostic builds vary it)
 #endif
-template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false>
+// MASK: some item of the batch has a keep-mask (--ignore-mask-label); every other launch runs the instance without that code
+template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? HCMVS_OCC : 1, !BIG ? HCMVS_OCC : 2))) void sweep_kernel(const EstConst* __restrict__ items, int nItems, int maxRows, SweepSync sy,
                                                         int iter0, int nSweeps, int lag, int affinity, int segLen) {
 	__shared__ RowShared<NW> sh;
@@ -1561,6 +1562,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			}
 			pp.tx1 = pp.tx2;
 			if (q + 2 < q1) pp.tx2 = uniform_byte(c.gra, y * c.W + x + 2 * dx);
+			uint8_t km = 1; // keep-mask byte of this column, loaded with the pixel's own batch (MASK: some item of the batch has a mask)
+			if constexpr (MASK) km = uniform_byte(c.keep ? c.keep : c.gra, y * c.W + x); // (an item without one reads a byte it ignores)
 			STAMP(12)
 			// ... and the patch weights are computed while they (and the previous row) arrive
 			Patch<S> P;
@@ -1581,6 +1584,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			// load still "in flight" at the loop's back-edge would make the compiler put a full `s_waitcnt vmcnt(0)` there (see the hook's poll)
 			asm volatile("s_waitcnt vmcnt(0)" : "+v"(pp.nI), "+v"(pp.nC) :: "memory");
 			STAMP(0)
+			if (MASK && c.keep && km == 0) { // (workgroup-uniform: every wave of the row reads the same byte)
+				// left out of the visiting order by the keep-mask (DepthMap.cpp:354-381): no evaluation, nothing stored.  Its stored state
+				// (in.cur, loaded above) enters the row's ring for the neighbours behind it, and the column is published at once -- the wait
+				// above drained the previous column's stores, and the row above has passed this column, so whoever waits on it may go on
+				if (L.lane == 0) {
+					float* hrec = sh.hist[q & (kHist - 1)];
+					hrec[0] = in.cur.x; hrec[1] = in.cur.y; hrec[2] = in.cur.z; hrec[3] = in.cur.w; hrec[4] = in.curConf;
+					if (wv == NW - 1) __hip_atomic_store(pp.myWord, pp.base + q + 1, __ATOMIC_RELAXED, HC_SCOPE);
+				}
+				pp.pendingPub = 0;
+				continue;
+			}
 			const unsigned e0 = evals;
 			process_pixel<S, NW, BIG, TWO, PACK, HINT>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued STAMP_PASS);
 			taps += (unsigned long long)(evals - e0) * (unsigned)((P.a + 1) * (P.a + 1));
@@ -1613,7 +1628,12 @@ __global__ void import_kernel(EstConst c, const float* depthIn, const float* nor
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
 		const int x = i % c.W, y = i / c.W;
 		const bool inb = x >= c.border && y >= c.border && x < c.W - c.border && y < c.H - c.border;
-		if (inb) {
+		if (c.keep && !c.keep[i]) {
+			// ignored (keep-mask): no pass visits it, not even the border's depth 0 / conf 2 -- it keeps the median's depth and the
+			// zero normal and confidence of ApplyIgnoreMask (DepthMap.cpp:233-248)
+			c.dn[i] = make_float4(depthIn[i], 0.f, 0.f, 0.f);
+			c.conf[i] = 0.f;
+		} else if (inb) {
 			c.dn[i] = make_float4(depthIn[i], normalIn[3 * i], normalIn[3 * i + 1], normalIn[3 * i + 2]);
 			c.conf[i] = 2.f;
 		} else {
@@ -1623,7 +1643,7 @@ __global__ void import_kernel(EstConst c, const float* depthIn, const float* nor
 	}
 }
 
-template <int S, bool BIG, bool TWO = false>
+template <int S, bool BIG, bool TWO = false, bool MASK = false>
 __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long long* evalsOut) {
 	LaneCtx<S> L;
 	lane_init<S>(c, L);
@@ -1649,6 +1669,7 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 	for (int p = gw; p < total; p += nw) {
 		const int x = c.border + p % ncols, y = c.border + p / ncols;
 		const int idx = y * c.W + x;
+		if constexpr (MASK) if (!uniform_byte(c.keep, idx)) continue; // ignored by the keep-mask (one wave per pixel: uniform)
 		const uint32_t rk = rand_key(c.seed, (uint32_t)idx, stream0);
 		PixIn<S> in;
 		in.tx = (float)c.gra[idx];
@@ -1723,7 +1744,7 @@ __global__ void end_kernel(EstConst c, int finalPass, float* depth, float* norma
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
 		float4 v = c.dn[i];
 		float cf = c.conf[i];
-		if (finalPass) {
+		if (finalPass && !(c.keep && !c.keep[i])) { // (an ignored pixel is not in the end pass's visiting order either)
 			if (v.x <= 0.f || cf >= c.thKeep) { v = make_float4(0.f, 0.f, 0.f, 0.f); cf = 0.f; }
 			else cf = cf >= 1.f ? 0.f : 1.f - cf;
 		}
@@ -1803,6 +1824,11 @@ __global__ void median3_kernel(const float* in, float* out, int W, int H) {
 #undef HC_SORT2
 	out[y * W + x] = v[4];
 }
+// DepthData::ApplyIgnoreMask (DepthMap.cpp:233-248) on the initial maps, in place, before the median (SceneDensify.cpp:776-860)
+__global__ void apply_mask_kernel(const uint8_t* keep, float* depth, float* normal, int n) {
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+		if (!keep[i]) { depth[i] = 0.f; normal[3 * i] = 0.f; normal[3 * i + 1] = 0.f; normal[3 * i + 2] = 0.f; }
+}
 
 // ------------------------------------------------------------------------------------------------------
 // launch wrappers
@@ -1834,22 +1860,27 @@ void launch_quads(const float* gray, float4* out, int W, int H, hipStream_t s) {
 void launch_median3(const float* in, float* out, int W, int H, hipStream_t s) {
 	hipLaunchKernelGGL(median3_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, s, in, out, W, H);
 }
+void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, hipStream_t s) {
+	hipLaunchKernelGGL(apply_mask_kernel, dim3(2048), dim3(256), 0, s, keep, depth, normal, n);
+}
 
-template <bool BIG>
+template <bool BIG, bool MASK>
 static void launch_score_big(const EstConst& c, unsigned long long* evals, hipStream_t s) {
 	const dim3 grid(4096), block(256);
-	if (c.V <= 8) hipLaunchKernelGGL((score_kernel<8, BIG>), grid, block, 0, s, c, evals);
-	else hipLaunchKernelGGL((score_kernel<8, BIG, true>), grid, block, 0, s, c, evals); // 9..16 views: two sets of eight
+	if (c.V <= 8) hipLaunchKernelGGL((score_kernel<8, BIG, false, MASK>), grid, block, 0, s, c, evals);
+	else hipLaunchKernelGGL((score_kernel<8, BIG, true, MASK>), grid, block, 0, s, c, evals); // 9..16 views: two sets of eight
 
 }
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
                        hipStream_t s) {
 	hipLaunchKernelGGL(import_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn);
-	if (c.adapthalfwin > kHalfWindow) launch_score_big<true>(c, evals, s);
-	else launch_score_big<false>(c, evals, s);
+	const bool big = c.adapthalfwin > kHalfWindow;
+	if (c.keep) { if (big) launch_score_big<true, true>(c, evals, s); else launch_score_big<false, true>(c, evals, s); }
+	else if (big) launch_score_big<true, false>(c, evals, s);
+	else launch_score_big<false, false>(c, evals, s);
 }
 
-template <int NW, bool BIG, bool HINT>
+template <int NW, bool BIG, bool HINT, bool MASK>
 static void launch_sweep_nw(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, const SweepSync& sync, int iter, int nSweeps, int lag,
                             int affinity, int segLen, hipStream_t s) {
 	// one workgroup per row; rows beyond the resident set are picked up through the ticket
@@ -1860,41 +1891,44 @@ static void launch_sweep_nw(const EstConst* dItems, int nItems, int maxRows, int
 	// (hypothesis, view) pairs of their own (score_chunk PACK; with one idle group it costs more than it saves)
 	const bool pack = V % 8 != 0 && V % 8 != 7;
 	if (V <= 8) {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, false, HINT>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, true, HINT>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, false, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, true, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
 	} else {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, false, HINT>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, true, HINT>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, false, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, true, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
 	}
 
 }
-template <bool HINT>
+template <bool HINT, bool MASK>
 static void launch_sweep_hint(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, const SweepSync& sync, int iter, int nSweeps, int lag,
                               int wavesPerRow, int affinity, int segLen, hipStream_t s) {
 	if (bigPatch) { // patches beyond 64 taps: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, true, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, true, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		if (wavesPerRow >= 2) launch_sweep_nw<2, true, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		else launch_sweep_nw<1, true, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
 		return;
 	}
 	if constexpr (HINT) { // the one sweep of a run that carries the hint: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, false, true>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, false, true>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		if (wavesPerRow >= 2) launch_sweep_nw<2, false, true, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		else launch_sweep_nw<1, false, true, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
 		return;
 	}
 	switch (wavesPerRow) {
-	case 1: launch_sweep_nw<1, false, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 3: launch_sweep_nw<3, false, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 4: launch_sweep_nw<4, false, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	default: launch_sweep_nw<2, false, HINT>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 1: launch_sweep_nw<1, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 3: launch_sweep_nw<3, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 4: launch_sweep_nw<4, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	default: launch_sweep_nw<2, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
 	}
 }
 // One launch for the sweeps iter .. iter + nSweeps - 1 of every item (tickets, rowsDone and the progress words of the items must be
 // zero).  hint: some item of the batch offers the `restore` variant's extra hypothesis in one of these sweeps (EstConst::hintDepth,
-// hintIter): the instance that knows the hint.
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, const SweepSync& sync, int iter, int nSweeps,
-                  int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
-	if (hint) launch_sweep_hint<true>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	else launch_sweep_hint<false>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+// hintIter): the instance that knows the hint.  mask: some item has a keep-mask (EstConst::keep): the instance that skips its ignored pixels.
+void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter,
+                  int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
+	if (mask) {
+		if (hint) launch_sweep_hint<true, true>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+		else launch_sweep_hint<false, true>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+	} else if (hint) launch_sweep_hint<true, false>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+	else launch_sweep_hint<false, false>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
 }
 
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s) {

@@ -83,7 +83,7 @@ def _device_sync(dev):
 
 
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
-                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False):
+                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -117,6 +117,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     order:     fusion order, best connected first       (SceneDensify.cpp:3302)
     init:      {image id: (depth0 (H,W), normal0 (H,W,3), d_min, d_max)} numpy, at least for this rank's images
     params:    binding.Params of the estimate; it_external / n_external_iters are set here
+    masks:     optional {image id: (labels (h, w) u16 of any size, [ignored labels])}: --ignore-mask-label for those reference images
+               (binding.Context.set_ignore_mask on the rank that estimates them)
     Returns the fused cloud dict of binding.Context.fuse plus `maps`: {id: (depth, normal, conf) device tensors}."""
     import copy
     import numpy as np
@@ -138,6 +140,9 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             ctx.upload_view(i, v["gray"], v["K"], v["R"], v["C"], bgr=v.get("bgr"))
         else:
             ctx.upload_view(i, None, v["K"], v["R"], v["C"], bgr=v["bgr"])
+    for img in mine:
+        if masks and img in masks:
+            ctx.set_ignore_mask(img, masks[img][0], masks[img][1])
     slabs = torch.zeros(n_local, FLOATS_PER_PIXEL * hw, dtype=torch.float32, device=dev)
     rng = torch.zeros(n_local, 2, dtype=torch.float32, device=dev)      # (d_min, d_max) travel with the maps
     for j, img in enumerate(mine):

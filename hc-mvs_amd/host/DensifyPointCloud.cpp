@@ -53,6 +53,7 @@ namespace {
 
 struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	std::string input, output, workdir;
+	std::string ignoreMaskLabel;  // --ignore-mask-label: labels of the segmentation image whose pixels are not estimated (empty: none)
 	int resolutionLevel = 1, numberViews = 5, numberViewsFuse = 2, fusionMode = 0, verbosity = 2;
 	int estimationIters = 1, estimationItersExternal = 4, adaptHalfWin = 5, propagateHalfWin = 1, propagateStep = 4;
 	float photometricFlow = 0.5f, depthweight = 1.f, normalweight = 1.f;
@@ -236,7 +237,7 @@ bool save_mvs(const std::string& path, const std::vector<MvsPlatform>& platforms
 
 // ---- images --------------------------------------------------------------------------------------------------------
 // header of a binary PPM / PGM: size and channel count; the stream is left at the first pixel
-bool pnm_header(std::ifstream& f, int& w, int& h, int& ch) {
+bool pnm_header(std::ifstream& f, int& w, int& h, int& ch, int* maxvOut = nullptr) { // maxvOut: any maxval, reported
 	std::string magic;
 	f >> magic;
 	if (magic != "P5" && magic != "P6") return false;
@@ -245,7 +246,28 @@ bool pnm_header(std::ifstream& f, int& w, int& h, int& ch) {
 	const int maxv = next();
 	f.get();
 	ch = magic == "P6" ? 3 : 1;
-	return w > 0 && h > 0 && maxv == 255 && (bool)f;
+	if (maxvOut) *maxvOut = maxv;
+	return w > 0 && h > 0 && (maxv == 255 || maxvOut) && (bool)f;
+}
+// a label image of --ignore-mask-label as Image16U::Load reads it (Types.inl:2972-2991: imread UNCHANGED, colour -> gray, convertTo 16U):
+// 8-bit P5, 16-bit P5 (maxval 65535, big-endian), or 8-bit P6 through cv::cvtColor's integer BGR2GRAY.  Any other maxval: no mask.
+bool load_labels(const std::string& path, int& w, int& h, std::vector<uint16_t>& lab) {
+	std::ifstream f(path, std::ios::binary);
+	if (!f) return false;
+	int ch = 0, maxv = 0;
+	if (!pnm_header(f, w, h, ch, &maxv)) return false;
+	if (!(maxv == 255 || (maxv == 65535 && ch == 1))) return false;
+	const size_t n = (size_t)w * h, bpp = maxv == 65535 ? 2 : 1;
+	std::vector<uint8_t> raw(n * ch * bpp);
+	f.read((char*)raw.data(), (std::streamsize)raw.size());
+	if (!f) return false;
+	lab.resize(n);
+	for (size_t i = 0; i < n; ++i) {
+		if (bpp == 2) lab[i] = (uint16_t)((raw[2 * i] << 8) | raw[2 * i + 1]);
+		else if (ch == 1) lab[i] = raw[i];
+		else lab[i] = (uint16_t)((raw[3 * i + 2] * 1868 + raw[3 * i + 1] * 9617 + raw[3 * i] * 4899 + 8192) >> 14); // file order R, G, B
+	}
+	return true;
 }
 bool pnm_size(const std::string& path, int& w, int& h) {
 	std::ifstream f(path, std::ios::binary);
@@ -743,6 +765,7 @@ int main(int argc, char** argv) {
 	for (const char* k : {"-o", "--output-file"}) if (kv.count(k)) o.output = kv[k];
 	for (const char* k : {"-w", "--working-folder"}) if (kv.count(k)) o.workdir = kv[k];
 	geti("-v", o.verbosity); geti("--verbosity", o.verbosity);
+	if (kv.count("--ignore-mask-label")) o.ignoreMaskLabel = kv["--ignore-mask-label"];
 	geti("--resolution-level", o.resolutionLevel); geti("--number-views", o.numberViews); geti("--number-views-fuse", o.numberViewsFuse);
 	geti("--fusion-mode", o.fusionMode); geti("--n-EstimationIters", o.estimationIters);
 	geti("--n-EstimationIters-external", o.estimationItersExternal); geti("--n-adapthalfwin", o.adaptHalfWin);
@@ -1148,6 +1171,50 @@ int main(int argc, char** argv) {
 			}
 		}
 		HIPOK(hipSetDevice(o.device));
+	}
+	// --ignore-mask-label (DepthEstimator::ImportIgnoreMask, DepthMap.cpp:319-348): the labels split at every ',' (empty tokens kept,
+	// Util::strSplit) and read with atoi; every image to estimate gets the keep-mask of its label image on the context that estimates it
+	if (!o.ignoreMaskLabel.empty()) {
+		std::vector<int32_t> labels;
+		for (size_t b = 0;;) {
+			const size_t e = o.ignoreMaskLabel.find(',', b);
+			labels.push_back((int32_t)atoi(o.ignoreMaskLabel.substr(b, e == std::string::npos ? std::string::npos : e - b).c_str()));
+			if (e == std::string::npos) break;
+			b = e + 1;
+		}
+		size_t nMasked = 0, pxAll = 0, pxIgnored = 0;
+		for (uint32_t id : todo) {
+			const ImageData& im = images[id];
+			// the fork's rule (Scene.cpp:119-126): getFilePath(name) + "/seman/" + getFileName(name) + ".quad.png", read here as its binary
+			// Netpbm siblings.  A name without a folder resolves against the image's own folder (the fork makes it root-absolute).
+			const size_t sl = im.name.find_last_of('/');
+			std::string stem = sl == std::string::npos ? im.name : im.name.substr(sl + 1);
+			if (stem.find_last_of('.') != std::string::npos) stem = stem.substr(0, stem.find_last_of('.'));
+			const std::string base = dirname_of(paths[id]) + "/seman/" + stem + ".quad";
+			std::vector<uint16_t> lab;
+			int lw = 0, lh = 0;
+			std::string used;
+			for (const char* ext : {".pgm", ".ppm"})
+				if (load_labels(base + ext, lw, lh, lab)) { used = base + ext; break; }
+			if (used.empty()) {
+				if (o.verbosity > 1) fprintf(stderr, "warning: can not load the segmentation mask '%s.png' (tried '%s.pgm' and '%s.ppm'): image %u is not masked\n",
+				                             base.c_str(), base.c_str(), base.c_str(), id);
+				continue;
+			}
+			hcmvs_ctx* dctx = devs[(size_t)im.dev].ctx;
+			std::vector<uint8_t> keep((size_t)im.w * im.h);
+			if (hcmvs_set_ignore_mask(dctx, id, lab.data(), lw, lh, labels.data(), (int32_t)labels.size()) != HCMVS_OK ||
+			    hcmvs_get_ignore_mask(dctx, id, keep.data()) != HCMVS_OK) {
+				fprintf(stderr, "error: the ignore mask of image %u failed (%s)\n", id, hcmvs_last_error(dctx));
+				return EXIT_FAILURE;
+			}
+			++nMasked; pxAll += keep.size();
+			pxIgnored += (size_t)std::count(keep.begin(), keep.end(), (uint8_t)0);
+		}
+		HIPOK(hipSetDevice(o.device));
+		if (o.verbosity > 1)
+			printf("Ignore mask (labels %s): %zu of %zu images masked, %.2f %% of their pixels ignored\n", o.ignoreMaskLabel.c_str(), nMasked, todo.size(),
+			       pxAll ? 100.0 * (double)pxIgnored / (double)pxAll : 0.0);
 	}
 
 	// ---- the saver: copies + files of the final maps, behind the estimation ----

@@ -120,6 +120,21 @@ int hcmvs_release_view(hcmvs_ctx* ctx, uint32_t id);
 /* copy the u8 gradient map of a view (SceneDensify.cpp:581-595 InitGraMap) to a host buffer of w*h bytes */
 int hcmvs_get_gradient_map(hcmvs_ctx* ctx, uint32_t id, uint8_t* out);
 
+/* --ignore-mask-label (DepthEstimator::ImportIgnoreMask, DepthMap.cpp:319-348): a keep-mask for view `id` as a REFERENCE view.
+ * labels: a 16-bit label image of lw x lh (any size; resampled to the view's size with cv::resize INTER_NEAREST on the device);
+ * a pixel is ignored when its label equals one of ignore[0..n_ignore) (values outside 0..65535 never match).  Every estimate of
+ * the view then applies the mask to its initial maps (depth, normal = 0) before the median and leaves the ignored pixels out of
+ * every pass: they end the estimate with the median's depth, normal 0 and conf 0, and cost no evaluation.  Source views and views
+ * made by hcmvs_rescale_view ignore masks; registering the view again or hcmvs_release_view drops it.  labels == NULL removes
+ * the mask.  Blocking. */
+int hcmvs_set_ignore_mask(hcmvs_ctx* ctx, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, const int32_t* ignore,
+                          int32_t n_ignore);
+/* the same with the label image in DEVICE memory (ignore stays a host array) */
+int hcmvs_set_ignore_mask_device(hcmvs_ctx* ctx, uint32_t id, const uint16_t* d_labels, int32_t lw, int32_t lh, const int32_t* ignore,
+                                 int32_t n_ignore);
+/* copy the keep-mask of view `id` (1 = estimated, 0 = ignored; all 1 without a mask) to a host buffer of w*h bytes */
+int hcmvs_get_ignore_mask(hcmvs_ctx* ctx, uint32_t id, uint8_t* keep);
+
 /* One EstimateDepthMap call for reference view ref_id against src_ids[0..n_src): [median] -> init score
  * -> n_estimation_iters sweeps -> end pass if it_external == n_external_iters-1.
  * depth (w*h), normal (w*h*3), conf (w*h) are in/out HOST buffers: on entry the initial maps (zeros +
