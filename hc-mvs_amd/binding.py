@@ -48,6 +48,10 @@ class VisibilityStats(C.Structure):
                 ("hits", C.c_uint64), ("device_bytes", C.c_uint64), ("ms_device", C.c_float)]
 
 
+class SpreadStats(C.Structure):
+    _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
+
+
 class HcmvsError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("hcmvs error %d: %s" % (code, msg))
@@ -64,7 +68,8 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
            "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
-           "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask"]
+           "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
+           "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -155,6 +160,9 @@ def lib():
         L.hcmvs_point_cloud_filter.argtypes = [vp, C.c_uint64, fp, u32p, u32p, C.c_uint32, C.POINTER(C.c_int32), dp, dp, dp, C.c_int32,
                                                C.POINTER(C.c_int32), u32p, u64p, C.POINTER(VisibilityStats)]
         L.hcmvs_resize_area_up.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
+        L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
+        L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
+        L.hcmvs_get_spread_stats.argtypes = [vp, C.POINTER(SpreadStats)]
         _lib = L
     return _lib
 
@@ -330,6 +338,23 @@ class Context:
         s = Stats()
         self._chk(lib().hcmvs_get_stats(self._h, C.byref(s)))
         return s
+
+    # ---- view spread (--n-viewspread, DepthMap.cpp:1504-1608) ----------------------------------------------
+
+    def set_viewspread(self, on):
+        """switch view spread on or off for the estimates that follow (default off)"""
+        self._chk(lib().hcmvs_set_viewspread(self._h, int(bool(on))))
+
+    def set_spread_maps_device(self, vid, d_depth_ptr, d_normal_ptr, d_conf_ptr):
+        """the maps view vid offers as a source view: device memory of the view's size, caller-owned, not copied; all None removes them"""
+        self._chk(lib().hcmvs_set_spread_maps_device(self._h, vid, C.c_void_p(d_depth_ptr) if d_depth_ptr else None,
+                                                     C.c_void_p(d_normal_ptr) if d_normal_ptr else None, C.c_void_p(d_conf_ptr) if d_conf_ptr else None))
+
+    def spread_stats(self):
+        """counters of the view spread of the last estimate: dict(slots_scored, slots_accepted, slots_dropped, candidates_outside)"""
+        s = SpreadStats()
+        self._chk(lib().hcmvs_get_spread_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in SpreadStats._fields_}
 
     # ---- filter / fuse (SceneDensify.h:69-70) -----------------------------------------------------------
 

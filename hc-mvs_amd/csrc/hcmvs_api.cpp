@@ -48,6 +48,9 @@ struct View {
 	float dMin = 0.f, dMax = 0.f;
 	DevBuf dNeighbors; // uint32_t
 	std::vector<uint32_t> neighbors;
+	// --n-viewspread: the maps this view offers as a SOURCE view (hcmvs_set_spread_maps_device; the caller's, of the view's size)
+	const float *sDepth = nullptr, *sNormal = nullptr, *sConf = nullptr;
+	bool rescaled = false; // made by hcmvs_rescale_view: never spreads
 };
 
 } // namespace
@@ -77,6 +80,10 @@ struct hcmvs_ctx final : Reclaimer {
 	std::vector<DevView> hViews;          // host copy handed to hipMemcpyAsync (must outlive the call)
 	DevBuf dItems{this};                  // EstConst [kMaxBatch]
 	std::vector<EstConst> hItems;
+	DevBuf dSpread{this};                 // SpreadView [kMaxBatch][kMaxViews]
+	std::vector<SpreadView> hSpread;
+	int viewspread = 0;                   // hcmvs_set_viewspread
+	bool haveSpreadStats = false;         // the last estimate ran with view spread in effect
 	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
 	int sweepPerLaunch = 0;               // HCMVS_SWEEP_LAUNCHES: 0 automatic (one launch for all sweeps from 16 images on), 1 per-sweep, 2 one
 	DevBuf evals{this};                   // unsigned long long [4]
@@ -204,8 +211,9 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	c->stream = c->ownStream;
 	for (auto& e : c->ev)
 		if (hipEventCreate(&e) != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
-	c->hViews.resize((size_t)kMaxBatch * kMaxViews); c->hItems.resize(kMaxBatch);
-	if (c->dViews.reserve(sizeof(DevView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(32, c->stream) != hipSuccess ||
+	c->hViews.resize((size_t)kMaxBatch * kMaxViews); c->hItems.resize(kMaxBatch); c->hSpread.resize((size_t)kMaxBatch * kMaxViews);
+	if (c->dViews.reserve(sizeof(DevView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(64, c->stream) != hipSuccess ||
+	    c->dSpread.reserve(sizeof(SpreadView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess ||
 	    c->dItems.reserve(sizeof(EstConst) * kMaxBatch, c->stream) != hipSuccess || c->sync.reserve(64 + sizeof(int32_t) * 2 * kMaxBatch, c->stream) != hipSuccess) {
 		hcmvs_destroy(c);
 		return HCMVS_ERR_NO_DEVICE;
@@ -368,6 +376,7 @@ int hcmvs_rescale_view(hcmvs_ctx* c, uint32_t src_id, uint32_t dst_id, float sca
 	const double f = (double)std::max(nw, nh) / (double)std::max(src.w, src.h);
 	memcpy(v.K, src.K, sizeof v.K); memcpy(v.R, src.R, sizeof v.R); memcpy(v.C, src.C, sizeof v.C);
 	v.K[0] *= f; v.K[4] *= f; v.K[2] *= f; v.K[5] *= f;
+	v.rescaled = true;
 	c->views[dst_id] = std::move(v);
 	return HCMVS_OK;
 }
@@ -590,7 +599,35 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 		k.hintDepth = it.d_hint_depth; k.hintNormal = it.d_hint_normal; k.hintIter = p->n_estimation_iters - 1;
 	}
 	k.keep = ref.keep.capacity() ? ref.keep.get<uint8_t>() : nullptr; // the reference view's mask only (source views ignore theirs)
+	// --n-viewspread (DepthMap.cpp:1504-1608): from outer iteration 1 on, the source views that offer maps of their own
+	k.spread = nullptr;
+	SpreadView* hs = c->hSpread.data() + (size_t)slot * kMaxViews;
+	memset(hs, 0, sizeof(SpreadView) * kMaxViews);
+	if (c->viewspread && p->it_external >= 1) {
+		bool any = false;
+		for (int v = 0; v < n_src; ++v) {
+			const View& s = c->views.find(it.src_ids[v])->second;
+			if (!s.sDepth || s.rescaled) continue;
+			any = true;
+			hs[v].depth = s.sDepth; hs[v].normal = s.sNormal; hs[v].conf = s.sConf;
+			hs[v].w = s.w; hs[v].h = s.h;
+			hs[v].cx = s.K[2]; hs[v].cy = s.K[5]; hs[v].ifx = 1.0 / s.K[0]; hs[v].ify = 1.0 / s.K[4];
+			// depth in the reference camera of a point Xc of view j's camera: (R_ref R_j^T Xc + R_ref (C_j - C_ref)).z
+			double T[9];
+			mat3_mul_bt(ref.R, s.R, T);
+			const double dC[3] = {s.C[0] - ref.C[0], s.C[1] - ref.C[1], s.C[2] - ref.C[2]};
+			hs[v].Tz[0] = T[6]; hs[v].Tz[1] = T[7]; hs[v].Tz[2] = T[8];
+			hs[v].tz = ref.R[6] * dC[0] + ref.R[7] * dC[1] + ref.R[8] * dC[2];
+		}
+		if (any) k.spread = c->dSpread.get<SpreadView>() + (size_t)slot * kMaxViews;
+	}
 	return HCMVS_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+	const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+	return a0 < b0 + nb && b0 < a0 + na;
 }
 
 int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p) {
@@ -611,11 +648,35 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		if (rows > maxRows) maxRows = rows;
 		totalRows += rows;
 	}
+	// view spread: a launch must not read what it writes -- the in/out maps of no item may overlap the spread maps of a source view of any item
+	bool spread = false;
+	for (int i = 0; i < n_items; ++i) spread = spread || c->hItems[i].spread;
+	if (spread)
+		for (int i = 0; i < n_items; ++i) {
+			const size_t n = (size_t)c->hItems[i].W * c->hItems[i].H;
+			for (int k = 0; k < n_items; ++k)
+				for (int v = 0; v < items[k].n_src; ++v) {
+					const SpreadView& sv = c->hSpread[(size_t)k * kMaxViews + v];
+					if (!c->hItems[k].spread || !sv.depth) continue;
+					const size_t m = (size_t)sv.w * sv.h;
+					const void* io[3] = {items[i].d_depth, items[i].d_normal, items[i].d_conf};
+					const size_t ion[3] = {n * 4, n * 12, n * 4};
+					const void* sp[3] = {sv.depth, sv.normal, sv.conf};
+					const size_t spn[3] = {m * 4, m * 12, m * 4};
+					for (int a = 0; a < 3; ++a)
+						for (int b = 0; b < 3; ++b)
+							if (overlaps(io[a], ion[a], sp[b], spn[b]))
+								return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the spread maps of source view %u of item %d: "
+								            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", i, items[i].ref_id, items[k].src_ids[v], k);
+				}
+		}
 	hipStream_t s = c->stream;
 	// same stream => the previous call's kernels are done with these tables before the copies land
+	if (spread) HIPCHK(c, hipMemcpyAsync(c->dSpread.get(), c->hSpread.data(), sizeof(SpreadView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
+	c->haveSpreadStats = spread;
 	HIPCHK(c, hipMemcpyAsync(c->dViews.get(), c->hViews.data(), sizeof(DevView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
 	HIPCHK(c, hipMemcpyAsync(c->dItems.get(), c->hItems.data(), sizeof(EstConst) * n_items, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 32, s));
+	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 64, s));
 	HIPCHK(c, hipMemsetAsync(c->sync.get(), 0, 64 + sizeof(int32_t) * 2 * kMaxBatch, s));
 
 	HIPCHK(c, hipEventRecord(c->ev[0], s));
@@ -685,7 +746,7 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 					tickets += rows * ((cols + segLen - 1) / segLen);
 				}
 			}
-			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, mask, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
+			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, mask, spread, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
 			first += count; ++nLaunches;
 		}
 		c->lastSweepLaunches = nLaunches;
@@ -730,6 +791,37 @@ int hcmvs_get_stats(hcmvs_ctx* c, hcmvs_stats* out) {
 	out->ms_sweep_avg = c->lastSweeps > 0 ? out->ms_sweeps / (float)c->lastSweeps : 0.f;
 	c->errPending = true;
 	return check_sweep_error(c);
+}
+
+// ---- view spread (DensifyPointCloud --n-viewspread, DepthMap.cpp:1504-1608) ----
+
+int hcmvs_set_viewspread(hcmvs_ctx* c, int32_t on) {
+	if (!c) return HCMVS_ERR_INVALID;
+	c->viewspread = on != 0;
+	return HCMVS_OK;
+}
+int hcmvs_set_spread_maps_device(hcmvs_ctx* c, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf) {
+	if (!c) return HCMVS_ERR_INVALID;
+	auto it = c->views.find(id);
+	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: unknown view %u", id);
+	View& v = it->second;
+	if (!d_depth && !d_normal && !d_conf) { v.sDepth = v.sNormal = v.sConf = nullptr; return HCMVS_OK; }
+	if (!d_depth || !d_normal || !d_conf) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: view %u: depth, normal and conf are all needed (or all NULL)", id);
+	if (v.rescaled) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: view %u was made by hcmvs_rescale_view: a resampled view has no maps of its size and never spreads", id);
+	v.sDepth = d_depth; v.sNormal = d_normal; v.sConf = d_conf;
+	return HCMVS_OK;
+}
+int hcmvs_get_spread_stats(hcmvs_ctx* c, hcmvs_spread_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	memset(out, 0, sizeof *out);
+	if (!c->haveStats) return fail(c, HCMVS_ERR_INVALID, "get_spread_stats: no estimate has run");
+	if (!c->haveSpreadStats) return HCMVS_OK; // the last estimate had no view spread to do: all zero
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	unsigned long long ev[8];
+	HIPCHK(c, hipMemcpy(ev, c->evals.get(), 64, hipMemcpyDeviceToHost));
+	out->slots_scored = ev[4]; out->slots_accepted = ev[5]; out->slots_dropped = ev[6]; out->candidates_outside = ev[7];
+	return HCMVS_OK;
 }
 
 int hcmvs_estimate(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* src_ids, int32_t n_src, const hcmvs_params* p, float d_min,

@@ -28,6 +28,17 @@ struct DevView {
 	float Hm[3]; // Kj Rj (Ci - Cj)
 };
 
+// --n-viewspread (DepthMap.cpp:1504-1608): what a sweep worker needs of one source view j whose own maps are offered as hypotheses.
+// depth == null: the view offers none.  The maps have the view's image size.
+struct SpreadView {
+	const float* depth;     // w * h
+	const float* normal;    // w * h * 3, view j's camera frame
+	const float* conf;      // w * h
+	int32_t w, h;
+	double cx, cy, ifx, ify; // view j's principal point and 1 / focal
+	double Tz[3], tz;        // third row of R_ref R_j^T and of R_ref (C_j - C_ref): depth in the reference camera of a point of view j's
+};
+
 // uniform constants of one EstimateDepthMap call (DepthMap.cpp:386-439 DepthEstimator ctor)
 struct EstConst {
 	int32_t W, H, V;
@@ -57,13 +68,17 @@ struct EstConst {
 	// --ignore-mask-label (DepthMap.cpp:319-381): per pixel 1 = estimated, 0 = ignored (left out of the visiting order of every pass:
 	// the pixel keeps what ApplyIgnoreMask and the median left it); null when the reference view has no mask
 	const uint8_t* keep;
+	// view spread (SPREAD instances of the sweep): [V] entries in the estimate's view order; null when the call has it off, at outer
+	// iteration 0 or when no source view of the item offers maps
+	const SpreadView* spread;
 };
 
 struct SweepSync {
 	int32_t* ticket;   // [kMaxBatch] next row of every image of the batch, counted through the sweeps of the launch (row + sweep * rows)
 	int32_t* rowsDone; // [kMaxBatch] rows every image has finished, counted through the sweeps of the launch
 	int32_t* error;    // set non-zero when a worker times out
-	unsigned long long* evals;  // [0] ScorePixel calls of the sequential algorithm, [1] evaluations issued (incl. speculative), [2] patch taps of [0]
+	unsigned long long* evals;  // [0] ScorePixel calls of the sequential algorithm, [1] evaluations issued (incl. speculative), [2] patch taps of [0],
+	                            // [4 .. 8) view spread: slots scored, slots accepted, slots dropped (depth <= 0), candidates outside the view's map
 };
 
 // lane layout class for V source views (the items of a batch must share it): 8 for up to 8 views, 4 for 9..16 views, which run
@@ -79,7 +94,7 @@ void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, 
 void launch_quads(const float* gray, float4* out, int W, int H, hipStream_t s); // 2 x 2 footprint layout of a source view
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
                        hipStream_t s);
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter, int nSweeps,
+void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, bool spread, const SweepSync& sync, int iter, int nSweeps,
                   int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s); // segLen > 0: tickets are stretches of segLen columns of a row
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s);
 

@@ -1106,6 +1106,10 @@ __device__ __forceinline__ float share_scores(RowShared<NW>& sh, int& par, int l
 	return all;
 }
 
+// view-spread counters of one wave (SPREAD instances only): slots scored, slots accepted, slots whose transformed depth was not
+// positive, candidates outside the source view's map
+struct SpreadCount { unsigned scored, accepted, dropped, outside; };
+
 // DepthMap.cpp:1050-1501 ProcessPixel for logical column q of the row, pixel (x,y).
 // Per phase the hypotheses are generated lane-parallel (lane t = hypothesis t) by every wave, the smoothness
 // factors of a wave's share come from one smooth_pass, the share is scored hypothesis by hypothesis, the scores are
@@ -1115,10 +1119,13 @@ __device__ __forceinline__ float share_scores(RowShared<NW>& sh, int& par, int l
 // scored after the first, and the two best views are taken over both
 // HINT: the launch is the sweep in which the `restore` variant offers the up-sampled coarser level as one more hypothesis
 // (EstConst::hintDepth / hintIter); every other launch -- all of BASELINE configs[1] -- runs the instance without that code
-template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT>
+// SPREAD: view spread is on in this launch (--n-viewspread, DepthMap.cpp:1504-1608; EstConst::spread): after its refinement trials a
+// pixel also tries what its source views' own maps hold around the place it projects to; every other launch runs the instance
+// without that code
+template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT, bool SPREAD>
 __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S>& L, const LaneCtx<S>& L1, RowShared<NW>& sh, int& par, int wv,
                                               int x, int y, int q, int iter, const PixIn<S>& in, const Patch<S>& P,
-                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued STAMP_ARGS) {
+                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued, SpreadCount& spc STAMP_ARGS) {
 	const int W = c.W, lane = L.lane;
 	PixelGeom G;
 	pixel_geom(c, x, y, G);
@@ -1147,7 +1154,7 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 		C.kd = interpolate_pixel(c, G, nx, ny, C.d, C.n0, C.n1, C.n2);
 		correct_normal(G, C.k0, C.k1, C.k2);
 	}
-	const unsigned long long closeMask = C.closeMask, eligMask = C.eligMask;
+	unsigned long long closeMask = C.closeMask, eligMask = C.eligMask; // (SPREAD: replaced by the last spreading view's set)
 	{ // park the slots for the smoothness passes (LDS of this wave; same-wave LDS accesses are ordered)
 		float (*cl)[kMaxSlots] = st.pk->cl;
 		if (lane < kMaxSlots) {
@@ -1184,6 +1191,7 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 	unsigned idxScaleRange = 0;
 	float scaleRange = 1.f, depthRange = 0.f, p0 = 0.f, p1 = 0.f;
 	bool hooked = false, pollTaken = false;
+	bool randExit = false; // SPREAD: the pixel left through the `return` of the full-random branch (DepthMap.cpp:1464)
 	for (;;) {
 		if (phase == PH_PICK) { // the RefineIters label, DepthMap.cpp:1443-1448
 			BLOCK(blk_pick, 0)
@@ -1311,6 +1319,7 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 				}
 			}
 			phase = again ? PH_PICK : PH_DONE;
+			if constexpr (SPREAD) randExit = !again;
 		} else {
 			// the sequential scan stops at the first valid trial that beats the estimate (DepthMap.cpp:1484): found with
 			// one ballot; the trials before it were scored and rejected, the ones behind it are regenerated
@@ -1337,6 +1346,95 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 		if (phase == PH_DONE) break;
 	}
 	SUBMARK(blk_pixel_tail)
+	if constexpr (SPREAD) if (c.spread && !randExit) {
+		// View spread (DepthMap.cpp:1504-1608): V short propagation-like rounds, one per source view that offers maps, in the estimate's
+		// view order and sequentially -- view j + 1's homography uses the estimate as view j's accepts left it.  Per view: x1 = H_j (x, y, 1)
+		// truncated; the four candidates around it (up, down, left, right; lane i = candidate i) exist when x1 lies more than 7 pixels
+		// inside the REFERENCE image (DepthMap.cpp:1532) and, here, inside view j's map; one with a positive depth in view j's map is a
+		// slot (that depth, view j's stored normal as it is, X through view j's intrinsics) and the slots REPLACE the wave's smoothness
+		// table -- also when there are none (neighborsClose.Empty(), DepthMap.cpp:1523-1527), and the hint below reads the last view's.
+		// A slot whose conf in view j's map is below the keep threshold is a hypothesis: depth = z of the point in the reference camera
+		// (R_ref R_j^T Xc + R_ref (C_j - C_ref), double, row 2 only), CorrectNormal, InitPlane, ScorePixel; like the propagation round,
+		// slot i sees the slots <= i corrected (smooth_pass with limit = slot) and the accepts are replayed in slot order.  The maps are
+		// read with plain loads: no launch writes what it reads here (hcmvs_estimate_batch_device refuses the aliasing).  With several
+		// waves per row every wave scores the (at most four) slots itself, as for the hint.
+		const HC_GLOBAL SpreadView* sv = as_global(c.spread);
+		float (*cl)[kMaxSlots] = st.pk->cl;
+		for (int j = 0; j < c.V; ++j) {
+			gcfptr sdep = (gcfptr)sv[j].depth;
+			if (!sdep) continue; // the view offers no maps: passed over altogether
+			gcfptr snrm = (gcfptr)sv[j].normal, scnf = (gcfptr)sv[j].conf;
+			const int sw = sv[j].w, shh = sv[j].h;
+			float x1x, x1y;
+			{
+				float vA[9], vHm[3], Hj[9];
+				const float4 a = st.pk->vh[j][0], b = st.pk->vh[j][1], cc = st.pk->vh[j][2];
+				vA[0] = a.x; vA[1] = a.y; vA[2] = a.z; vA[3] = a.w; vA[4] = b.x; vA[5] = b.y; vA[6] = b.z; vA[7] = b.w; vA[8] = cc.x;
+				vHm[0] = cc.y; vHm[1] = cc.z; vHm[2] = cc.w;
+				make_homography(c, vA, vHm, G.v0, G.v1, depth, n0, n1, n2, Hj);
+				const float px = (float)x, py = (float)y;
+				const float Xx = fmaf(Hj[1], py, fmaf(Hj[0], px, Hj[2]));
+				const float Xy = fmaf(Hj[4], py, fmaf(Hj[3], px, Hj[5]));
+				const float Xz = fmaf(Hj[7], py, fmaf(Hj[6], px, Hj[8]));
+				const float iz = 1.0f / Xz;
+				x1x = Xx * iz; x1y = Xy * iz;
+			}
+			// 7 < (int)x1 < size - 7 tested on the floats: the same set for every finite value, and false for a NaN
+			const bool rim = x1x >= (float)(kHalfWindow + 1) && x1y >= (float)(kHalfWindow + 1) && x1x < (float)(W - kHalfWindow) &&
+			                 x1y < (float)(c.H - kHalfWindow);
+			const int ix = rim ? (int)x1x : kHalfWindow + 1, iy = rim ? (int)x1y : kHalfWindow + 1;
+			const int t = lane & 3;
+			const int cnx = ix + (t == 2 ? -1 : (t == 3 ? 1 : 0)), cny = iy + (t == 0 ? -1 : (t == 1 ? 1 : 0));
+			const bool cand = rim && lane < 4;
+			const bool inMap = cnx < sw && cny < shh; // (cnx, cny >= 7)
+			const bool ld = cand && inMap;
+			// the four depth, conf and normal gathers of the view go out together (lanes without a candidate read pixel 0)
+			const size_t nidx = ld ? (size_t)cny * (size_t)sw + (size_t)cnx : 0;
+			const float sd = sdep[nidx], scf = scnf[nidx];
+			const float sn0 = snrm[3 * nidx], sn1 = snrm[3 * nidx + 1], sn2 = snrm[3 * nidx + 2];
+			const bool slotV = ld && sd > 0.f;
+			const double z = sd;
+			const double Xc0 = ((double)cnx - sv[j].cx) * z * sv[j].ifx, Xc1 = ((double)cny - sv[j].cy) * z * sv[j].ify;
+			const float zt = (float)(((sv[j].Tz[0] * Xc0 + sv[j].Tz[1] * Xc1) + sv[j].Tz[2] * z) + sv[j].tz);
+			const bool open = slotV && !(scf >= c.thKeep);
+			const bool hv = open && zt > 0.f;
+			float k0 = sn0, k1 = sn1, k2 = sn2;
+			if (hv) correct_normal(G, k0, k1, k2);
+			closeMask = __ballot(slotV);
+			eligMask = __ballot(hv);
+			if (wv == 0) {
+				spc.outside += (unsigned)__builtin_popcountll(__ballot(cand && !inMap));
+				spc.dropped += (unsigned)__builtin_popcountll(__ballot(open && !hv));
+			}
+			if (lane < kMaxSlots) {
+				cl[0][lane] = (float)Xc0; cl[1][lane] = (float)Xc1; cl[2][lane] = sd;
+				cl[3][lane] = sn0; cl[4][lane] = sn1; cl[5][lane] = sn2;
+				cl[6][lane] = k0; cl[7][lane] = k1; cl[8][lane] = k2;
+			}
+			if (eligMask == 0ull) continue;
+			const int src = (lane >> 3) < 4 ? (lane >> 3) : 0;
+			const float gd = __shfl(zt, src, 64), g0 = __shfl(k0, src, 64), g1 = __shfl(k1, src, 64), g2 = __shfl(k2, src, 64);
+			const float gpd = -gd * dot3(g0, g1, g2, G.v0, G.v1, 1.f); // InitPlane
+			const float F = smooth_pass(c, cl, closeMask, eligMask, lane, gd, g0, g1, g2, g0, g1, g2, gpd, src);
+			float s1 = __builtin_huge_valf(), s2 = __builtin_huge_valf();
+			score_chunk<S, BIG, PACK>(c, L, P, st, G.v0, G.v1, F, zt, k0, k1, k2, eligMask, 0, __builtin_ctzll(eligMask), s1, s2, issued);
+			if constexpr (TWO) {
+				unsigned again = 0;
+				score_chunk<S, BIG, PACK>(c, L1, P, st, G.v0, G.v1, F, zt, k0, k1, k2, eligMask, 0, __builtin_ctzll(eligMask), s1, s2, again);
+			}
+			const float all = two_best(c, s1, s2);
+			for (unsigned long long mk = eligMask; mk; mk &= mk - 1ull) {
+				const int i = __builtin_ctzll(mk);
+				const float nconf = rlf(all, i);
+				++evals;
+				if (wv == 0) ++spc.scored;
+				if (conf > nconf) {
+					conf = nconf; depth = rlf(zt, i); n0 = rlf(k0, i); n1 = rlf(k1, i); n2 = rlf(k2, i);
+					if (wv == 0) ++spc.accepted;
+				}
+			}
+		}
+	}
 	if constexpr (HINT) if (c.hintDepth && iter == c.hintIter) {
 		// restore variant, last sweep of the last outer iteration (restore/libs/MVS/DepthMap.cpp:1527-1549): the estimate of the
 		// up-sampled coarser level is one more hypothesis; it wins even when up to 0.1 worse.  Every wave evaluates it itself.
@@ -1390,7 +1488,8 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 #define HCMVS_OCC 3 // waves per SIMD the register allocation of the 5..8-view sweep worker is held to (diagnostic builds vary it)
 #endif
 // MASK: some item of the batch has a keep-mask (--ignore-mask-label); every other launch runs the instance without that code
-template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false>
+// SPREAD: the call has view spread on and some source view of the batch offers maps (EstConst::spread of some item is set)
+template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false, bool SPREAD = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? HCMVS_OCC : 1, !BIG ? HCMVS_OCC : 2))) void sweep_kernel(const EstConst* __restrict__ items, int nItems, int maxRows, SweepSync sy,
                                                         int iter0, int nSweeps, int lag, int affinity, int segLen) {
 	__shared__ RowShared<NW> sh;
@@ -1399,6 +1498,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 	const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave-uniform, and the compiler should know it
 	unsigned evals = 0, issued = 0;
 	unsigned long long taps = 0; // patch taps of the sequential algorithm's evaluations (per source view)
+	SpreadCount spc = {0u, 0u, 0u, 0u};
 	int par = 0, rot = (int)blockIdx.x;
 	STAMP_DECL
 	RowPipe<S> pp;
@@ -1597,7 +1697,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 				continue;
 			}
 			const unsigned e0 = evals;
-			process_pixel<S, NW, BIG, TWO, PACK, HINT>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued STAMP_PASS);
+			process_pixel<S, NW, BIG, TWO, PACK, HINT, SPREAD>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued, spc STAMP_PASS);
 			taps += (unsigned long long)(evals - e0) * (unsigned)((P.a + 1) * (P.a + 1));
 			STAMP(5) // (the pixel loop's back-edge is stamp 13's alone)
 		}
@@ -1617,6 +1717,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 	if ((threadIdx.x & 63) == 0) {
 		if (wv == 0 && evals) { atomicAdd(sy.evals, (unsigned long long)evals); atomicAdd(sy.evals + 2, taps); }
 		if (issued) atomicAdd(sy.evals + 1, (unsigned long long)issued);
+		if constexpr (SPREAD) if (wv == 0) { // the view-spread counters (hcmvs_get_spread_stats) follow the evaluation counters
+			if (spc.scored) atomicAdd(sy.evals + 4, (unsigned long long)spc.scored);
+			if (spc.accepted) atomicAdd(sy.evals + 5, (unsigned long long)spc.accepted);
+			if (spc.dropped) atomicAdd(sy.evals + 6, (unsigned long long)spc.dropped);
+			if (spc.outside) atomicAdd(sy.evals + 7, (unsigned long long)spc.outside);
+		}
 	}
 }
 
@@ -1880,7 +1986,7 @@ void launch_score_pass(const EstConst& c, const float* depthIn, const float* nor
 	else launch_score_big<false, false>(c, evals, s);
 }
 
-template <int NW, bool BIG, bool HINT, bool MASK>
+template <int NW, bool BIG, bool HINT, bool MASK, bool SPREAD>
 static void launch_sweep_nw(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, const SweepSync& sync, int iter, int nSweeps, int lag,
                             int affinity, int segLen, hipStream_t s) {
 	// one workgroup per row; rows beyond the resident set are picked up through the ticket
@@ -1891,44 +1997,54 @@ static void launch_sweep_nw(const EstConst* dItems, int nItems, int maxRows, int
 	// (hypothesis, view) pairs of their own (score_chunk PACK; with one idle group it costs more than it saves)
 	const bool pack = V % 8 != 0 && V % 8 != 7;
 	if (V <= 8) {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, false, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, true, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, false, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, true, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
 	} else {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, false, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, true, HINT, MASK>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, false, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
+		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, true, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
 	}
 
 }
-template <bool HINT, bool MASK>
+template <bool HINT, bool MASK, bool SPREAD>
 static void launch_sweep_hint(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, const SweepSync& sync, int iter, int nSweeps, int lag,
                               int wavesPerRow, int affinity, int segLen, hipStream_t s) {
 	if (bigPatch) { // patches beyond 64 taps: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, true, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, true, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		if (wavesPerRow >= 2) launch_sweep_nw<2, true, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		else launch_sweep_nw<1, true, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
 		return;
 	}
 	if constexpr (HINT) { // the one sweep of a run that carries the hint: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, false, true, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, false, true, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		if (wavesPerRow >= 2) launch_sweep_nw<2, false, true, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		else launch_sweep_nw<1, false, true, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
 		return;
 	}
 	switch (wavesPerRow) {
-	case 1: launch_sweep_nw<1, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 3: launch_sweep_nw<3, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 4: launch_sweep_nw<4, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	default: launch_sweep_nw<2, false, HINT, MASK>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 1: launch_sweep_nw<1, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 3: launch_sweep_nw<3, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
+	case 4: // (a launch with view spread has no four-wave instance: three waves compute the same maps)
+		if constexpr (SPREAD) launch_sweep_nw<3, false, HINT, MASK, true>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		else launch_sweep_nw<4, false, HINT, MASK, false>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
+		break;
+	default: launch_sweep_nw<2, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
 	}
 }
 // One launch for the sweeps iter .. iter + nSweeps - 1 of every item (tickets, rowsDone and the progress words of the items must be
 // zero).  hint: some item of the batch offers the `restore` variant's extra hypothesis in one of these sweeps (EstConst::hintDepth,
 // hintIter): the instance that knows the hint.  mask: some item has a keep-mask (EstConst::keep): the instance that skips its ignored pixels.
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter,
-                  int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
+// spread: some item has view spread to do (EstConst::spread): the instance with the spread rounds.
+template <bool SPREAD>
+static void launch_sweep_spread(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter,
+                                int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
 	if (mask) {
-		if (hint) launch_sweep_hint<true, true>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-		else launch_sweep_hint<false, true>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	} else if (hint) launch_sweep_hint<true, false>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	else launch_sweep_hint<false, false>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+		if (hint) launch_sweep_hint<true, true, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+		else launch_sweep_hint<false, true, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+	} else if (hint) launch_sweep_hint<true, false, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+	else launch_sweep_hint<false, false, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+}
+void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, bool spread, const SweepSync& sync, int iter,
+                  int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
+	if (spread) launch_sweep_spread<true>(dItems, nItems, maxRows, totalRows, V, bigPatch, hint, mask, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+	else launch_sweep_spread<false>(dItems, nItems, maxRows, totalRows, V, bigPatch, hint, mask, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
 }
 
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s) {

@@ -83,7 +83,7 @@ def _device_sync(dev):
 
 
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
-                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None):
+                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -119,6 +119,13 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     params:    binding.Params of the estimate; it_external / n_external_iters are set here
     masks:     optional {image id: (labels (h, w) u16 of any size, [ignored labels])}: --ignore-mask-label for those reference images
                (binding.Context.set_ignore_mask on the rank that estimates them)
+    viewspread: --n-viewspread (DepthMap.cpp:1504-1608): from outer iteration 1 on every pixel also tries what its
+               source views' own maps hold around the place it projects to.  Batch schedule: before each outer iteration >= 1 the maps of
+               ALL images are copied into a second buffer set (one all-gather with several ranks; 20 B per pixel of the scene), which the
+               estimates of that iteration read -- every image sees its source views as the previous outer iteration left them, post-filters
+               included (a Jacobi order).  interleave=True: the reference's own order -- the images are then estimated one after the other in
+               EVERY outer iteration >= 1 (not only the filtered ones) and read the live maps: images < k as this iteration left them (in the
+               last one: after the end pass), images > k from the previous one
     Returns the fused cloud dict of binding.Context.fuse plus `maps`: {id: (depth, normal, conf) device tensors}."""
     import copy
     import numpy as np
@@ -164,6 +171,15 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             by_class.setdefault(8 if len(srcs[img]) <= 8 else 16, []).append(item_of(img, store[row_of(img)].data_ptr()))
         return by_class
 
+    def register_spread(allm):      # every image offers the maps in allm to the estimates it is a source view of
+        for k, img in enumerate(ids):
+            base = allm[slab_index(k, world, n_local)].data_ptr()
+            ctx.set_spread_maps_device(img, base, base + 4 * hw, base + 16 * hw)
+
+    if viewspread:
+        ctx.set_viewspread(True)
+    snapshot = torch.empty_like(slabs) if viewspread and world == 1 and not interleave and n_external_iters > 1 else None
+
     def register(allm):
         for k, img in enumerate(ids):
             row = slab_index(k, world, n_local)
@@ -177,12 +193,15 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     for it in range(int(n_external_iters)):
         p.it_external = it
         filt = postfilter and it in (1, 2)
-        if filt and interleave:
+        spread = bool(viewspread) and it >= 1
+        if (filt or spread) and interleave:
             # the reference's order: estimate(k) -> post-filter(k) -> estimate(k + 1), image ids ascending.  The gathered buffer is the
             # state of the whole scene on every rank; an image is estimated in place by its owner and broadcast before its filter runs
             allm = allgather_maps(slabs, group, out=gathered)
             _device_sync(dev)
             register(allm)
+            if spread:
+                register_spread(allm)   # the live maps: the reference image is never its own source view, so no estimate reads what it writes
             for img in sorted(ids):
                 k = ids.index(img)
                 row = slab_index(k, world, n_local)
@@ -198,14 +217,23 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                     else:
                         dist.broadcast(allm[row], src=dist.get_global_rank(group, owner) if group is not None else owner, group=group)
                     _device_sync(dev)
-                ctx.postfilter(img, ids, **(pf_kw or {}))
+                if filt:
+                    ctx.postfilter(img, ids, **(pf_kw or {}))
             ctx.synchronize()
             if world > 1:
                 for j, img in enumerate(mine):
                     slabs[j].copy_(allm[slab_index(ids.index(img), world, n_local)])
                 _device_sync(dev)
             continue
-        for cls, items in sorted(my_items(slabs, lambda img: mine.index(img)).items()):     # NO collective on the estimation path
+        if spread:      # the maps as the previous outer iteration left them, of every image, apart from the ones being written
+            if world > 1:
+                snap = allgather_maps(slabs, group, out=gathered)
+            else:
+                snapshot.copy_(slabs)
+                snap = snapshot
+            _device_sync(dev)
+            register_spread(snap)
+        for cls, items in sorted(my_items(slabs, lambda img: mine.index(img)).items()):     # NO collective on the estimation path (view spread: the one above)
             for b0 in range(0, len(items), batch):
                 ctx.estimate_batch_device(items[b0:b0 + batch], p)
         ctx.synchronize()
@@ -238,5 +266,9 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     if capacity is None and hasattr(ctx, "fuse_count"):
         cloud["n_depths"] = counted[1]                     # the depths the fusion visited before it invalidated any (SceneDensify.cpp:3461 logs that number)
     cloud["maps"] = maps
+    if viewspread:
+        ctx.set_viewspread(False)
+        for img in ids:
+            ctx.set_spread_maps_device(img, None, None, None)
     cloud["_keep"] = (allm, allr, slabs)                   # the registered device maps must outlive the context's use of them
     return cloud

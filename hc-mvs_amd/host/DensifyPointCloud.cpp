@@ -13,8 +13,10 @@
  * PPM/PGM files (no PNG/JPEG codecs here); the initial maps come from the Delaunay triangulation of the sparse points
  * (--n-initTriangulate 1, the default), from the previous run's maps under <working-folder>/depthmap + normalmap
  * (--n-initTriangulate 0, the fork's hand-off, SceneDensify.cpp:527-553) or from a splat (--min-views-trust-point 1); --n-nOptimize
- * gates the fork's post-filters (RemoveSmallSegments + GapInterpolation) as in the reference; optical flow, semantic priors, view
- * spread and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
+ * gates the fork's post-filters (RemoveSmallSegments + GapInterpolation) as in the reference; --n-viewspread 1 lets every pixel also try
+ * the estimates of its source views' own maps from outer iteration 1 on (DepthMap.cpp:1504-1608; default 0 here, 1 in the reference, so
+ * that existing command lines keep their results; one device); optical flow, semantic priors and SGM modes are not available and
+ * the corresponding flags are accepted and ignored with a note.
  *
  * How the run is laid out in time (the reference overlaps image k + 1's InitViews with image k's estimate, SceneDensify.cpp:3699-3703;
  * here the unit is a batch of reference images):
@@ -68,6 +70,8 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	int nOptimize = 2;            // --n-nOptimize (DensifyPointCloud.cpp:164, 268): bits REMOVE_SPECKLES 1 | FILL_GAPS 2 (DepthMap.h:113-118) gate the fork's
 	                              // RemoveSmallSegments + GapInterpolation after outer iterations 1 and 2 (SceneDensify.cpp:3916, 3939-3958)
 	int postFilter = -1;          // --n-postfilter 0|1: override of that gate (-1: follow --n-nOptimize)
+	int viewspread = 0;           // --n-viewspread 1: view spread (DepthMap.cpp:1504-1608).  The reference's default is 1; 0 here keeps
+	                              // the results of every existing command line
 	int postFilterInterleave = 0; // --n-postfilter-interleave 1: estimate(k) -> post-filter(k) -> estimate(k + 1), the reference's own order
 	                              // (SceneDensify.cpp:3889-3965), one image per launch; 0: estimate all, then filter all
 	int resume = 1;               // skip-if-exists (SceneDensify.cpp:3865-3880): an image whose final depth map is already in the working folder is not estimated again
@@ -772,7 +776,7 @@ int main(int argc, char** argv) {
 	geti("--n-propagatehalfwin", o.propagateHalfWin); geti("--n-propagatestep", o.propagateStep);
 	getf("--n-photometric_flow", o.photometricFlow); getf("--depthweight", o.depthweight); getf("--normalweight", o.normalweight);
 	geti("--n-initTriangulate", o.initTriangulate); geti("--min-views-trust-point", o.minViewsTrustPoint);
-	geti("--fuse-order", o.fuseOrder); geti("--fuse-count", o.fuseCount); geti("--restore-hypothesis", o.restoreHypothesis); geti("--n-postfilter", o.postFilter); geti("--n-postfilter-interleave", o.postFilterInterleave); geti("--n-nOptimize", o.nOptimize); geti("--resume", o.resume);
+	geti("--fuse-order", o.fuseOrder); geti("--fuse-count", o.fuseCount); geti("--restore-hypothesis", o.restoreHypothesis); geti("--n-postfilter", o.postFilter); geti("--n-postfilter-interleave", o.postFilterInterleave); geti("--n-nOptimize", o.nOptimize); geti("--resume", o.resume); geti("--n-viewspread", o.viewspread);
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -788,7 +792,7 @@ int main(int argc, char** argv) {
 	geti("--estimate-colors", o.estimateColors); geti("--estimate-normals", o.estimateNormals);
 	geti("--max-resolution", o.maxResolution); geti("--min-resolution", o.minResolution);
 	if (o.postFilter < 0) o.postFilter = (o.nOptimize & 3) != 0 ? 1 : 0; // OPTDENSE::OPTIMIZE = REMOVE_SPECKLES | FILL_GAPS (DepthMap.h:113-118)
-	for (const char* k : {"--n-opticalflow", "--n-viewspread", "--use-semantic", "--n-usegeoconsistency", "--n-usepartconsistency"})
+	for (const char* k : {"--n-opticalflow", "--use-semantic", "--n-usegeoconsistency", "--n-usepartconsistency"})
 		if (kv.count(k) && atoi(kv[k].c_str()) != 0 && o.verbosity > 1)
 			fprintf(stderr, "note: %s is not available in this build (defined subset); treated as 0\n", k);
 	const int thFilterPointCloud = kv.count("--filter-point-cloud") ? atoi(kv["--filter-point-cloud"].c_str()) : 0; // >= 0: no effect, as in the reference
@@ -796,6 +800,8 @@ int main(int argc, char** argv) {
 	if (o.input.empty() || kv.count("--help")) {
 		fprintf(stderr, "usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
 		                "[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n"
+		                "       --n-viewspread 0|1   from outer iteration 1 on every pixel also tries what its source views' depth maps hold where it projects to\n"
+		                "                            (default 0; the reference's default is 1 -- 0 keeps the results of command lines written before it existed)\n"
 		                "       DensifyPointCloud -i dense.mvs [-o out.mvs] --filter-point-cloud <negative threshold>   (visibility filter of the cloud only:\n"
 		                "       writes <out>_filtered.mvs and <out>_filtered.ply)\n");
 		return EXIT_FAILURE;
@@ -896,6 +902,7 @@ int main(int argc, char** argv) {
 		if (d.createRc != HCMVS_OK) { fprintf(stderr, "error: device %d is not a usable MI355X (there is no CPU path)\n", d.ordinal); return EXIT_FAILURE; }
 	hcmvs_ctx* ctx = devs[0].ctx; // the context of the post-filters and the fusion
 	if (hipSetDevice(o.device) != hipSuccess) { fprintf(stderr, "error: hipSetDevice failed\n"); return EXIT_FAILURE; }
+	if (nDev > 1 && o.viewspread) { fprintf(stderr, "error: --n-viewspread 1 runs on one device: every estimate reads the depth maps of its source views, which other devices would hold (drop --devices)\n"); return EXIT_FAILURE; }
 	if (nDev > 1 && o.postFilterInterleave) { fprintf(stderr, "error: --n-postfilter-interleave 1 estimates one image at a time and runs on one device (drop --devices)\n"); return EXIT_FAILURE; }
 	std::vector<uint32_t> todo;
 	for (auto& im : images) {
@@ -1294,7 +1301,8 @@ int main(int argc, char** argv) {
 
 	const double tInit = now_s();
 	double tPostfilter = 0;
-	const bool filterOnLast = o.postFilter && (o.estimationItersExternal - 1 == 1 || o.estimationItersExternal - 1 == 2);
+	const bool filterOnLast = (o.postFilter && (o.estimationItersExternal - 1 == 1 || o.estimationItersExternal - 1 == 2)) ||
+	                          (o.postFilterInterleave && o.viewspread && o.estimationItersExternal - 1 >= 1); // (the main thread hands the last iteration's maps to the saver)
 	// one launch set for the reference images `ids` (all of device context d)
 	auto estimate_images = [&](int d, const std::vector<uint32_t>& ids, const hcmvs_params& pr, std::string& err) -> bool {
 		hcmvs_ctx* dctx = devs[(size_t)d].ctx;
@@ -1360,6 +1368,36 @@ int main(int argc, char** argv) {
 		}
 		return true;
 	};
+	// --n-viewspread (one device): what the source views offer.  Batch schedule: before every outer iteration >= 1 the maps of all images are
+	// copied into a second buffer set (20 B per pixel of the scene) -- every estimate of the iteration reads its source views as the previous
+	// iteration left them, post-filters included.  Interleaved schedule: the live maps (the reference's order; an image is never its own
+	// source view, and one image is estimated per call).
+	struct SpreadSnap { float *d = nullptr, *n = nullptr, *c = nullptr; };
+	std::map<uint32_t, SpreadSnap> spreadSnap;
+	struct SnapFree { std::map<uint32_t, SpreadSnap>& m; ~SnapFree() { for (auto& kv : m) for (float* q : {kv.second.d, kv.second.n, kv.second.c}) if (q) (void)hipFree(q); } } snapFree{spreadSnap};
+	auto offer_spread_maps = [&](bool live, std::string& err) -> bool {
+		if (hcmvs_synchronize(ctx) != HCMVS_OK) { err = hcmvs_last_error(ctx); return false; }
+		for (uint32_t id : todo) {
+			ImageData& im = images[id];
+			if (!im.dDepth || !im.dNormal || !im.dConf) continue;
+			const size_t n = (size_t)im.w * im.h;
+			const float *sd = im.dDepth, *sn = im.dNormal, *sc = im.dConf;
+			if (!live) {
+				SpreadSnap& sp = spreadSnap[id];
+				if (!sp.d && (hipMalloc(&sp.d, n * 4) != hipSuccess || hipMalloc(&sp.n, n * 12) != hipSuccess || hipMalloc(&sp.c, n * 4) != hipSuccess)) { err = "no device memory for the view-spread copy of the depth maps (20 B per pixel of the scene)"; return false; }
+				if (hipMemcpyAsync(sp.d, im.dDepth, n * 4, hipMemcpyDeviceToDevice, xs) != hipSuccess || hipMemcpyAsync(sp.n, im.dNormal, n * 12, hipMemcpyDeviceToDevice, xs) != hipSuccess ||
+				    hipMemcpyAsync(sp.c, im.dConf, n * 4, hipMemcpyDeviceToDevice, xs) != hipSuccess) { err = "copying the depth maps for view spread failed"; return false; }
+				sd = sp.d; sn = sp.n; sc = sp.c;
+			}
+			if (hcmvs_set_spread_maps_device(ctx, id, sd, sn, sc) != HCMVS_OK) { err = hcmvs_last_error(ctx); return false; }
+		}
+		if (hipStreamSynchronize(xs) != hipSuccess) { err = "copying the depth maps for view spread failed"; return false; }
+		return true;
+	};
+	if (o.viewspread) CHK(hcmvs_set_viewspread(ctx, 1));
+	// an outer iteration that the main thread runs image after image: the interleaved schedule, where it filters and -- with view spread -- in
+	// every outer iteration >= 1
+	auto serial_iteration = [&](int it) { return o.postFilterInterleave && !work.empty() && ((o.postFilter && (it == 1 || it == 2)) || (o.viewspread && it >= 1)); };
 	const int nMinViewsFuse = std::min<int>(o.numberViewsFuse, (int)images.size());
 	// outer iterations over all images (SceneDensify.cpp:3684).  Every device context has a host thread that estimates the context's
 	// batches; where an outer iteration ends with the post-filters the threads meet, the main thread gathers the maps on the first
@@ -1385,7 +1423,12 @@ int main(int argc, char** argv) {
 			pr.it_external = it;
 			const bool last = it == o.estimationItersExternal - 1;
 			const bool filtered = o.postFilter && (it == 1 || it == 2) && !work.empty();
-			if (!(filtered && o.postFilterInterleave)) { // (the interleaved mode runs on the main thread, one device)
+			const bool serial = serial_iteration(it);
+			if (!serial) { // (the interleaved mode runs on the main thread, one device)
+				if (o.viewspread && it >= 1) { // (one device: this is the only worker, and the previous iteration's filters are done)
+					std::string err;
+					if (!offer_spread_maps(false, err)) { fail_run(err); return; }
+				}
 				for (size_t b = 0; b < batches.size(); ++b) {
 					if (batches[b].dev != d) continue;
 					{ std::lock_guard<std::mutex> g(runMu); if (!runError.empty()) return; }
@@ -1395,7 +1438,7 @@ int main(int argc, char** argv) {
 					if (last && !filterOnLast) saver_submit(batches[b].ids); // final maps of this batch: off to the host while the next batch runs
 				}
 			}
-			if (filtered) { // meet the others; the main thread filters
+			if (filtered || serial) { // meet the others; the main thread filters
 				std::unique_lock<std::mutex> g(runMu);
 				++arrived;
 				runCv.notify_all();
@@ -1414,7 +1457,8 @@ int main(int argc, char** argv) {
 		// iterations 1 and 2 every image goes through RemoveSmallSegments (in the fork: a whole fusion pass over the current maps of all
 		// images) and GapInterpolation
 		const bool filtered = o.postFilter && (it == 1 || it == 2) && !work.empty();
-		if (!filtered) continue;
+		const bool serial = serial_iteration(it);
+		if (!filtered && !serial) continue;
 		{ // every device has finished the estimates of this outer iteration (or, interleaved mode, is waiting for the main thread to run it)
 			std::unique_lock<std::mutex> g(runMu);
 			runCv.wait(g, [&] { return arrived == nDev || !runError.empty(); });
@@ -1425,7 +1469,11 @@ int main(int argc, char** argv) {
 		if (!exchange_maps(true)) { fprintf(stderr, "error: gathering the depth maps on device %d failed\n", devs[0].ordinal); return EXIT_FAILURE; }
 		if (!register_maps()) return EXIT_FAILURE;
 		uint64_t filledAll = 0;
-		if (o.postFilterInterleave) {
+		if (serial) {
+			if (o.viewspread && it >= 1) {
+				std::string err;
+				if (!offer_spread_maps(true, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return EXIT_FAILURE; }
+			}
 			// the reference's order, exactly (single-thread event loop, SceneDensify.cpp:3889-3965: EVTEstimateDepthMap(k) queues
 			// EVTOptimizeDepthMap(k) FIRST): image k is filtered right after its own estimate, so its fusion sees the images > k as the
 			// previous outer iteration left them and zeroes depths in them before they are estimated again.  One image per launch: the
@@ -1436,6 +1484,7 @@ int main(int argc, char** argv) {
 			for (uint32_t id : work) {
 				std::string err;
 				if (!estimate_images(0, std::vector<uint32_t>(1, id), pr, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return EXIT_FAILURE; }
+				if (!filtered) continue; // (view spread alone: image after image, nothing to filter in this outer iteration)
 				const double t0 = now_s();
 				uint64_t filled = 0;
 				CHK(hcmvs_postfilter(ctx, id, filterOrder.data(), (int32_t)filterOrder.size(), nMinViewsFuse, 0.01f, 25.f, 7, &filled));
@@ -1443,7 +1492,8 @@ int main(int argc, char** argv) {
 				tf += now_s() - t0;
 			}
 			tPostfilter += tf;
-			if (o.verbosity > 1) printf("Depth-maps estimated and filtered image after image in outer iteration %d (the reference's order): %llu pixels filled "
+			if (o.verbosity > 1 && !filtered) printf("Depth-maps estimated image after image in outer iteration %d (the reference's order, view spread on the live maps) (%.2f s)\n", it, now_s() - tp);
+			else if (o.verbosity > 1) printf("Depth-maps estimated and filtered image after image in outer iteration %d (the reference's order): %llu pixels filled "
 			                            "(%.2f s, %.2f s of it post-filters)\n", it, (unsigned long long)filledAll, now_s() - tp, tf);
 		} else {
 			// the batch schedule of the post-filters: every image of the outer iteration has been estimated, now

@@ -167,6 +167,31 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* ctx, const hcmvs_batch_item* items, i
 /* synchronises, then reports counters/timings of the last estimate (summed over the items of a batch) */
 int hcmvs_get_stats(hcmvs_ctx* ctx, hcmvs_stats* out);
 
+/* ---- view spread (DensifyPointCloud --n-viewspread; DepthEstimator::ProcessPixel, DepthMap.cpp:1504-1608) --------------------
+ * From outer iteration 1 on (params->it_external >= 1), after its refinement trials, every pixel that did not leave through the
+ * full-random branch also tries the estimates its SOURCE views' own maps hold around the place it projects to: per source view, in
+ * the estimate's view order, the four neighbours of the projected pixel in that view's map (depth brought into the reference camera,
+ * normal as stored, CorrectNormal, accepted when the score improves); they also become the pixel's smoothness set.  What the
+ * reference leaves undefined is fixed in DESIGN.md section 5, D10. */
+/* switch view spread on (non-zero) or off for the estimates that follow.  Default 0 (the reference's default is 1): every caller that
+ * does not ask for it computes what it computed before the feature existed. */
+int hcmvs_set_viewspread(hcmvs_ctx* ctx, int32_t on);
+/* the maps view `id` offers when it is a source view of an estimate with view spread on: DEVICE memory of the view's image size
+ * (depth w*h, normal w*h*3 in the view's camera frame, conf w*h: the score, as an estimate leaves it between outer iterations),
+ * caller-owned, not copied, read by the estimates that follow.  All three NULL removes them; registering the view again or
+ * hcmvs_release_view drops them.  A view without maps, and a view made by hcmvs_rescale_view (refused here: there are no maps of
+ * its size), never spreads.  An estimate must not write the maps it reads: hcmvs_estimate_batch_device fails with
+ * HCMVS_ERR_INVALID when the in/out maps of an item overlap the spread maps of a source view of any item of the same call. */
+int hcmvs_set_spread_maps_device(hcmvs_ctx* ctx, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf);
+/* counters of the view spread of the last estimate (summed over the items of a batch and its sweeps); synchronises */
+typedef struct {
+	uint64_t slots_scored;       /* hypotheses taken from source views' maps and scored (they are part of hcmvs_stats::evals) */
+	uint64_t slots_accepted;     /* ... that replaced the pixel's estimate */
+	uint64_t slots_dropped;      /* not scored: their depth in the reference camera was not positive */
+	uint64_t candidates_outside; /* candidate pixels beyond the source view's map (a source view smaller than the reference image) */
+} hcmvs_spread_stats;
+int hcmvs_get_spread_stats(hcmvs_ctx* ctx, hcmvs_spread_stats* out);
+
 /* SceneDensify.cpp:783-808: splat n_points sparse world points (xyz f32) seen by view `id` as 5x5 blocks
  * into host maps depth (w*h) / normal (w*h*3); returns the depth range (min*0.9, max*1.1). Host-side helper. */
 int hcmvs_splat_init(hcmvs_ctx* ctx, uint32_t id, const float* points_xyz, int32_t n_points, float* depth,
