@@ -85,13 +85,13 @@ struct hcmvs_ctx final : Reclaimer {
 	int viewspread = 0;                   // hcmvs_set_viewspread
 	bool haveSpreadStats = false;         // the last estimate ran with view spread in effect
 	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
-	int sweepPerLaunch = 0;               // HCMVS_SWEEP_LAUNCHES: 0 automatic (one launch for all sweeps from 16 images on), 1 per-sweep, 2 one
+	int sweepPerLaunch = 0;               // HCMVS_SWEEP_LAUNCHES: 0 automatic, 1 per-sweep, 2 one (sweep_plan.h)
 	DevBuf evals{this};                   // unsigned long long [4]
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	int lastSweeps = 0, lastSweepLaunches = 0;
 	bool haveStats = false;
 	int sweepLag = 1;
-	int sweepSegment = -1; // columns per ticket of the sweep worker: -1 = automatic (see the launch of the sweeps), 0 = whole rows
+	int sweepSegment = -1; // columns per ticket of the sweep worker: -1 = automatic (sweep_plan.h), 0 = whole rows
 	int fuseOrder = 0; // hcmvs_set_fuse_order
 	int xcdAffinity = 1; // rows of an image prefer the workgroups of one XCD (HCMVS_XCD_AFFINITY=0 turns it off)
 	// filter / fuse scratch
@@ -101,10 +101,10 @@ struct hcmvs_ctx final : Reclaimer {
 	DevBuf passScratch{this}; // per-pass tables of the fusion (hcmvs_fuse_cloud, hcmvs_postfilter_sequence)
 	DevBuf pfState;           // the post-filter chain's state kept from fusion to fusion (pf_kernels.hip); never reserved with the reclaimer
 	bool errPending = false; // an estimate was enqueued since the error word was last read
-	int nCU = 0;          // compute units of the device: 4 SIMDs x 3 sweep workers each (the waves-per-row policy)
+	int nCU = 0;          // compute units of the device (sweep_plan.h)
 	hipEvent_t upEv[2] = {nullptr, nullptr};
 	char* pinned = nullptr; size_t capPinned = 0; // page-locked staging of the host-buffer uploads (a pageable hipMemcpy crawls at ~1.3 GB/s here)
-	int wavesPerRow = 0; // 0 = automatic: 3 waves per row for one image, 2 for two (latency), 1 when >= 3 images fill the chip
+	int wavesPerRow = 0; // HCMVS_WAVES_PER_ROW: 1..4 requested, 0 = automatic by the batch's rows (sweep_plan.h)
 
 	bool reclaim() override {
 		if (!pfState.capacity()) return false;
@@ -630,6 +630,29 @@ static inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) 
 	return a0 < b0 + nb && b0 < a0 + na;
 }
 
+// view spread: a launch must not read what it writes -- the in/out maps of no item may overlap the spread maps of a source view of any item
+static int check_spread_overlap(hcmvs_ctx* c, const hcmvs_batch_item* items, int n_items) {
+	for (int i = 0; i < n_items; ++i) {
+		const size_t n = (size_t)c->hItems[i].W * c->hItems[i].H;
+		for (int k = 0; k < n_items; ++k)
+			for (int v = 0; v < items[k].n_src; ++v) {
+				const SpreadView& sv = c->hSpread[(size_t)k * kMaxViews + v];
+				if (!c->hItems[k].spread || !sv.depth) continue;
+				const size_t m = (size_t)sv.w * sv.h;
+				const void* io[3] = {items[i].d_depth, items[i].d_normal, items[i].d_conf};
+				const size_t ion[3] = {n * 4, n * 12, n * 4};
+				const void* sp[3] = {sv.depth, sv.normal, sv.conf};
+				const size_t spn[3] = {m * 4, m * 12, m * 4};
+				for (int a = 0; a < 3; ++a)
+					for (int b = 0; b < 3; ++b)
+						if (overlaps(io[a], ion[a], sp[b], spn[b]))
+							return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the spread maps of source view %u of item %d: "
+							            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", i, items[i].ref_id, items[k].src_ids[v], k);
+			}
+	}
+	return HCMVS_OK;
+}
+
 int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!items || !p) return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
@@ -638,38 +661,23 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 	if (p->n_estimation_iters < 0 || p->n_random_iters < 0 || p->n_random_iters > 20)
 		return fail(c, HCMVS_ERR_INVALID, "estimate: bad iteration counts");
 	HIPCHK(c, hipSetDevice(c->device));
-	int maxRows = 0, totalRows = 0;
+	int maxRows = 0;
+	bool spread = false;
+	hcmvs::SweepBatch batch;
+	batch.big = p->adapthalfwin > kHalfWindow; batch.nSweeps = p->n_estimation_iters; batch.nCU = c->nCU;
+	batch.sweepPerLaunch = c->sweepPerLaunch; batch.sweepSegment = c->sweepSegment; batch.wavesPerRow = c->wavesPerRow;
 	for (int i = 0; i < n_items; ++i) {
 		if (items[i].n_src < 1 || items[i].n_src > kMaxViews || hcmvs::segments_for(items[i].n_src) != hcmvs::segments_for(items[0].n_src))
 			return fail(c, HCMVS_ERR_INVALID, "estimate: the items of a batch must use source-view counts of one class (1-8 or 9-16)");
 		int rc = build_item(c, i, items[i], p, c->hItems[i]);
 		if (rc) return rc;
-		const int rows = c->hItems[i].H - 2 * c->hItems[i].border;
+		const EstConst& k = c->hItems[i];
+		const int rows = k.H - 2 * k.border;
 		if (rows > maxRows) maxRows = rows;
-		totalRows += rows;
+		spread = spread || k.spread;
+		batch.items.push_back({rows, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == batch.nSweeps - 1, k.keep != nullptr, k.spread != nullptr});
 	}
-	// view spread: a launch must not read what it writes -- the in/out maps of no item may overlap the spread maps of a source view of any item
-	bool spread = false;
-	for (int i = 0; i < n_items; ++i) spread = spread || c->hItems[i].spread;
-	if (spread)
-		for (int i = 0; i < n_items; ++i) {
-			const size_t n = (size_t)c->hItems[i].W * c->hItems[i].H;
-			for (int k = 0; k < n_items; ++k)
-				for (int v = 0; v < items[k].n_src; ++v) {
-					const SpreadView& sv = c->hSpread[(size_t)k * kMaxViews + v];
-					if (!c->hItems[k].spread || !sv.depth) continue;
-					const size_t m = (size_t)sv.w * sv.h;
-					const void* io[3] = {items[i].d_depth, items[i].d_normal, items[i].d_conf};
-					const size_t ion[3] = {n * 4, n * 12, n * 4};
-					const void* sp[3] = {sv.depth, sv.normal, sv.conf};
-					const size_t spn[3] = {m * 4, m * 12, m * 4};
-					for (int a = 0; a < 3; ++a)
-						for (int b = 0; b < 3; ++b)
-							if (overlaps(io[a], ion[a], sp[b], spn[b]))
-								return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the spread maps of source view %u of item %d: "
-								            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", i, items[i].ref_id, items[k].src_ids[v], k);
-				}
-		}
+	if (spread) { int rc = check_spread_overlap(c, items, n_items); if (rc) return rc; }
 	hipStream_t s = c->stream;
 	// same stream => the previous call's kernels are done with these tables before the copies land
 	if (spread) HIPCHK(c, hipMemcpyAsync(c->dSpread.get(), c->hSpread.data(), sizeof(SpreadView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
@@ -693,64 +701,18 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s);
 	}
 	HIPCHK(c, hipEventRecord(c->ev[1], s));
-	SweepSync sy;
 	int32_t* sync = c->sync.get<int32_t>();
-	sy.ticket = sync + 16; sy.rowsDone = sync + 16 + kMaxBatch; sy.error = sync + 1; sy.evals = c->evals.get<unsigned long long>();
-	// A batch whose rows fill the chip four times over (12 images of 1080p or more) runs all its sweeps in ONE launch (round 4): the images go
-	// through their sweeps independently of each other, without a chip-wide drain and refill between two sweeps (+5 % at 12, +7 % at 16 images,
-	// +2.6 ... 3.5 % at 32; profiles/r04_launch_modes.txt).  Fewer images are bound by the latency of their row wavefronts, not by the
-	// chip, and gain nothing from it (measured: 4 -> 8 % slower), so they keep one launch per sweep.  HCMVS_SWEEP_LAUNCHES=one | per-sweep
-	// overrides.  The `restore` variant's extra hypothesis belongs to the last sweep of the last outer iteration: that sweep then
-	// gets a launch of its own, with the kernel instance that knows the hint.
-	{
-		const int nSweeps = p->n_estimation_iters;
-		bool hintLast = false;
-		for (int i = 0; i < n_items; ++i) hintLast = hintLast || (c->hItems[i].hintDepth && c->hItems[i].hintIter == nSweeps - 1);
-		bool mask = false; // some item has a keep-mask: the sweep instance that skips ignored pixels
-		for (int i = 0; i < n_items; ++i) mask = mask || c->hItems[i].keep;
-		// Waves per row, by how the batch's rows compare with the workers the chip holds at once (12 per CU; measured on 1080p images,
-		// profiles/r04_launch_modes.txt): a batch of few rows is bound by the latency of one pixel along the (W + H) critical path of its row
-		// wavefronts, and the scoring of a pixel's hypotheses divides among the waves of a row -- three waves for one image (1066 rows), two
-		// for two or three (a lone 3840x2160 image has 2146 rows: two), one from there on, where the chip's throughput counts.  More waves
-		// than workers are fine since the rows are handed out in stretches (below): a row no longer needs a worker of its own from its
-		// first to its last column.
-		const int slots = (c->nCU > 0 ? c->nCU : 256) * (p->adapthalfwin > kHalfWindow ? 8 : 12); // (the big-patch worker: two waves per SIMD)
-		const int nw = c->wavesPerRow ? c->wavesPerRow : (10 * totalRows <= 4 * slots ? 3 : (10 * totalRows <= 11 * slots ? 2 : 1));
-		// the launcher picks the kernel variant by view count: an item whose count leaves two or more view groups idle wants the
-		// pair-packing variant, which is correct for the other items of its layout class too
-		int vSel = items[0].n_src;
-		for (int i = 0; i < n_items; ++i) if (items[i].n_src % 8 != 0 && items[i].n_src % 8 != 7) vSel = items[i].n_src;
-		int first = 0, nLaunches = 0;
-		c->lastSweepLaunches = 0;
-		while (first < nSweeps) {
-			const bool perSweep = c->sweepPerLaunch == 1 || (c->sweepPerLaunch == 0 && totalRows < 4 * slots);
-			int count = perSweep ? 1 : nSweeps - first;
-			bool hint = false;
-			if (hintLast) { if (first == nSweeps - 1) hint = true; else if (first + count == nSweeps) --count; } // the hint sweep runs alone
-			HIPCHK(c, hipMemsetAsync(sync + 16, 0, sizeof(int32_t) * 2 * kMaxBatch, s)); // tickets + rowsDone; the error word stays sticky
-			for (int i = 0; i < n_items; ++i)
-				HIPCHK(c, hipMemsetAsync(c->slots[i].progress.get(), 0, (size_t)(c->hItems[i].H - 2 * c->hItems[i].border) * kProgressStride * sizeof(int32_t), s));
-			// A launch of ONE sweep with more waves than the chip holds workers (and less than four times as many rows: from there on all
-			// sweeps run in one launch) hands out stretches of 256 columns instead of whole rows: a worker's slot comes free after 256 pixels.
-			// With whole rows the rows beyond the resident set begin only when row 0 has reached its end -- 8 images: 107.2 -> 100.3 ms per
-			// sweep; it is also what lets one to three images have two or three waves per row (1: 35.6 -> 33.7 ms, 2: 46.1 -> 42.0,
-			// 3: 59.9 -> 55.4); 4 and 5 images: 0 ... +2 % (profiles/r04_launch_modes.txt).  HCMVS_SWEEP_SEGMENT=N forces stretches of N
-			// columns, 0 whole rows.
-			int segLen = 0, tickets = totalRows;
-			if (c->sweepSegment > 0 || (c->sweepSegment < 0 && count == 1 && nw * totalRows > slots && totalRows < 4 * slots)) {
-				segLen = c->sweepSegment > 0 ? c->sweepSegment : 256;
-				if (segLen < 32) segLen = 32; // (the ring of a row's latest results is re-read from memory at the start of a stretch)
-				tickets = 0;
-				for (int i = 0; i < n_items; ++i) {
-					const int rows = c->hItems[i].H - 2 * c->hItems[i].border, cols = c->hItems[i].W - 2 * c->hItems[i].border;
-					tickets += rows * ((cols + segLen - 1) / segLen);
-				}
-			}
-			launch_sweep(c->dItems.get<EstConst>(), n_items, maxRows, tickets, vSel, p->adapthalfwin > kHalfWindow, hint, mask, spread, sy, first, count, c->sweepLag, nw, c->xcdAffinity, segLen, s);
-			first += count; ++nLaunches;
-		}
-		c->lastSweepLaunches = nLaunches;
+	const SweepArgs sa{c->dItems.get<EstConst>(), n_items, maxRows, {sync + 16, sync + 16 + kMaxBatch, sync + 1, c->evals.get<unsigned long long>()}, c->sweepLag, c->xcdAffinity};
+	const std::vector<hcmvs::SweepLaunch> plan = hcmvs::plan_sweeps(batch); // HCMVS_SWEEP_LAUNCHES, HCMVS_SWEEP_SEGMENT, HCMVS_WAVES_PER_ROW
+	for (const hcmvs::SweepLaunch& l : plan) {
+		HIPCHK(c, hipMemsetAsync(sync + 16, 0, sizeof(int32_t) * 2 * kMaxBatch, s)); // tickets + rowsDone; the error word stays sticky
+		for (int i = 0; i < n_items; ++i)
+			HIPCHK(c, hipMemsetAsync(c->slots[i].progress.get(), 0, (size_t)batch.items[i].rows * kProgressStride * sizeof(int32_t), s));
+		if (!launch_sweep(sa, l, s))
+			return fail(c, HCMVS_ERR_INVALID, "estimate: no sweep kernel for %d waves per row, big %d two %d pack %d hint %d mask %d spread %d",
+			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread);
 	}
+	c->lastSweepLaunches = (int)plan.size();
 	HIPCHK(c, hipEventRecord(c->ev[2], s));
 	for (int i = 0; i < n_items; ++i)
 		launch_end_pass(c->hItems[i], p->it_external == p->n_external_iters - 1 ? 1 : 0, items[i].d_depth, items[i].d_normal, items[i].d_conf, s);

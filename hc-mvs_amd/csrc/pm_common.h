@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility> // std::integer_sequence: the kernel tables of pm_kernels.hip
+#include "sweep_plan.h"
 
 namespace hcmvs {
 
@@ -81,9 +83,13 @@ struct SweepSync {
 	                            // [4 .. 8) view spread: slots scored, slots accepted, slots dropped (depth <= 0), candidates outside the view's map
 };
 
-// lane layout class for V source views (the items of a batch must share it): 8 for up to 8 views, 4 for 9..16 views, which run
-// the 8 x 8 lane layout twice (two sets of eight view groups)
-int segments_for(int V);
+// what all sweep launches of one call share
+struct SweepArgs {
+	const EstConst* dItems;
+	int nItems, maxRows;
+	SweepSync sync;
+	int lag, affinity;
+};
 
 // launch wrappers (pm_kernels.hip)
 void launch_gray_to_u8(const float* gray, uint8_t* out, int n, hipStream_t s);
@@ -94,8 +100,7 @@ void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, 
 void launch_quads(const float* gray, float4* out, int W, int H, hipStream_t s); // 2 x 2 footprint layout of a source view
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
                        hipStream_t s);
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, bool spread, const SweepSync& sync, int iter, int nSweeps,
-                  int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s); // segLen > 0: tickets are stretches of segLen columns of a row
+bool launch_sweep(const SweepArgs& a, const SweepLaunch& l, hipStream_t s); // false: the library holds no instance l.v (nothing is launched)
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s);
 
 } // namespace hcmvs

@@ -1946,11 +1946,6 @@ void debug_read_stamps(unsigned long long* out, int reset) {
 }
 #endif
 
-// lane layout class of an estimate with V source views.  Every estimate runs the 8 view groups x 8 tap segments layout: once
-// for up to 8 views (class 8), twice for 9..16 (class 4: two sets of eight view groups, TWO in the kernels); view counts that
-// leave groups idle let them work on (hypothesis, view) pairs of their own (PACK)
-int segments_for(int V) { return V <= 8 ? 8 : 4; }
-
 void launch_gray_to_u8(const float* gray, uint8_t* out, int n, hipStream_t s) {
 	hipLaunchKernelGGL(gray_to_u8_kernel, dim3(2048), dim3(256), 0, s, gray, out, n);
 }
@@ -1970,81 +1965,46 @@ void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, 
 	hipLaunchKernelGGL(apply_mask_kernel, dim3(2048), dim3(256), 0, s, keep, depth, normal, n);
 }
 
-template <bool BIG, bool MASK>
-static void launch_score_big(const EstConst& c, unsigned long long* evals, hipStream_t s) {
-	const dim3 grid(4096), block(256);
-	if (c.V <= 8) hipLaunchKernelGGL((score_kernel<8, BIG, false, MASK>), grid, block, 0, s, c, evals);
-	else hipLaunchKernelGGL((score_kernel<8, BIG, true, MASK>), grid, block, 0, s, c, evals); // 9..16 views: two sets of eight
-
+// score_kernel<8, BIG, TWO, MASK> by (BIG, TWO, MASK): all eight exist
+template <class K, int N>
+struct KernelTable { K at[N]; };
+using ScoreKernel = void (*)(EstConst, unsigned long long*);
+template <int... I>
+static constexpr KernelTable<ScoreKernel, sizeof...(I)> score_table(std::integer_sequence<int, I...>) {
+	return {{score_kernel<8, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0>...}};
 }
+static constexpr auto kScoreKernels = score_table(std::make_integer_sequence<int, 8>{});
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
                        hipStream_t s) {
 	hipLaunchKernelGGL(import_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn);
-	const bool big = c.adapthalfwin > kHalfWindow;
-	if (c.keep) { if (big) launch_score_big<true, true>(c, evals, s); else launch_score_big<false, true>(c, evals, s); }
-	else if (big) launch_score_big<true, false>(c, evals, s);
-	else launch_score_big<false, false>(c, evals, s);
+	// 9..16 views: two sets of eight
+	hipLaunchKernelGGL(kScoreKernels.at[(c.adapthalfwin > kHalfWindow ? 4 : 0) | (c.V > 8 ? 2 : 0) | (c.keep ? 1 : 0)], dim3(4096), dim3(256), 0, s, c, evals);
 }
 
-template <int NW, bool BIG, bool HINT, bool MASK, bool SPREAD>
-static void launch_sweep_nw(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, const SweepSync& sync, int iter, int nSweeps, int lag,
-                            int affinity, int segLen, hipStream_t s) {
-	// one workgroup per row; rows beyond the resident set are picked up through the ticket
-	int grid = totalRows < 8192 ? totalRows : 8192;
-	if (grid < 1) return;
-	const dim3 g(grid), b(64 * NW);
-	// a view count that leaves two or more of a set's eight view groups idle takes the variant whose idle groups work on
-	// (hypothesis, view) pairs of their own (score_chunk PACK; with one idle group it costs more than it saves)
-	const bool pack = V % 8 != 0 && V % 8 != 7;
-	if (V <= 8) {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, false, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, false, true, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-	} else {
-		if (!pack) hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, false, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-		else hipLaunchKernelGGL((sweep_kernel<8, NW, BIG, true, true, HINT, MASK, SPREAD>), g, b, 0, s, dItems, nItems, maxRows, sync, iter, nSweeps, lag, affinity, segLen);
-	}
+// sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD> by SweepVariant: exactly the instances sweep_variant_exists admits, null elsewhere
+using SweepKernel = void (*)(const EstConst*, int, int, SweepSync, int, int, int, int, int);
+constexpr int sweep_variant_index(SweepVariant v) {
+	return (v.nw - 1) << 6 | v.big << 5 | v.two << 4 | v.pack << 3 | v.hint << 2 | v.mask << 1 | (int)v.spread;
+}
+constexpr SweepVariant sweep_variant_at(int i) {
+	return {(i >> 6) + 1, (i & 32) != 0, (i & 16) != 0, (i & 8) != 0, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0};
+}
+template <int I>
+static constexpr SweepKernel sweep_instance() {
+	constexpr SweepVariant v = sweep_variant_at(I);
+	if constexpr (sweep_variant_exists(v)) return sweep_kernel<8, v.nw, v.big, v.two, v.pack, v.hint, v.mask, v.spread>;
+	else return nullptr;
+}
+template <int... I>
+static constexpr KernelTable<SweepKernel, sizeof...(I)> sweep_table(std::integer_sequence<int, I...>) { return {{sweep_instance<I>()...}}; }
+static constexpr auto kSweepKernels = sweep_table(std::make_integer_sequence<int, 4 * 64>{});
 
-}
-template <bool HINT, bool MASK, bool SPREAD>
-static void launch_sweep_hint(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, const SweepSync& sync, int iter, int nSweeps, int lag,
-                              int wavesPerRow, int affinity, int segLen, hipStream_t s) {
-	if (bigPatch) { // patches beyond 64 taps: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, true, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, true, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		return;
-	}
-	if constexpr (HINT) { // the one sweep of a run that carries the hint: one or two waves per row
-		if (wavesPerRow >= 2) launch_sweep_nw<2, false, true, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<1, false, true, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		return;
-	}
-	switch (wavesPerRow) {
-	case 1: launch_sweep_nw<1, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 3: launch_sweep_nw<3, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	case 4: // (a launch with view spread has no four-wave instance: three waves compute the same maps)
-		if constexpr (SPREAD) launch_sweep_nw<3, false, HINT, MASK, true>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		else launch_sweep_nw<4, false, HINT, MASK, false>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s);
-		break;
-	default: launch_sweep_nw<2, false, HINT, MASK, SPREAD>(dItems, nItems, maxRows, totalRows, V, sync, iter, nSweeps, lag, affinity, segLen, s); break;
-	}
-}
-// One launch for the sweeps iter .. iter + nSweeps - 1 of every item (tickets, rowsDone and the progress words of the items must be
-// zero).  hint: some item of the batch offers the `restore` variant's extra hypothesis in one of these sweeps (EstConst::hintDepth,
-// hintIter): the instance that knows the hint.  mask: some item has a keep-mask (EstConst::keep): the instance that skips its ignored pixels.
-// spread: some item has view spread to do (EstConst::spread): the instance with the spread rounds.
-template <bool SPREAD>
-static void launch_sweep_spread(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, const SweepSync& sync, int iter,
-                                int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
-	if (mask) {
-		if (hint) launch_sweep_hint<true, true, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-		else launch_sweep_hint<false, true, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	} else if (hint) launch_sweep_hint<true, false, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	else launch_sweep_hint<false, false, SPREAD>(dItems, nItems, maxRows, totalRows, V, bigPatch, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-}
-void launch_sweep(const EstConst* dItems, int nItems, int maxRows, int totalRows, int V, bool bigPatch, bool hint, bool mask, bool spread, const SweepSync& sync, int iter,
-                  int nSweeps, int lag, int wavesPerRow, int affinity, int segLen, hipStream_t s) {
-	if (spread) launch_sweep_spread<true>(dItems, nItems, maxRows, totalRows, V, bigPatch, hint, mask, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
-	else launch_sweep_spread<false>(dItems, nItems, maxRows, totalRows, V, bigPatch, hint, mask, sync, iter, nSweeps, lag, wavesPerRow, affinity, segLen, s);
+bool launch_sweep(const SweepArgs& a, const SweepLaunch& l, hipStream_t s) {
+	const SweepKernel k = sweep_variant_exists(l.v) ? kSweepKernels.at[sweep_variant_index(l.v)] : nullptr;
+	if (!k) return false;
+	// one workgroup per ticket; tickets beyond the resident set are picked up through the ticket counter
+	if (l.grid >= 1) hipLaunchKernelGGL(k, dim3(l.grid), dim3(64 * l.v.nw), 0, s, a.dItems, a.nItems, a.maxRows, a.sync, l.first, l.count, a.lag, a.affinity, l.segLen);
+	return true;
 }
 
 void launch_end_pass(const EstConst& c, int finalPass, float* depth, float* normal, float* conf, hipStream_t s) {

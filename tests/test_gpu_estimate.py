@@ -326,7 +326,7 @@ def test_full_size_schedule_invariance():
     (2 propagations + 6 refinements, fewer where a neighbour is already good), and the result converges to the analytic ground truth."""
     torch = pytest.importorskip("torch")
     import os
-    os.environ["HCMVS_SWEEP_SEGMENT"] = "256"     # (the automatic policy takes stretches for 6 .. 11 images of this size)
+    os.environ["HCMVS_SWEEP_SEGMENT"] = "256"     # (the automatic policy takes stretches for 1 .. 11 images of this size: sweep_plan.h)
     try:
         c = binding.Context(0)
     finally:
