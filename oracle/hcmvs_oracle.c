@@ -3,7 +3,7 @@
  *
  * CPU restatement of the PatchMatch depth-map estimation path of HC-MVS:
  *   DM.cpp:354-381 (visiting order), 386-439 (constants), 442-519 (patch + bilateral weights),
- *   522-616 + 890-893 (ScorePixelImage), 987-1046 (ScorePixel), 1050-1501 (ProcessPixel),
+ *   522-616 + 890-893 (ScorePixelImage), 987-1046 (ScorePixel), 1050-1501 (ProcessPixel), 1504-1608 (view spread, hcmvs_spread.inc),
  *   1671-1738 (InterpolatePixel, InitPlane); DM.h:537-548, 565-574, 618-634;
  *   SD.cpp:581-595 (gradient map), 649-744 (passes), 758-1056 (driver), 783-808 (splat init).
  *
@@ -406,6 +406,9 @@ typedef struct {
 	float smoothBonusDepth, smoothBonusNormal, smoothSigmaDepth, smoothSigmaNormal;
 	float angle1Range, angle2Range;
 	float thConfSmall, thConfBig, thConfRand, thRobust;
+	/* view spread (hcmvs_spread.inc): on for this call; R_ref R_j^T, R_ref (C_j - C_ref), 1 / f of view j */
+	int spread;
+	double spT[HCOR_MAX_VIEWS][9], spt[HCOR_MAX_VIEWS][3], jifx[HCOR_MAX_VIEWS], jify[HCOR_MAX_VIEWS];
 	uint64_t evals;
 } est_ctx;
 
@@ -430,7 +433,12 @@ static void ctx_init(est_ctx* c, const hcor_view* ref, const hcor_view* srcs, in
 		mat3_mul(c->Hl[v], c->Hr, c->A[v]);
 		for (int i = 0; i < 9; ++i) c->Af[v][i] = (float)c->A[v][i];
 		for (int i = 0; i < 3; ++i) c->Hmf[v][i] = (float)c->Hm[v][i];
+		mat3_mul_bt(ref->R, srcs[v].R, c->spT[v]);
+		const double sC[3] = {srcs[v].C[0] - ref->C[0], srcs[v].C[1] - ref->C[1], srcs[v].C[2] - ref->C[2]};
+		for (int i = 0; i < 3; ++i) c->spt[v][i] = ref->R[i * 3] * sC[0] + ref->R[i * 3 + 1] * sC[1] + ref->R[i * 3 + 2] * sC[2];
+		c->jifx[v] = 1.0 / srcs[v].K[0]; c->jify[v] = 1.0 / srcs[v].K[4];
 	}
+	c->spread = p->spread_on && p->spread_maps && p->it_external >= 1;
 	for (int i = 0; i < 9; ++i) c->Hrf[i] = (float)c->Hr[i];
 	c->ifx = 1.0 / ref->K[0]; c->ify = 1.0 / ref->K[4];
 	c->S = device_segments(V);
@@ -976,7 +984,9 @@ static void add_close(const est_ctx* c, pix_state* ps, int nx, int ny, float nd,
 	ps->cX[k][2] = (float)z;
 }
 
-/* DM.cpp:1050-1501 ProcessPixel (DENSE_REFINE_ITER, DENSE_SMOOTHNESS_PLANE) */
+#include "hcmvs_spread.inc" /* spread_block, the one-pixel trace */
+
+/* DM.cpp:1050-1608 ProcessPixel (DENSE_REFINE_ITER, DENSE_SMOOTHNESS_PLANE) */
 static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, float* normalMap, float* confMap) {
 	const hcor_view* ref = c->ref;
 	const int W = ref->width, H = ref->height, hw7 = border_of(&c->p);
@@ -1068,7 +1078,7 @@ static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, f
 				}
 			}
 			if (again) continue;
-			done = 1;
+			done = 1; /* the `return` of DM.cpp:1464 */
 		}
 		break;
 	}
@@ -1097,9 +1107,16 @@ static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, f
 			}
 		}
 	}
+	const int tr = x == g_tr_x && y == g_tr_y;
+	/* view spread, DM.cpp:1504-1608 */
+	if (c->spread) {
+		tr_put(tr, 0, (float)iter, (float)done, conf, 0, 0, 0, 0);
+		if (!done) spread_block(c, &ps, tr, &conf, &depth, normal);
+	}
 	/* restore/libs/MVS/DepthMap.cpp:1527-1549: last sweep of the last outer iteration */
 	if (c->p.hint_depth && c->p.hint_normal && c->p.it_external == c->p.n_external_iters - 1 && iter == c->p.n_estimation_iters - 1 &&
 	    c->p.hint_depth[idx] > 0) {
+		tr_put(tr, 3, (float)iter, (float)ps.nClose, 0, 0, 0, 0, 0);
 		float nn[3] = {c->p.hint_normal[3 * idx], c->p.hint_normal[3 * idx + 1], c->p.hint_normal[3 * idx + 2]};
 		const float nd = interpolate_pixel(c, &ps, x, y, c->p.hint_depth[idx], nn);
 		correct_normal(c->mt, ps.viewDir, nn);
@@ -1110,6 +1127,8 @@ static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, f
 	confMap[idx] = conf; depthMap[idx] = depth;
 	normalMap[3 * idx] = normal[0]; normalMap[3 * idx + 1] = normal[1]; normalMap[3 * idx + 2] = normal[2];
 }
+
+static inline int kept(const hcor_params* p, long i) { return !p->keep || p->keep[i]; } /* the keep-mask, hcmvs_oracle.h */
 
 void hcor_pass_score(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p,
                      float dMin, float dMax, float* depth, float* normal, float* conf, uint64_t* evals) {
@@ -1123,7 +1142,8 @@ void hcor_pass_score(const hcor_view* ref, const hcor_view* srcs, int V, const u
 		ctx_init(&c, ref, srcs, V, gra, p, dMin, dMax);
 #pragma omp for schedule(dynamic, 4)
 		for (int y = 0; y < H; ++y)
-			for (int x = 0; x < W; ++x) score_one(&c, x, y, depth, normal, conf);
+			for (int x = 0; x < W; ++x)
+				if (kept(p, (long)y * W + x)) score_one(&c, x, y, depth, normal, conf);
 		total += c.evals;
 	}
 	if (evals) *evals += total;
@@ -1134,7 +1154,7 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 	const int W = ref->width, H = ref->height;
 	const int rev = (iter % 2) != 0;
 	if (p->order == HCOR_ORDER_ZIGZAG) {
-		/* SD.cpp:677-686 with one thread: coords forward (LT2RB) or reversed (RB2LT), DM.cpp:1054 */
+		/* SD.cpp:677-686 with one thread: coords forward (LT2RB) or reversed (RB2LT), DM.cpp:1054; without the ignored pixels */
 		est_ctx c;
 		ctx_init(&c, ref, srcs, V, gra, p, dMin, dMax);
 		uint16_t* coords = (uint16_t*)malloc(sizeof(uint16_t) * 2 * (size_t)W * H);
@@ -1142,7 +1162,8 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 		const int n = hcor_zigzag_coords(W, H, stride, coords);
 		for (int i = 0; i < n; ++i) {
 			const int k = rev ? n - 1 - i : i;
-			process_pixel(&c, coords[2 * k], coords[2 * k + 1], iter, depth, normal, conf);
+			const int x = coords[2 * k], y = coords[2 * k + 1];
+			if (kept(p, (long)y * W + x)) process_pixel(&c, x, y, iter, depth, normal, conf);
 		}
 		free(coords);
 		if (evals) *evals += c.evals;
@@ -1171,8 +1192,8 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 					}
 				}
 				const int x = rev ? W - 1 - q : q;
-				process_pixel(&c, x, y, iter, depth, normal, conf);
-atomic_store_explicit(&progress[r], q + 1, memory_order_release);
+				if (kept(p, (long)y * W + x)) process_pixel(&c, x, y, iter, depth, normal, conf);
+				atomic_store_explicit(&progress[r], q + 1, memory_order_release); /* an ignored pixel's column still counts as done */
 			}
 		}
 		total += c.evals;
@@ -1184,6 +1205,7 @@ atomic_store_explicit(&progress[r], q + 1, memory_order_release);
 void hcor_pass_end(const hcor_params* p, int W, int H, float* depth, float* normal, float* conf) {
 	/* SD.cpp:688-744 */
 	for (long i = 0; i < (long)W * H; ++i) {
+		if (!kept(p, i)) continue;
 		if (depth[i] <= 0 || conf[i] >= p->ncc_threshold_keep) {
 			conf[i] = 0; normal[3 * i] = normal[3 * i + 1] = normal[3 * i + 2] = 0; depth[i] = 0;
 		} else {
@@ -1198,6 +1220,8 @@ int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int V, const uint
 	if (p->adapthalfwin < 1 || p->adapthalfwin > HCOR_MAX_HALF_WINDOW) return 1;
 	const int W = ref->width, H = ref->height;
 	if (evals) *evals = 0;
+	for (long i = 0; i < (long)W * H; ++i) /* DepthData::ApplyIgnoreMask */
+		if (!kept(p, i)) { depth[i] = 0; normal[3 * i] = normal[3 * i + 1] = normal[3 * i + 2] = 0; conf[i] = 0; }
 	if (p->median_blur) {
 		float* tmp = (float*)malloc(sizeof(float) * (size_t)W * H);
 		hcor_median3(depth, W, H, tmp);

@@ -13,7 +13,7 @@
  *   DM.cpp = MVS/DepthMap.cpp, DM.h = MVS/DepthMap.h, SD.cpp = MVS/SceneDensify.cpp,
  *   Util.inl / Types.h / Types.inl / Random.h = Common/...
  *
- * "Defined subset" (SURVEY.md Appendix A): opticalflow=0, use-semantic=0, viewspread=0, nOptimize=0;
+ * "Defined subset" (SURVEY.md Appendix A): opticalflow=0, use-semantic=0, nOptimize=0;
  * photometric_flow is honoured as the plain (1-pf) scale it amounts to (DM.cpp:892,931).
  */
 #ifndef HCMVS_ORACLE_H
@@ -46,6 +46,14 @@ typedef struct {
 	double K[9], R[9], C[3];
 } hcor_view;
 
+/* view spread: the maps a source view offers, width x height floats (normal: 3 per pixel); depth == NULL: none */
+typedef struct {
+	int width, height;
+	const float* depth;
+	const float* normal;
+	const float* conf;
+} hcor_spread_map;
+
 /* replaces the OPTDENSE globals (DM.cpp:67-143) for this path */
 typedef struct {
 	int adapthalfwin;           /* --n-adapthalfwin (DM.cpp:455-461); reference <= 7, generalised to <= HCOR_MAX_HALF_WINDOW */
@@ -73,6 +81,14 @@ typedef struct {
 	 * tried as one more hypothesis, with a 0.1 bonus, in the last sweep of the last outer iteration; NULL = frame_main behaviour */
 	const float* hint_depth;
 	const float* hint_normal;
+	/* --ignore-mask-label (DM.cpp:233-248, 319-381; SD.cpp:649-744, 776-860): W*H bytes, 1 = estimated, 0 = ignored; NULL = no mask.
+	 * MapMatrix2ZigzagIdx drops the ignored pixels from the visiting order, so no pass writes them: hcor_estimate zeroes their depth,
+	 * normal and conf before the median (DepthData::ApplyIgnoreMask) and they end holding the median's depth, normal 0, conf 0. */
+	const uint8_t* keep;
+	/* --n-viewspread (DM.cpp:1504-1608, hcmvs_spread.inc): one entry per source view, NULL = none.  Active when spread_on, maps are
+	 * given and it_external >= 1.  The maps must not alias depth / normal / conf (a sweep must not read what it writes). */
+	const hcor_spread_map* spread_maps;
+	int spread_on;
 } hcor_params;
 
 void hcor_default_params(hcor_params* p);
@@ -145,7 +161,7 @@ float hcor_interpolate_pixel(const hcor_view* ref, int x, int y, int nx, int ny,
 
 /* SD.cpp:758-1072 EstimateDepthMap for one reference view (defined subset).
  * depth/normal/conf: H*W, H*W*3, H*W in/out.  gra: H*W gradient map (SD.cpp:581-595).
- * Runs: [median blur] -> pass A (SD.cpp:649-675) -> n_estimation_iters sweeps (SD.cpp:677-686,
+ * Runs: [keep-mask applied] -> [median blur] -> pass A (SD.cpp:649-675) -> n_estimation_iters sweeps (SD.cpp:677-686,
  * DM.cpp:1050-1501) -> pass C when it_external == n_external_iters-1 (SD.cpp:688-744).
  * eval_count (optional): receives the number of ScorePixel evaluations performed. */
 int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
@@ -160,6 +176,15 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int n_src, con
                      const hcor_params* p, int iter, float d_min, float d_max, float* depth,
                      float* normal, float* conf, uint64_t* eval_count);
 void hcor_pass_end(const hcor_params* p, int w, int h, float* depth, float* normal, float* conf);
+
+/* view spread (hcmvs_spread.inc).  Counters summed over every call since the last reset: slots scored, slots accepted, slots dropped
+ * by the depth <= 0 rule, candidates outside view j's map. */
+void hcor_spread_stats(uint64_t* scored, uint64_t* accepted, uint64_t* dropped, uint64_t* outside, int reset);
+/* trace of ONE pixel for the known-answer tests (single-threaded runs only): rows of 8 floats, see hcmvs_spread.inc */
+void hcor_spread_trace_pixel(int x, int y);
+int hcor_spread_trace_get(float* out, int cap);
+/* DM.cpp:1590-1592 alone: depth of view src's pixel (nx, ny, nd) seen from ref */
+float hcor_spread_transform_depth(const hcor_view* ref, const hcor_view* src, int nx, int ny, float nd, int mode);
 
 /* ---- filter and fuse (hcmvs_fuse.c) ----------------------------------------------------------- */
 

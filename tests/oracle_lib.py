@@ -17,6 +17,11 @@ class View(C.Structure):
                 ("bgr", C.POINTER(C.c_uint8)), ("K", C.c_double * 9), ("R", C.c_double * 9), ("C", C.c_double * 3)]
 
 
+class SpreadMap(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("depth", C.POINTER(C.c_float)), ("normal", C.POINTER(C.c_float)),
+                ("conf", C.POINTER(C.c_float))]
+
+
 class Params(C.Structure):
     _fields_ = [("adapthalfwin", C.c_int), ("n_estimation_iters", C.c_int), ("it_external", C.c_int),
                 ("n_external_iters", C.c_int), ("propagate_halfwin", C.c_int), ("propagate_step", C.c_int),
@@ -25,7 +30,8 @@ class Params(C.Structure):
                 ("random_smooth_depth", C.c_float), ("random_smooth_normal_deg", C.c_float),
                 ("random_smooth_bonus", C.c_float), ("photometric_flow", C.c_float), ("seed", C.c_uint32),
                 ("arith_mode", C.c_int), ("order", C.c_int), ("n_threads", C.c_int), ("median_blur", C.c_int),
-                ("hint_depth", C.POINTER(C.c_float)), ("hint_normal", C.POINTER(C.c_float))]
+                ("hint_depth", C.POINTER(C.c_float)), ("hint_normal", C.POINTER(C.c_float)),
+                ("keep", C.POINTER(C.c_uint8)), ("spread_maps", C.POINTER(SpreadMap)), ("spread_on", C.c_int)]
 
 
 class DepthMap(C.Structure):
@@ -47,10 +53,8 @@ _lib = None
 
 
 def build():
-    if not os.path.exists(LIB_PATH) or any(
-            os.path.getmtime(os.path.join(ORACLE_DIR, f)) > os.path.getmtime(LIB_PATH)
-            for f in os.listdir(ORACLE_DIR) if f.endswith((".c", ".h"))):
-        subprocess.check_call(["make", "-C", ORACLE_DIR, "libhcmvs_oracle.so"], stdout=subprocess.DEVNULL)
+    """oracle/Makefile knows what the library depends on"""
+    subprocess.check_call(["make", "-C", ORACLE_DIR, "libhcmvs_oracle.so"], stdout=subprocess.DEVNULL)
 
 
 def lib():
@@ -97,6 +101,15 @@ def lib():
         L.hcor_pass_score.argtypes = est_args
         L.hcor_pass_sweep.argtypes = est_args[:5] + [C.c_int] + est_args[5:]
         L.hcor_pass_end.argtypes = [C.POINTER(Params), C.c_int, C.c_int, fp, fp, fp]
+        u64p = C.POINTER(C.c_uint64)
+        L.hcor_spread_stats.argtypes = [u64p, u64p, u64p, u64p, C.c_int]
+        L.hcor_spread_stats.restype = None
+        L.hcor_spread_trace_pixel.argtypes = [C.c_int, C.c_int]
+        L.hcor_spread_trace_pixel.restype = None
+        L.hcor_spread_trace_get.argtypes = [fp, C.c_int]
+        L.hcor_spread_trace_get.restype = C.c_int
+        L.hcor_spread_transform_depth.argtypes = [C.POINTER(View), C.POINTER(View), C.c_int, C.c_int, C.c_float, C.c_int]
+        L.hcor_spread_transform_depth.restype = C.c_float
         L.hcor_filter_depthmap.argtypes = [C.POINTER(DepthMap), C.c_uint32, C.POINTER(C.c_uint32), C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_float, fp, fp, C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint64)]
@@ -189,8 +202,27 @@ def resize_area_up(src, dw, dh):
     return out
 
 
-def estimate(views, params, d_min, d_max, depth, normal, gra=None, passes="all", iter_index=0):
-    """Runs the oracle on views[0] (ref) vs views[1:].  depth (h,w), normal (h,w,3) are copied.
+def make_maps(maps):
+    """maps: one entry per source view, None or (depth (h, w), normal (h, w, 3), conf (h, w)).  Returns the ctypes array (keeps the arrays
+    alive); the size of an entry is the size of its depth map -- a view spreads only when that equals its image size."""
+    arr = (SpreadMap * max(len(maps), 1))()
+    keep = []
+    for i, m in enumerate(maps):
+        if m is None:
+            continue
+        d = np.ascontiguousarray(m[0], np.float32); n = np.ascontiguousarray(m[1], np.float32); c = np.ascontiguousarray(m[2], np.float32)
+        assert n.shape == d.shape + (3,) and c.shape == d.shape
+        arr[i].height, arr[i].width = d.shape
+        arr[i].depth = fptr(d); arr[i].normal = fptr(n); arr[i].conf = fptr(c)
+        keep += [d, n, c]
+    arr._keep = keep
+    return arr
+
+
+def estimate(views, params, d_min, d_max, depth, normal, gra=None, keep=None, maps=None, on=False, conf=None):
+    """Runs the oracle on views[0] (ref) vs views[1:].  depth (h,w), normal (h,w,3) and conf (h,w; None = zeros) are copied.
+    keep: keep-mask (h, w) u8 (1 = estimated, 0 = ignored; None = no mask).  maps: the source views' spread maps as make_maps takes
+    them (None: no view has maps), on = --n-viewspread.  params itself is left as it was.
     Returns depth, normal, conf, evals."""
     L = lib()
     ref = make_view(views[0]); srcs = make_view_array(views[1:])
@@ -199,12 +231,45 @@ def estimate(views, params, d_min, d_max, depth, normal, gra=None, passes="all",
         gra = gradient_map(views[0]["gray"])
     d = np.ascontiguousarray(depth, np.float32).copy()
     n = np.ascontiguousarray(normal, np.float32).copy()
-    c = np.zeros((h, w), np.float32)
+    c = np.zeros((h, w), np.float32) if conf is None else np.ascontiguousarray(conf, np.float32).copy()
+    p = Params.from_buffer_copy(params)
+    assert maps is None or len(maps) == len(views) - 1
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    sm = None if maps is None else make_maps(maps)
+    if k is not None:
+        p.keep = u8ptr(k)
+    if sm is not None:
+        p.spread_maps = sm
+    p.spread_on = int(bool(on))
     ev = C.c_uint64(0)
-    rc = L.hcor_estimate(C.byref(ref), srcs, len(views) - 1, u8ptr(gra), C.byref(params), d_min, d_max, fptr(d),
+    rc = L.hcor_estimate(C.byref(ref), srcs, len(views) - 1, u8ptr(gra), C.byref(p), d_min, d_max, fptr(d),
                          fptr(n), fptr(c), C.byref(ev))
     assert rc == 0
     return d, n, c, ev.value
+
+
+def stats(reset=False):
+    """view spread: (slots scored, slots accepted, slots dropped by the depth <= 0 rule, candidates outside view j's map) since the last reset"""
+    v = [C.c_uint64() for _ in range(4)]
+    lib().hcor_spread_stats(*[C.byref(x) for x in v], int(reset))
+    return tuple(int(x.value) for x in v)
+
+
+def trace(x, y):
+    """view spread: start tracing pixel (x, y) (single-threaded runs only); trace_rows() returns what the runs since then recorded"""
+    lib().hcor_spread_trace_pixel(int(x), int(y))
+
+
+def trace_rows():
+    buf = np.zeros((256, 8), np.float32)
+    n = lib().hcor_spread_trace_get(fptr(buf), 256)
+    return buf[:min(n, 256)].copy()
+
+
+def transform_depth(ref, src, nx, ny, nd, mode=ARITH_REFERENCE):
+    """DepthMap.cpp:1590-1592: the depth of view src's pixel (nx, ny, nd) in ref's camera frame"""
+    r = make_view(ref); s = make_view(src)
+    return float(lib().hcor_spread_transform_depth(C.byref(r), C.byref(s), int(nx), int(ny), C.c_float(nd), int(mode)))
 
 
 def make_depthmaps(maps):

@@ -1,72 +1,10 @@
-"""ctypes binding of the masked estimate of the CPU oracle (tests/oracle_mask.c -> tests/libhcmvs_oracle_mask.so), plus numpy
-restatements of what --ignore-mask-label does before the estimate: the label list (Util::strSplit + atoi) and cv::resize
-INTER_NEAREST of the label image (OpenCV's resizeNN).  Test infrastructure only."""
-import ctypes as C
-import os
+"""numpy restatements of what --ignore-mask-label does before the estimate: the label list (Util::strSplit + atoi), cv::resize
+INTER_NEAREST of the label image (OpenCV's resizeNN) and the keep-mask they give.  The masked estimate itself is the oracle's
+(oracle_lib.estimate(keep=...)).  Test infrastructure only."""
 import re
-import subprocess
 
 import numpy as np
 
-import oracle_lib as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "oracle_mask.c")
-LIB_PATH = os.path.join(HERE, "libhcmvs_oracle_mask.so")
-
-
-def oracle_cflags():
-    """oracle/Makefile's CFLAGS, exactly (-ffp-contract=off -mavx2 -mfma keep the device-association mode bit-reproducible)"""
-    with open(os.path.join(O.ORACLE_DIR, "Makefile")) as f:
-        for line in f:
-            m = re.match(r"\s*CFLAGS\s*=\s*(.*)$", line)
-            if m:
-                return m.group(1).split()
-    raise RuntimeError("oracle/Makefile has no CFLAGS line")
-
-
-def build(force=False):
-    deps = [SRC] + [os.path.join(O.ORACLE_DIR, f) for f in os.listdir(O.ORACLE_DIR) if f.endswith((".c", ".h"))]
-    if force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps):
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", LIB_PATH, SRC, "-lm"])
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        build()
-        L = C.CDLL(LIB_PATH)
-        fp, u8p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(O.View)
-        L.hcor_mask_estimate.argtypes = [vp, vp, C.c_int, u8p, C.POINTER(O.Params), u8p, C.c_float, C.c_float, fp, fp, fp,
-                                         C.POINTER(C.c_uint64)]
-        L.hcor_mask_estimate.restype = C.c_int
-        _lib = L
-    return _lib
-
-
-def estimate(views, params, d_min, d_max, depth, normal, keep=None, gra=None):
-    """oracle_lib.estimate with a keep-mask (h, w) u8 (1 = estimated, 0 = ignored; None = no mask).  Returns depth, normal, conf, evals."""
-    ref = O.make_view(views[0]); srcs = O.make_view_array(views[1:])
-    h, w = views[0]["gray"].shape
-    if gra is None:
-        gra = O.gradient_map(views[0]["gray"])
-    d = np.ascontiguousarray(depth, np.float32).copy()
-    n = np.ascontiguousarray(normal, np.float32).copy()
-    c = np.zeros((h, w), np.float32)
-    k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
-    ev = C.c_uint64(0)
-    rc = lib().hcor_mask_estimate(C.byref(ref), srcs, len(views) - 1, O.u8ptr(gra), C.byref(params), None if k is None else O.u8ptr(k),
-                                  d_min, d_max, O.fptr(d), O.fptr(n), O.fptr(c), C.byref(ev))
-    assert rc == 0
-    return d, n, c, ev.value
-
-
-# ---- what happens before the estimate (numpy restatements) ---------------------------------------------------------------------
 
 def parse_labels(arg):
     """--ignore-mask-label: Util::strSplit(s, ",") keeping empty tokens (libs/Common/Util.h:530-545), each token through atoi

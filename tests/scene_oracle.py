@@ -10,6 +10,14 @@ Two schedules of the post-filters of outer iterations 1 and 2:
   interleave=False  the batch schedule of the device path: every image of the outer iteration is estimated,
                     then the images are filtered one after the other in the same (ascending id) order
 
+With viewspread=True (--n-viewspread) every estimate of outer iteration i >= 1 is offered its source views' maps:
+
+  interleave=False  batch: the maps as outer iteration i - 1 left them, post-filters included (a snapshot taken before the iteration:
+                    Jacobi order)
+  interleave=True   the reference's order: in EVERY outer iteration >= 1 the images are estimated one after the other (ids ascending,
+                    each followed by its post-filter in the filtered iterations) and read the live maps -- images < k as this iteration
+                    left them (after the end pass in the last one), images > k from the previous one
+
 Image ids must be 0 .. n-1.  Seeds follow hc-mvs_amd/distributed.py::densify_scene (params.seed + image id)."""
 import ctypes as C
 
@@ -32,11 +40,11 @@ def gradient_map(view):
 
 
 def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=False, interleave=False, mode=O.ARITH_DEVICE, seed=1234,
-            n_threads=8, fuse=True, pf_kw=None, fuse_kw=None, hints=None, **est_kw):
+            n_threads=8, fuse=True, pf_kw=None, fuse_kw=None, hints=None, viewspread=False, **est_kw):
     """views: {id: dict(gray, K, R, C[, bgr])}; srcs / neighbors: {id: [ids]}; order: fusion order; init: {id: (depth0, normal0, d_min, d_max)};
     hints: optional {id: (hint_depth, hint_normal)} (the `restore` variant's extra hypothesis, last sweep of the last outer iteration);
     est_kw: oracle estimate parameters (adapthalfwin, n_estimation_iters, propagate_halfwin, ...).
-    Returns dict(maps={id: (depth, normal, conf)}, cloud=..., filled=[...], evals=int)."""
+    Returns dict(maps={id: (depth, normal, conf)}, cloud=..., filled=[...], evals=int, spread=(scored, accepted, dropped, outside))."""
     ids = sorted(views)
     assert ids == list(range(len(ids)))
     gra = {i: gradient_map(views[i]) for i in ids}
@@ -47,8 +55,9 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
                       normal=np.ascontiguousarray(n0, np.float32).copy(), conf=np.zeros(d0.shape, np.float32), bgr=views[i].get("bgr"),
                       d_min=float(dmin), d_max=float(dmax), neighbors=[n for n in neighbors[i] if n in views][:31])
     filled, evals = [], 0
+    O.stats(reset=True)
 
-    def estimate(i, it):
+    def estimate(i, it, offered):
         nonlocal evals
         kw = dict(est_kw)
         keep = []
@@ -59,7 +68,10 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
         p = O.default_params(arith_mode=mode, order=O.ORDER_ROWS, n_threads=n_threads, it_external=it, n_external_iters=n_external_iters,
                              seed=(seed + i) & 0xFFFFFFFF, **kw)
         vs = [views[i]] + [views[s] for s in srcs[i]]
-        d, n, c, ev = O.estimate(vs, p, cur[i]["d_min"], cur[i]["d_max"], cur[i]["depth"], cur[i]["normal"], gra=gra[i])
+        maps = None
+        if offered is not None:
+            maps = [(offered[s]["depth"], offered[s]["normal"], offered[s]["conf"]) for s in srcs[i]]
+        d, n, c, ev = O.estimate(vs, p, cur[i]["d_min"], cur[i]["d_max"], cur[i]["depth"], cur[i]["normal"], gra=gra[i], maps=maps, on=viewspread)
         cur[i]["depth"], cur[i]["normal"], cur[i]["conf"] = d, n, c
         evals += ev
 
@@ -72,17 +84,23 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
 
     for it in range(n_external_iters):
         filt = postfilter and it in (1, 2)
-        if filt and interleave:
+        spread = viewspread and it >= 1
+        if (filt or spread) and interleave:
             for i in ids:
-                estimate(i, it)
-                post(i)
+                estimate(i, it, cur if spread else None)  # the live maps (O.estimate works on copies of image i's own)
+                if filt:
+                    post(i)
         else:
+            snap = None
+            if spread:
+                snap = {k: dict(depth=cur[k]["depth"].copy(), normal=cur[k]["normal"].copy(), conf=cur[k]["conf"].copy()) for k in ids}
             for i in ids:
-                estimate(i, it)
+                estimate(i, it, snap)
             if filt:
                 for i in ids:
                     post(i)
-    out = dict(maps={i: (cur[i]["depth"].copy(), cur[i]["normal"].copy(), cur[i]["conf"].copy()) for i in ids}, filled=filled, evals=evals)
+    out = dict(maps={i: (cur[i]["depth"].copy(), cur[i]["normal"].copy(), cur[i]["conf"].copy()) for i in ids}, filled=filled, evals=evals,
+               spread=O.stats())
     if fuse:
         h, w = cur[ids[0]]["depth"].shape
         out["cloud"] = O.fuse_depthmaps([cur[k] for k in ids], list(order), h * w * len(ids) // 2 + 16, **(fuse_kw or {}))

@@ -1,6 +1,6 @@
 """densify_scene(viewspread=True) with two ranks on the CPU (gloo), the oracle standing in for the device context: the per-iteration
 all-gather that gives every rank the previous iteration's maps of its source views (batch schedule) and the live maps of the interleaved
-schedule must give what one process gives, which is what the scene-level harness tests/scene_oracle_spread.py gives."""
+schedule must give what one process gives, which is what the scene-level harness tests/scene_oracle.py gives with viewspread=True."""
 import importlib
 import os
 import socket
@@ -21,7 +21,6 @@ KW = dict(adapthalfwin=5, n_estimation_iters=2, propagate_halfwin=5, propagate_s
 
 
 def _context():
-    import oracle_spread_lib as S
     import scene_oracle as SO
 
     class SpreadOracleContext(SO.OracleContext):
@@ -59,7 +58,7 @@ def _context():
                     assert pd != it["d_depth"], "an estimate must not read what it writes"
                     maps.append((self._arr(pd, sh * sw).reshape(sh, sw).copy(), self._arr(pn, 3 * sh * sw).reshape(sh, sw, 3).copy(),
                                  self._arr(pc, sh * sw).reshape(sh, sw).copy()))
-                dd, nn, cc, _ = S.estimate(vs, po, it["d_min"], it["d_max"], d, n, maps=maps, on=self.spread_on, gra=self.gra[i])
+                dd, nn, cc, _ = O.estimate(vs, po, it["d_min"], it["d_max"], d, n, maps=maps, on=self.spread_on, gra=self.gra[i])
                 d[...] = dd; n[...] = nn; c[...] = cc
 
     return SpreadOracleContext()
@@ -90,7 +89,6 @@ def _scene_worker(rank, world, port, ret, interleave):
 
 def test_densify_scene_viewspread_two_ranks_both_schedules():
     import scene_oracle as SO
-    import scene_oracle_spread as SOS
     clouds = {}
     for interleave in (False, True):
         mgr = mp.Manager()
@@ -105,7 +103,7 @@ def test_densify_scene_viewspread_two_ranks_both_schedules():
             for i in single[0][2]:
                 assert ret[r][2][i] == single[0][2][i]
         views, srcs, neighbors, order, init = SO.ring_scene(n=5, w=96, h=80, f=90.0, n_points=60)
-        want = SOS.densify(views, srcs, neighbors, order, init, n_external_iters=3, postfilter=True, interleave=interleave, seed=900, **KW)
+        want = SO.densify(views, srcs, neighbors, order, init, viewspread=True, n_external_iters=3, postfilter=True, interleave=interleave, seed=900, **KW)
         assert want["spread"][0] > 0
         assert want["cloud"]["n_points"] == single[0][0] and want["cloud"]["xyz"].tobytes() == single[0][1]
         clouds[interleave] = single[0][1]

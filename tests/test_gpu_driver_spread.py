@@ -1,5 +1,5 @@
 """DensifyPointCloud --n-viewspread 1 (files in, files out) against the scene-level oracle harness with view spread
-(tests/scene_oracle_spread.py) in the same schedule, bit for bit: the batch schedule (the maps of the previous outer iteration, copied)
+(tests/scene_oracle.py, viewspread=True) in the same schedule, bit for bit: the batch schedule (the maps of the previous outer iteration, copied)
 and --n-postfilter-interleave 1 (the reference's order on the live maps; with four outer iterations the last one is estimated image
 after image without a filter).  And the combinations the driver refuses or leaves alone."""
 import importlib
@@ -13,7 +13,6 @@ import pytest
 
 import scene_files as SF
 import scene_oracle as SO
-import scene_oracle_spread as SOS
 import test_gpu_schedule as GS
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
@@ -63,7 +62,7 @@ def test_driver_viewspread_matches_the_scene_oracle(tmp_path, interleave, outer)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "not available" not in r.stderr
     oviews, srcs, neighbors, order, init = _oracle_inputs(views, verts)
-    want = SOS.densify(oviews, srcs, neighbors, order, init, n_external_iters=outer, postfilter=True, interleave=bool(interleave), seed=seed, n_threads=16,
+    want = SO.densify(oviews, srcs, neighbors, order, init, viewspread=True, n_external_iters=outer, postfilter=True, interleave=bool(interleave), seed=seed, n_threads=16,
                        adapthalfwin=6, n_estimation_iters=2, propagate_halfwin=5, propagate_step=4, photometric_flow=0.0)
     assert want["spread"][0] > 0 and want["spread"][2] == 0
     plain = SO.densify(oviews, srcs, neighbors, order, init, n_external_iters=outer, postfilter=True, interleave=bool(interleave), seed=seed, n_threads=16, fuse=False,

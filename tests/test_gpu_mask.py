@@ -1,5 +1,5 @@
 """--ignore-mask-label on the GPU: estimates of reference views that carry a keep-mask (hcmvs_set_ignore_mask) against the oracle's
-masked estimate (tests/oracle_mask.c), bit for bit, with equal evaluation counts -- single estimates, batches mixing masked and
+masked estimate (oracle_lib.estimate with a keep-mask), bit for bit, with equal evaluation counts -- single estimates, batches mixing masked and
 unmasked items in every launch mode, the 9..16-view and big-patch kernels, the restore hint, and the device-side resampling of a
 label image of another size."""
 import ctypes as C
@@ -69,7 +69,7 @@ def _upload(ctx, views, base):
 
 
 def _want(views, po, dmin, dmax, d0, n0, keep):
-    return M.estimate(views, po, dmin, dmax, d0, n0, keep=keep)
+    return O.estimate(views, po, dmin, dmax, d0, n0, keep=keep)
 
 
 def _params(**kw):

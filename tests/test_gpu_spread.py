@@ -1,5 +1,5 @@
 """View spread (--n-viewspread, DepthMap.cpp:1504-1608) on the GPU: estimates whose source views offer maps of their own
-(hcmvs_set_spread_maps_device + hcmvs_set_viewspread) against the oracle extension tests/oracle_spread.c in device association, bit for
+(hcmvs_set_spread_maps_device + hcmvs_set_viewspread) against the oracle's estimate with spread maps (oracle/hcmvs_spread.inc) in device association, bit for
 bit -- depth, normal, conf, the evaluation count and the four spread counters.  The dropped-slot counter is 0 in every scene but the
 one built to have such slots (checked on the oracle's side of every comparison)."""
 import ctypes as C
@@ -9,9 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-import oracle_spread_lib as S
 import scene_oracle as SO
-import scene_oracle_spread as SOS
 
 pytestmark = pytest.mark.gpu
 
@@ -102,12 +100,12 @@ def run(ctx, cases, pg, po, base=0, on=True, expect_dropped=False, spread_oracle
         po.hint_depth = None; po.hint_normal = None
         if cs.get("hint") is not None:
             po.hint_depth = O.fptr(cs["hint"][0]); po.hint_normal = O.fptr(cs["hint"][1])
-        S.stats(reset=True)
+        O.stats(reset=True)
         if spread_oracle:
-            wants.append(S.estimate(views, po, cs["dmin"], cs["dmax"], cs["d"], cs["n"], maps=cs["maps"], on=on, keep=keep))
+            wants.append(O.estimate(views, po, cs["dmin"], cs["dmax"], cs["d"], cs["n"], maps=cs["maps"], on=on, keep=keep))
         else:
             wants.append(O.estimate(views, po, cs["dmin"], cs["dmax"], cs["d"], cs["n"]))
-        tot += np.array(S.stats(), np.int64)
+        tot += np.array(O.stats(), np.int64)
         td = torch.from_numpy(cs["d"]).to(dev); tn = torch.from_numpy(cs["n"]).to(dev); tc = torch.zeros_like(td)
         it = dict(ref_id=ids[0], src_ids=ids[1:], d_min=cs["dmin"], d_max=cs["dmax"], d_depth=td.data_ptr(), d_normal=tn.data_ptr(), d_conf=tc.data_ptr(),
                   seed_offset=7 * k)
@@ -388,11 +386,11 @@ def test_spread_pulls_a_poor_map_towards_its_source_views():
 @pytest.mark.parametrize("interleave", [False, True], ids=["batch", "interleaved"])
 @pytest.mark.parametrize("postfilter", [False, True], ids=["plain", "postfilter"])
 def test_densify_scene_with_viewspread_matches_the_scene_oracle(interleave, postfilter):
-    """densify_scene(viewspread=True) over three outer iterations on one context, in both schedules, against tests/scene_oracle_spread.py"""
+    """densify_scene(viewspread=True) over three outer iterations on one context, in both schedules, against tests/scene_oracle.py"""
     import torch
     views, srcs, neighbors, order, init = SO.ring_scene(n=5, w=128, h=96, f=120.0, n_points=80)
     kw = dict(adapthalfwin=6, n_estimation_iters=2, propagate_halfwin=5, propagate_step=4)
-    want = SOS.densify(views, srcs, neighbors, order, init, n_external_iters=3, postfilter=postfilter, interleave=interleave, seed=900, fuse=False, **kw)
+    want = SO.densify(views, srcs, neighbors, order, init, viewspread=True, n_external_iters=3, postfilter=postfilter, interleave=interleave, seed=900, fuse=False, **kw)
     assert want["spread"][0] > 0 and want["spread"][2] == 0
     ctx = binding.Context(0)
     try:

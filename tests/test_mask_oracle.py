@@ -1,5 +1,5 @@
 """--ignore-mask-label on the CPU: the label parse and resizeNN restatements against hand-worked cases, and the oracle's masked estimate
-(tests/oracle_mask.c) against hcor_estimate and against itself in both visiting orders."""
+(hcor_params.keep) against the unmasked one and against itself in both visiting orders."""
 import importlib
 import os
 import sys
@@ -112,7 +112,7 @@ def test_mask_keeping_everything_is_the_unmasked_estimate(order):
     h, w = d0.shape
     ref = O.estimate(views, p, dmin, dmax, d0, n0)
     for keep in (None, np.ones((h, w), np.uint8), M.keep_mask(np.full((h // 2, w // 3), 4, np.uint16), [3, 5, -1], w, h)):
-        got = M.estimate(views, p, dmin, dmax, d0, n0, keep=keep)
+        got = O.estimate(views, p, dmin, dmax, d0, n0, keep=keep)
         for a, b in zip(ref, got):
             assert np.array_equal(a, b)
 
@@ -124,8 +124,8 @@ def test_zigzag_equals_rows_under_masks():
     for keep in (_blobs(h, w), line):
         pz = O.default_params(adapthalfwin=5, n_estimation_iters=2, arith_mode=O.ARITH_DEVICE, order=O.ORDER_ZIGZAG)
         pr = O.default_params(adapthalfwin=5, n_estimation_iters=2, arith_mode=O.ARITH_DEVICE, order=O.ORDER_ROWS, n_threads=4)
-        a = M.estimate(views, pz, dmin, dmax, d0, n0, keep=keep)
-        b = M.estimate(views, pr, dmin, dmax, d0, n0, keep=keep)
+        a = O.estimate(views, pz, dmin, dmax, d0, n0, keep=keep)
+        b = O.estimate(views, pr, dmin, dmax, d0, n0, keep=keep)
         for x, y in zip(a, b):
             assert np.array_equal(x, y)
         assert 0 < a[3] < O.estimate(views, pz, dmin, dmax, d0, n0)[3]  # masked pixels cost no evaluation
@@ -139,7 +139,7 @@ def test_ignored_pixels_hold_applied_then_median(last):
     d0 = np.where(d0 > 0, d0, np.float32(0.5 * (dmin + dmax))).astype(np.float32)
     keep = _blobs(h, w, seed=3); keep[:, 20] = 0; keep[: 3, :] = 0
     p.it_external = 0; p.n_external_iters = 1 if last else 2
-    d, n, c, ev = M.estimate(views, p, dmin, dmax, d0, n0, keep=keep)
+    d, n, c, ev = O.estimate(views, p, dmin, dmax, d0, n0, keep=keep)
     applied = np.where(keep != 0, d0, 0).astype(np.float32)
     med = np.empty_like(applied)
     O.lib().hcor_median3(O.fptr(applied), w, h, O.fptr(med))

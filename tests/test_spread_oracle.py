@@ -1,4 +1,4 @@
-"""View spread (--n-viewspread, DepthMap.cpp:1504-1608) on the CPU: the oracle extension tests/oracle_spread.c against hcor_estimate, against
+"""View spread (--n-viewspread, DepthMap.cpp:1504-1608) on the CPU: the oracle's estimate with spread maps (oracle/hcmvs_spread.inc) against the plain one, against
 itself in both visiting orders, against hand-derived known answers, its two arithmetic modes against each other (the bridge), the two
 schedules of the scene-level harness against each other, and the three entry points of the C-ABI (exported and bound)."""
 import ctypes as C
@@ -13,9 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oracle_lib as O  # noqa: E402
-import oracle_spread_lib as S  # noqa: E402
 import scene_oracle as SO  # noqa: E402
-import scene_oracle_spread as SOS  # noqa: E402
 import test_oracle_bridge as BR  # noqa: E402
 import test_oracle_schedule as SCH  # noqa: E402
 
@@ -51,16 +49,16 @@ def test_spread_off_or_without_maps_is_hcor_estimate(mode, order, threads):
     d, n, dmin, dmax = prepared(views, mode, **kw)
     p = O.default_params(arith_mode=mode, order=order, n_threads=threads, it_external=1, n_external_iters=3, **kw)
     want = O.estimate(views, p, dmin, dmax, d, n)
-    assert same(S.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=False), want)    # switched off, maps there
-    assert same(S.estimate(views, p, dmin, dmax, d, n, maps=None, on=True), want)               # switched on, no maps
-    assert same(S.estimate(views, p, dmin, dmax, d, n, maps=[None] * 3, on=True), want)
+    assert same(O.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=False), want)    # switched off, maps there
+    assert same(O.estimate(views, p, dmin, dmax, d, n, maps=None, on=True), want)               # switched on, no maps
+    assert same(O.estimate(views, p, dmin, dmax, d, n, maps=[None] * 3, on=True), want)
     small = [(m[0][:-2], m[1][:-2], m[2][:-2]) for m in gt_maps(views)]                         # maps of another size: the view does not spread
-    assert same(S.estimate(views, p, dmin, dmax, d, n, maps=small, on=True), want)
+    assert same(O.estimate(views, p, dmin, dmax, d, n, maps=small, on=True), want)
     p0 = O.default_params(arith_mode=mode, order=order, n_threads=threads, it_external=0, n_external_iters=3, **kw)   # outer iteration 0
     pts = synth.sparse_points(views, 80)
     d0, n0, lo, hi = SO.splat(views[0], pts)
-    assert same(S.estimate(views, p0, lo, hi, d0, n0, maps=gt_maps(views), on=True), O.estimate(views, p0, lo, hi, d0, n0))
-    assert not same(S.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=True), want)  # and with everything there it does something
+    assert same(O.estimate(views, p0, lo, hi, d0, n0, maps=gt_maps(views), on=True), O.estimate(views, p0, lo, hi, d0, n0))
+    assert not same(O.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=True), want)  # and with everything there it does something
 
 
 @pytest.mark.parametrize("mode", [O.ARITH_REFERENCE, O.ARITH_DEVICE])
@@ -73,8 +71,8 @@ def test_zigzag_equals_rows_with_spread(mode):
     res = []
     for order, threads in [(O.ORDER_ZIGZAG, 1), (O.ORDER_ROWS, 1), (O.ORDER_ROWS, 3), (O.ORDER_ROWS, 8)]:
         p = O.default_params(arith_mode=mode, order=order, n_threads=threads, it_external=1, n_external_iters=3, **kw)
-        S.stats(reset=True)
-        res.append(S.estimate(views, p, dmin, dmax, d, n, maps=maps, on=True) + (S.stats(),))
+        O.stats(reset=True)
+        res.append(O.estimate(views, p, dmin, dmax, d, n, maps=maps, on=True) + (O.stats(),))
     assert res[0][4][0] > 0 and res[0][4][1] > 0    # slots were scored and some accepted
     for r in res[1:]:
         assert same(r, res[0]) and r[4] == res[0][4]
@@ -115,11 +113,11 @@ def run_traced(views, x, y, mode, wrong=12.0, maps=None, on=True, hint=None, it=
         kw = dict(hint_depth=O.fptr(hint[0]), hint_normal=O.fptr(hint[1]))
     p = O.default_params(adapthalfwin=a, n_estimation_iters=1, arith_mode=mode, order=O.ORDER_ZIGZAG, n_threads=1, it_external=it, n_external_iters=n_ext,
                          median_blur=0, **kw)
-    S.trace(x, y); S.stats(reset=True)
-    d, n, c, ev = S.estimate(views, p, 5.0, 40.0, d0, n0, maps=maps, on=on)
-    tr = S.trace_rows()
-    S.trace(-1, -1)
-    return d, n, c, tr, S.stats()
+    O.trace(x, y); O.stats(reset=True)
+    d, n, c, ev = O.estimate(views, p, 5.0, 40.0, d0, n0, maps=maps, on=on)
+    tr = O.trace_rows()
+    O.trace(-1, -1)
+    return d, n, c, tr, O.stats()
 
 
 MODES = [O.ARITH_REFERENCE, O.ARITH_DEVICE]
@@ -131,11 +129,11 @@ def test_transformed_depth_is_the_analytic_one(mode):
     give 10, up to the float32 roundings of the stored depth and of the cast(s) (2^-23 * 10 = 1.2e-6 each; a handful of them)"""
     views = plane_scene()
     for nx, ny in [(9, 8), (40, 40), (88, 70), (0, 0)]:
-        z = S.transform_depth(views[0], views[1], nx, ny, float(views[1]["depth"][ny, nx]), mode)
+        z = O.transform_depth(views[0], views[1], nx, ny, float(views[1]["depth"][ny, nx]), mode)
         assert abs(z - 10.0) < 2e-5, (nx, ny, z)
     # and for a pure translation along the axis by hand: a point at depth 7 of a camera 2 units behind the reference is at depth 5
     back = dict(views[0]); back["C"] = np.array([0., 0., 2.])
-    assert S.transform_depth(back, views[0], 30, 20, 7.0, mode) == 5.0
+    assert O.transform_depth(back, views[0], 30, 20, 7.0, mode) == 5.0
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -237,9 +235,9 @@ def test_candidates_outside_a_smaller_source_map_are_counted_not_read():
     vs = [views[0], views[1], small]     # (a pixel that leaves the small view is still scored through the full-size one, so it reaches the block)
     d, n, dmin, dmax = prepared(vs, O.ARITH_DEVICE, adapthalfwin=5, n_estimation_iters=1)
     p = O.default_params(arith_mode=O.ARITH_DEVICE, order=O.ORDER_ROWS, n_threads=4, it_external=1, n_external_iters=3, adapthalfwin=5, n_estimation_iters=1)
-    S.stats(reset=True)
-    S.estimate(vs, p, dmin, dmax, d, n, maps=gt_maps(vs), on=True)
-    st = S.stats()
+    O.stats(reset=True)
+    O.estimate(vs, p, dmin, dmax, d, n, maps=gt_maps(vs), on=True)
+    st = O.stats()
     print("ragged: scored %d accepted %d dropped %d outside %d" % st)
     assert st[3] > 0 and st[0] > 0
 
@@ -256,7 +254,7 @@ BRIDGE = [
 
 @pytest.mark.parametrize("sc", BRIDGE, ids=[s["name"] for s in BRIDGE])
 def test_bridge_reference_and_device_arithmetic_agree_with_spread(sc):
-    """oracle_spread in both arithmetic modes through outer iterations 0 .. it (spread from 1 on, the source views offering their analytic
+    """the estimate with view spread in both arithmetic modes through outer iterations 0 .. it (spread from 1 on, the source views offering their analytic
     maps), held to the rows of tests/test_oracle_bridge.py::TOL (BASELINE.md section 3) for whole estimates"""
     views = synth.make_views(128, 96, 110.0, sc["n_src"], seed=sc["seed"])
     pts = synth.sparse_points(views, 150)
@@ -266,9 +264,9 @@ def test_bridge_reference_and_device_arithmetic_agree_with_spread(sc):
         d, n = d0, n0
         for it in range(sc["it"] + 1):
             p = O.default_params(arith_mode=mode, order=O.ORDER_ROWS, n_threads=8, it_external=it, n_external_iters=sc["it"] + 1, **sc["kw"])
-            S.stats(reset=True)
-            d, n, c, ev = S.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=True)
-        assert S.stats()[0] > 0
+            O.stats(reset=True)
+            d, n, c, ev = O.estimate(views, p, dmin, dmax, d, n, maps=gt_maps(views), on=True)
+        assert O.stats()[0] > 0
         out.append((d, n, c))
     m = BR.compare(out[0], out[1], views[0]["depth"], views[0]["normal"])
     print("spread bridge %-20s" % sc["name"], {k: round(x, 4) for k, x in m.items()})
@@ -288,8 +286,8 @@ def test_batch_and_interleaved_schedules_agree_within_tolerance_with_spread(case
     row is in BASELINE.md section 3."""
     views, srcs, neighbors, order, init = SO.ring_scene(**case["scene"])
     kw = dict(n_external_iters=3, postfilter=True, mode=case["mode"], seed=900, adapthalfwin=6, n_estimation_iters=2, propagate_halfwin=5, propagate_step=4)
-    batch = SOS.densify(views, srcs, neighbors, order, init, interleave=False, **kw)
-    inter = SOS.densify(views, srcs, neighbors, order, init, interleave=True, **kw)
+    batch = SO.densify(views, srcs, neighbors, order, init, viewspread=True, interleave=False, **kw)
+    inter = SO.densify(views, srcs, neighbors, order, init, viewspread=True, interleave=True, **kw)
     m = SCH.compare(inter, batch, views)
     print("spread schedule (interleaved = a, batch = b):", {k: round(v, 4) if isinstance(v, float) else v for k, v in m.items()},
           "filled:", sum(inter["filled"]), sum(batch["filled"]), "spread:", inter["spread"], batch["spread"])
@@ -304,7 +302,7 @@ def test_scene_harness_without_spread_is_the_plain_harness():
     views, srcs, neighbors, order, init = SO.ring_scene(n=4, w=96, h=80, f=90.0, n_src=2, n_points=60)
     kw = dict(n_external_iters=2, postfilter=True, seed=5, adapthalfwin=5, n_estimation_iters=1, propagate_halfwin=5, propagate_step=4)
     a = SO.densify(views, srcs, neighbors, order, init, **kw)
-    b = SOS.densify(views, srcs, neighbors, order, init, viewspread=False, **kw)
+    b = SO.densify(views, srcs, neighbors, order, init, viewspread=False, **kw)
     assert all(np.array_equal(x, y) for i in a["maps"] for x, y in zip(a["maps"][i], b["maps"][i])) and a["evals"] == b["evals"]
 
 
