@@ -52,6 +52,12 @@ class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
 
+class FilterStats(C.Structure):
+    _fields_ = [("n_processed", C.c_uint64), ("n_discarded", C.c_uint64), ("n_filtered", C.c_uint32), ("n_skipped", C.c_uint32),
+                ("batch", C.c_uint32), ("ms_device", C.c_float), ("device_bytes", C.c_uint64), ("image_processed", C.POINTER(C.c_uint64)),
+                ("image_discarded", C.POINTER(C.c_uint64))]
+
+
 class HcmvsError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("hcmvs error %d: %s" % (code, msg))
@@ -66,7 +72,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_get_view_gray",
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
-           "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
+           "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_filter_sequence", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
            "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
@@ -150,6 +156,7 @@ def lib():
         L.hcmvs_set_fuse_order.argtypes = [vp, C.c_int32]
         L.hcmvs_filter.argtypes = [vp, C.c_uint32, u32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, fp, fp,
                                    u64p, u64p]
+        L.hcmvs_filter_sequence.argtypes = [vp, u32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(FilterStats)]
         L.hcmvs_fuse.argtypes = [vp, u32p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64,
                                  fp, fp, u8p, u32p, u64p, u64p]
         L.hcmvs_fuse_cloud.argtypes = [vp, u32p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Cloud)]
@@ -392,6 +399,22 @@ class Context:
         self._chk(lib().hcmvs_filter(self._h, ref_id, ids, len(neighbor_ids), int(adjust), n_min_views, n_min_views_adjust,
                                      depth_diff_threshold, _f(d), _f(c), C.byref(npr), C.byref(nd)))
         return d, c, npr.value, nd.value
+
+    def filter_sequence(self, ids, max_neighbors=8, adjust=True, n_min_views=2, n_min_views_adjust=1, depth_diff_threshold=0.01):
+        """The filter stage (Scene::DenseReconstructionFilter, SceneDensify.cpp:4100-4185): every image of ids that has registered maps is
+        filtered against the first max_neighbors entries of its neighbour list that have maps, all from the maps as they stand now; depth
+        and confidence are then updated in place (get_depthmap reads them back).  Returns dict(n_processed, n_discarded, n_filtered,
+        n_skipped, batch, ms_device, device_bytes, image_processed, image_discarded): the last two per entry of ids (0 for a skipped image)"""
+        ids = [int(i) for i in ids]
+        arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+        per = np.zeros((2, max(len(ids), 1)), np.uint64)
+        st = FilterStats()
+        st.image_processed = per[0].ctypes.data_as(C.POINTER(C.c_uint64)); st.image_discarded = per[1].ctypes.data_as(C.POINTER(C.c_uint64))
+        self._chk(lib().hcmvs_filter_sequence(self._h, arr, len(ids), int(max_neighbors), int(bool(adjust)), int(n_min_views), int(n_min_views_adjust),
+                                              C.c_float(depth_diff_threshold), C.byref(st)))
+        out = {k: getattr(st, k) for k, _ in FilterStats._fields_[:7]}
+        out["image_processed"] = [int(x) for x in per[0][:len(ids)]]; out["image_discarded"] = [int(x) for x in per[1][:len(ids)]]
+        return out
 
     def fuse(self, order, capacity, n_min_views_fuse=2, depth_diff_threshold=0.01, normal_diff_deg=25.0, depthweight=1.0,
              normalweight=1.0, with_normals=True, with_colors=True):

@@ -30,6 +30,25 @@ void launch_fill_u64(unsigned long long* p, unsigned long long v, size_t n, hipS
 void launch_filter_splat(const DevMap& ref, const DevMap& nb, unsigned long long* key, hipStream_t s);
 void launch_filter_vote(const DevMap& ref, const DevMap* nbs, int N, const unsigned long long* keys, int adjust, int nMinViews,
                         int nMinViewsAdjust, float thr, float* newDepth, float* newConf, unsigned long long* counters, hipStream_t s);
+// ---- the scene-level filter stage (hcmvs_filter_sequence, filter_kernels.hip) ----
+// one reference image of the stage, as the batched kernels see it
+struct FilterRef {
+	DevMap map;                  // the image's registered maps: read by the splat (as a neighbour's copy) and the vote, written by the commit only
+	const DevMap* nbs;           // its nNbs neighbours (device copies), in the order of its neighbour list
+	int32_t nNbs;
+	unsigned long long* keys;    // z-buffer planes of its batch: nNbs x (w*h)
+	float *newDepth, *newConf;   // staging slabs (w*h each): the filtered maps until the commit
+	unsigned long long* counters; // [0] processed, [1] discarded depths of this image
+};
+struct FilterPair { int32_t ref, nb; }; // a (reference, neighbour) pair of a batch: index into the FilterRef table, index into that image's nbs
+int filter_blocks(size_t pixels);       // workgroups a pair of the splat / an image of the vote gets
+// pairFirst[0 .. nPairs]: first workgroup of every pair, pairFirst[nPairs] == nBlocks; the same for refFirst over the batch's images
+// (refs points at the batch's first image)
+void launch_filter_splat_batch(const FilterRef* refs, const FilterPair* pairs, const int* pairFirst, int nPairs, int nBlocks, hipStream_t s);
+void launch_filter_vote_batch(const FilterRef* refs, const int* refFirst, int nRefs, int nBlocks, int adjust, int nMinViews, int nMinViewsAdjust, float thr,
+                              hipStream_t s);
+void launch_filter_commit(const FilterRef* refs, int nRefs, hipStream_t s);
+
 // per-pass tables of image A (sized for the largest image / neighbour count of the call)
 struct FuseTables {
 	int32_t* targets;    // [w*h][nNeighbors]: pixel index A's pixel projects onto in neighbour q (SceneDensify.cpp:3387-3393) + what it can do there

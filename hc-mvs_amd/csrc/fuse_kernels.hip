@@ -29,6 +29,7 @@
  */
 #include "fuse_common.h"
 #include "fuse_device.h"
+#include "filter_device.h"
 #include "pm_math.h"
 
 #include <cstdlib>
@@ -45,112 +46,22 @@ static const dim3 kGrid(2048), kBlock(256);
 
 __global__ void filter_splat_kernel(DevMap ref, DevMap nb, unsigned long long* key) {
 	const int n = nb.w * nb.h;
-	for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-		const float depth = nb.depth[s];
-		if (depth == 0.f) continue;
-		const int j = s % nb.w, i = s / nb.w;
-		double X[3], c[3];
-		i2w(nb, (double)j, (double)i, (double)depth, X);
-		w2c(ref, X, c);
-		if (c[2] <= 0) continue;
-		const double ix = ref.K[2] + ref.K[0] * (c[0] / c[2]), iy = ref.K[5] + ref.K[4] * (c[1] / c[2]);
-		const int fx = (int)floor(ix), fy = (int)floor(iy), cx = (int)ceil(ix), cy = (int)ceil(iy);
-		const int xs[4] = {fx, fx, cx, cx}, ys[4] = {fy, cy, fy, cy};
-		const float z = (float)c[2];
-#pragma unroll
-		for (int p = 0; p < 4; ++p) {
-			if (xs[p] < 0 || ys[p] < 0 || xs[p] >= ref.w || ys[p] >= ref.h) continue;
-			// nearest depth wins; among equal depths the later (source raster, footprint) writer wins
-			const unsigned long long k = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(0xFFFFFFFFu - ((unsigned)s * 4u + (unsigned)p));
-			atomicMin(&key[(size_t)ys[p] * ref.w + xs[p]], k);
-		}
-	}
-}
-
-__device__ __forceinline__ float key_depth(unsigned long long k) { return k == ~0ull ? 0.f : __uint_as_float((unsigned)(k >> 32)); }
-__device__ __forceinline__ float key_conf(unsigned long long k, const float* conf) {
-	return k == ~0ull ? 0.f : conf[(0xFFFFFFFFu - (unsigned)k) >> 2];
+	for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) filter_splat_pixel(ref, nb, key, s);
 }
 
 __global__ void filter_vote_kernel(DevMap ref, const DevMap* nbs, int N, const unsigned long long* keys, int adjust, int nMinViews,
                                    int nMinViewsAdjust, float fDepthDiffThreshold, float* newDepth, float* newConf,
                                    unsigned long long* counters) {
-	const int W = ref.w, H = ref.h;
-	const size_t area = (size_t)W * H;
-	const float thDepthDiff = fDepthDiffThreshold * 1.2f;
+	const int area = ref.w * ref.h;
 	unsigned nProc = 0, nDisc = 0;
-	for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < W * H; idx += gridDim.x * blockDim.x) {
-		const int j = idx % W, i = idx / W;
+	for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < area; idx += gridDim.x * blockDim.x) {
 		const float depth = ref.depth[idx];
-		if (depth == 0.f) { newDepth[idx] = 0.f; newConf[idx] = 0.f; continue; }
-		++nProc;
-		if (adjust) { // SceneDensify.cpp:3097-3170
-			float posConf = ref.conf[idx], negConf = 0.f;
-			float avgDepth = depth * posConf;
-			unsigned nPos = 0, nNeg = 0;
-			int n = N;
-			bool discard = false;
-			do {
-				--n;
-				const unsigned long long k = keys[area * n + idx];
-				const float d = key_depth(k);
-				if (d == 0.f) {
-					if (nPos + nNeg + (unsigned)n < (unsigned)nMinViews) { discard = true; break; }
-					continue;
-				}
-				const float cproj = key_conf(k, nbs[n].conf);
-				if (is_depth_similar(depth, d, 0.12f)) {
-					avgDepth += d * cproj;
-					posConf += cproj;
-					++nPos;
-				} else {
-					if (depth > d) {
-						negConf += cproj;
-					} else {
-						const DevMap& nb = nbs[n];
-						double X[3], c[3];
-						i2w(ref, (double)j, (double)i, (double)depth, X);
-						w2c(nb, X, c);
-						const int x = (int)floor(nb.K[2] + nb.K[0] * (c[0] / c[2]) + .5);
-						const int y = (int)floor(nb.K[5] + nb.K[4] * (c[1] / c[2]) + .5);
-						if (x >= 0 && y >= 0 && x < nb.w && y < nb.h) {
-							const float cc = nb.conf[(size_t)y * nb.w + x];
-							negConf += (cc > 0.f ? cc : cproj);
-						} else
-							negConf += cproj;
-					}
-					++nNeg;
-				}
-			} while (n);
-			bool keep = false;
-			if (!discard && nPos >= (unsigned)nMinViewsAdjust && posConf > negConf) {
-				avgDepth /= posConf;
-				if (ref.dMin <= avgDepth && avgDepth < ref.dMax) { newDepth[idx] = avgDepth; newConf[idx] = posConf - negConf; keep = true; }
-			}
-			if (!keep) { newDepth[idx] = 0.f; newConf[idx] = 0.f; ++nDisc; }
-		} else { // SceneDensify.cpp:3171-3249
-			const float thStrict = fDepthDiffThreshold * 0.8f;
-			const unsigned nMinViewsDelta = (unsigned)nMinViews * 2u;
-			unsigned good = 0, views = 0;
-			for (int n = N; n-- > 0;) {
-				const float d = key_depth(keys[area * n + idx]);
-				if (d > 0.f) { ++views; if (is_depth_similar(depth, d, thStrict)) ++good; }
-			}
-			if (good < (unsigned)nMinViews || good < views * 75u / 100u) { newDepth[idx] = 0.f; newConf[idx] = 0.f; ++nDisc; continue; }
-			good = views = 0;
-			const int dx[4] = {-1, 1, 0, 0}, dy[4] = {0, 0, -1, 1};
-#pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int xx = j + dx[q], yy = i + dy[q];
-				if (xx < 0 || yy < 0 || xx >= W || yy >= H) continue;
-				for (int n = N; n-- > 0;) {
-					const float d = key_depth(keys[area * n + (size_t)yy * W + xx]);
-					if (d > 0.f) { ++views; if (is_depth_similar(depth, d, thDepthDiff)) ++good; }
-				}
-			}
-			if (good < nMinViewsDelta || good < views * 65u / 100u) { newDepth[idx] = 0.f; newConf[idx] = 0.f; ++nDisc; continue; }
-			newDepth[idx] = depth; newConf[idx] = ref.conf[idx];
+		float d = 0.f, c = 0.f;
+		if (depth != 0.f) {
+			++nProc;
+			if (!filter_vote_pixel(ref, nbs, N, keys, idx, depth, adjust, nMinViews, nMinViewsAdjust, fDepthDiffThreshold, d, c)) ++nDisc;
 		}
+		newDepth[idx] = d; newConf[idx] = c;
 	}
 	if (nProc) atomicAdd(&counters[0], (unsigned long long)nProc);
 	if (nDisc) atomicAdd(&counters[1], (unsigned long long)nDisc);

@@ -10,6 +10,7 @@
 #include "pm_common.h"
 #include "fuse_common.h"
 #include "pf_chain.h"
+#include "filter_plan.h"
 #include "tri_init.h"
 #include "cloud_kernels.h"
 #include "vis_kernels.h"
@@ -98,6 +99,7 @@ struct hcmvs_ctx final : Reclaimer {
 	DevBuf dMaps{this};       // DevMap per view id
 	DevBuf counters{this};    // unsigned long long [8]
 	DevBuf fuseScratch{this};
+	DevBuf filterStage{this}, filterTab{this}, filterCnt{this}; // hcmvs_filter_sequence: staging slabs, tables, per-image counters (its keys: fuseScratch)
 	DevBuf passScratch{this}; // per-pass tables of the fusion (hcmvs_fuse_cloud, hcmvs_postfilter_sequence)
 	DevBuf pfState;           // the post-filter chain's state kept from fusion to fusion (pf_kernels.hip); never reserved with the reclaimer
 	bool errPending = false; // an estimate was enqueued since the error word was last read
@@ -1044,6 +1046,144 @@ int hcmvs_filter(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* nbr, int32_t N, 
 	HIPCHK(c, hipStreamSynchronize(s));
 	if (n_processed) *n_processed = cnt[0];
 	if (n_discarded) *n_discarded = cnt[1];
+	return HCMVS_OK;
+}
+
+// Scene::DenseReconstructionFilter (SceneDensify.cpp:4100-4185): the filter stage over the registered maps, batched
+int hcmvs_filter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, int32_t max_neighbors, int32_t adjust, int32_t n_min_views,
+                          int32_t n_min_views_adjust, float depth_diff_threshold, hcmvs_filter_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (n_ids < 0 || (n_ids > 0 && !ids) || max_neighbors < 1 || max_neighbors > 64) return fail(c, HCMVS_ERR_INVALID, "filter_sequence: bad arguments");
+	uint64_t* const imgProc = stats ? stats->image_processed : nullptr;
+	uint64_t* const imgDisc = stats ? stats->image_discarded : nullptr;
+	if (stats) { memset(stats, 0, sizeof *stats); stats->image_processed = imgProc; stats->image_discarded = imgDisc; }
+	for (int i = 0; i < n_ids; ++i) { if (imgProc) imgProc[i] = 0; if (imgDisc) imgDisc[i] = 0; }
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	std::vector<DevMap> host;
+	int rc = build_map_table(c, host);
+	if (rc) return rc;
+	// the images to filter and their neighbours: the first max_neighbors of the list that have maps (SceneDensify.cpp:4116-4131)
+	struct Item { int pos; uint32_t id; std::vector<uint32_t> nbs; size_t area; };
+	std::vector<Item> items;
+	size_t stagePx = 0, nNbAll = 0;
+	for (int i = 0; i < n_ids; ++i) {
+		if (ids[i] >= host.size() || !host[ids[i]].depth) continue; // :4110-4113
+		Item it{i, ids[i], {}, (size_t)host[ids[i]].w * host[ids[i]].h};
+		for (uint32_t nb : c->views[ids[i]].neighbors) {
+			if (nb >= host.size() || !host[nb].depth) continue;
+			it.nbs.push_back(nb);
+			if ((int)it.nbs.size() == max_neighbors) break;
+		}
+		const int N = (int)it.nbs.size();
+		if (N < 1 || N < n_min_views || N < n_min_views_adjust) continue; // :3016-3019
+		stagePx += it.area; nNbAll += (size_t)N;
+		items.push_back(std::move(it));
+	}
+	if (stats) { stats->n_filtered = (uint32_t)items.size(); stats->n_skipped = (uint32_t)((size_t)n_ids - items.size()); }
+	if (items.empty()) return HCMVS_OK;
+	hipStream_t s = c->stream;
+	size_t cap = 0; // images per batch the environment asks for, 0 = by memory alone
+	if (!parse_filter_batch(getenv("HCMVS_FILTER_BATCH"), items.size(), &cap))
+		return fail(c, HCMVS_ERR_INVALID, "filter_sequence: HCMVS_FILTER_BATCH='%s' is neither a positive number nor 'all'", getenv("HCMVS_FILTER_BATCH"));
+	HIPCHK(c, c->filterStage.reserve(stagePx * 8, s));
+	HIPCHK(c, c->filterCnt.reserve(items.size() * 16, s));
+	// the batches (filter_plan.h): as many images as their keys fit into half of what is free (the keys buffer a previous call left counts
+	// as free).  When the keys cannot be allocated (the reserve has given back the post-filter chain's state by then) the plan is made again
+	// with half the bytes, until the largest batch is one image
+	std::vector<size_t> need;
+	for (const Item& it : items) need.push_back(it.area * it.nbs.size() * 8);
+	size_t freeB = 0, totalB = 0;
+	HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
+	size_t budget = cap ? ~(size_t)0 : (freeB + c->fuseScratch.capacity()) / 2;
+	FilterPlan plan;
+	for (;;) {
+		plan = plan_filter_batches(need, budget, cap);
+		const hipError_t e = c->fuseScratch.reserve(plan.keyBytes, s);
+		if (e == hipSuccess) break;
+		budget = filter_retry_budget(need, plan);
+		if (!budget) return fail(c, HCMVS_ERR_HIP, "filter_sequence: no device memory for the z-buffer keys of one image (%zu bytes): %s", plan.keyBytes, hipGetErrorString(e));
+	}
+	const std::vector<size_t>& first = plan.first;
+	const size_t keyBytes = plan.keyBytes;
+	const size_t nBatches = first.size() - 1;
+	// one table for the whole call: FilterRef per image | the neighbours' DevMaps | pairs | first workgroup per pair and per image, batch
+	// after batch.  It lives on the host until the synchronisation at the end (the upload is asynchronous).
+	Carve cv;
+	const size_t offRefs = cv(items.size() * sizeof(FilterRef)), offNbs = cv(nNbAll * sizeof(DevMap)), offPairs = cv(nNbAll * sizeof(FilterPair)),
+	             offPairFirst = cv((nNbAll + nBatches) * sizeof(int)), offRefFirst = cv((items.size() + nBatches) * sizeof(int));
+	HIPCHK(c, c->filterTab.reserve(cv.size, s));
+	std::vector<char> tab(cv.size, 0);
+	char* dTab = c->filterTab.get();
+	FilterRef* hRefs = (FilterRef*)(tab.data() + offRefs);
+	DevMap* hNbs = (DevMap*)(tab.data() + offNbs);
+	FilterPair* hPairs = (FilterPair*)(tab.data() + offPairs);
+	int* hPairFirst = (int*)(tab.data() + offPairFirst);
+	int* hRefFirst = (int*)(tab.data() + offRefFirst);
+	struct Launch { size_t ref0, nRefs, pair0, nPairs, pairFirst0, refFirst0, keyWords; int splatBlocks, voteBlocks; };
+	std::vector<Launch> launches;
+	size_t nbAt = 0, stageAt = 0, pfAt = 0, rfAt = 0;
+	for (size_t b = 0; b < nBatches; ++b) {
+		Launch L{first[b], first[b + 1] - first[b], nbAt, 0, pfAt, rfAt, 0, 0, 0};
+		size_t keyAt = 0;
+		for (size_t k = first[b]; k < first[b + 1]; ++k) {
+			const Item& it = items[k];
+			FilterRef& r = hRefs[k];
+			r.map = host[it.id];
+			r.nbs = (const DevMap*)(dTab + offNbs) + nbAt;
+			r.nNbs = (int32_t)it.nbs.size();
+			r.keys = c->fuseScratch.get<unsigned long long>() + keyAt;
+			r.newDepth = c->filterStage.get<float>() + stageAt; r.newConf = r.newDepth + it.area;
+			r.counters = c->filterCnt.get<unsigned long long>() + 2 * k;
+			stageAt += 2 * it.area;
+			hRefFirst[rfAt++] = L.voteBlocks;
+			L.voteBlocks += filter_blocks(it.area);
+			for (size_t n = 0; n < it.nbs.size(); ++n) {
+				hNbs[nbAt] = host[it.nbs[n]];
+				hPairs[nbAt] = FilterPair{(int32_t)(k - first[b]), (int32_t)n};
+				hPairFirst[pfAt++] = L.splatBlocks;
+				L.splatBlocks += filter_blocks((size_t)host[it.nbs[n]].w * host[it.nbs[n]].h);
+				++nbAt; ++L.nPairs;
+			}
+			keyAt += it.area * it.nbs.size();
+		}
+		hPairFirst[pfAt++] = L.splatBlocks;
+		hRefFirst[rfAt++] = L.voteBlocks;
+		L.keyWords = keyAt;
+		launches.push_back(L);
+	}
+	std::vector<unsigned long long> cnt(items.size() * 2); // (declared before the guard below: it must outlive the copy into it)
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	HIPCHK(c, hipEventCreate(&ev[0]));
+	if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(c, HCMVS_ERR_HIP, "filter_sequence: hipEventCreate failed"); }
+	// whichever way the call ends: the stream is idle before the host tables (tab, cnt: source and target of asynchronous copies) go
+	struct EndGuard { hipEvent_t* e; hipStream_t s; ~EndGuard() { (void)hipStreamSynchronize(s); (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } endGuard{ev, s};
+	HIPCHK(c, hipMemcpyAsync(dTab, tab.data(), cv.size, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemsetAsync(c->filterCnt.get(), 0, items.size() * 16, s));
+	HIPCHK(c, hipEventRecord(ev[0], s));
+	const FilterRef* dRefs = (const FilterRef*)(dTab + offRefs);
+	for (const Launch& L : launches) {
+		launch_fill_u64(c->fuseScratch.get<unsigned long long>(), ~0ull, L.keyWords, s);
+		launch_filter_splat_batch(dRefs + L.ref0, (const FilterPair*)(dTab + offPairs) + L.pair0, (const int*)(dTab + offPairFirst) + L.pairFirst0, (int)L.nPairs,
+		                          L.splatBlocks, s);
+		launch_filter_vote_batch(dRefs + L.ref0, (const int*)(dTab + offRefFirst) + L.refFirst0, (int)L.nRefs, L.voteBlocks, adjust, n_min_views, n_min_views_adjust,
+		                         depth_diff_threshold, s);
+	}
+	launch_filter_commit(dRefs, (int)items.size(), s); // every image was voted from the maps as the call found them; now they change
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[1], s));
+	HIPCHK(c, hipMemcpyAsync(cnt.data(), c->filterCnt.get(), items.size() * 16, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipStreamSynchronize(s)); // the only wait after the first launch: nothing synchronises between the batches
+	if (stats) {
+		for (size_t k = 0; k < items.size(); ++k) {
+			stats->n_processed += cnt[2 * k]; stats->n_discarded += cnt[2 * k + 1];
+			if (imgProc) imgProc[items[k].pos] = cnt[2 * k];
+			if (imgDisc) imgDisc[items[k].pos] = cnt[2 * k + 1];
+		}
+		for (const Launch& L : launches) stats->batch = std::max(stats->batch, (uint32_t)L.nRefs);
+		stats->device_bytes = keyBytes + stagePx * 8 + cv.size + items.size() * 16;
+		HIPCHK(c, hipEventElapsedTime(&stats->ms_device, ev[0], ev[1]));
+	}
 	return HCMVS_OK;
 }
 

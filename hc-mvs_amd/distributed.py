@@ -83,7 +83,8 @@ def _device_sync(dev):
 
 
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
-                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False):
+                  fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
+                  geometric_filter=None, gf_kw=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -93,7 +94,7 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             if postfilter and it in (1, 2):
                 all-gather of the packed maps -> hcmvs_postfilter_sequence over ALL images, on every rank -> the rank
                 takes its own images' filtered maps back out of the gathered buffer
-        all-gather of the packed maps -> hcmvs_set_depthmap_device + hcmvs_fuse on every rank (identical clouds)
+        all-gather of the packed maps -> hcmvs_set_depthmap_device [+ hcmvs_filter_sequence] + hcmvs_fuse on every rank (identical clouds)
 
     The post-filter is REPLICATED, not sharded: filtering image k is a fusion over the whole scene whose result (the depths it
     invalidates, the gaps it fills) is what image k + 1's fusion sees, so the images form one sequential chain; every rank runs that
@@ -126,6 +127,11 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                included (a Jacobi order).  interleave=True: the reference's own order -- the images are then estimated one after the other in
                EVERY outer iteration >= 1 (not only the filtered ones) and read the live maps: images < k as this iteration left them (in the
                last one: after the end pass), images > k from the previous one
+    geometric_filter: None (default: off), "adjust" or "strict": the depth-map filter stage (Scene::DenseReconstructionFilter,
+               SceneDensify.cpp:4100-4185; binding.Context.filter_sequence) over ALL images between the final all-gather and the fusion.
+               Replicated on every rank like the fusion -- every rank filters identical gathered maps with a deterministic kernel, and a
+               second all-gather of the filtered maps would cost more than the filter; gf_kw: max_neighbors, n_min_views,
+               n_min_views_adjust, depth_diff_threshold.  The returned `maps` are the filtered ones, `filter` the stage's counters
     Returns the fused cloud dict of binding.Context.fuse plus `maps`: {id: (depth, normal, conf) device tensors}."""
     import copy
     import numpy as np
@@ -251,6 +257,11 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     _device_sync(dev)
     register(allm)
     maps = {img: unpack_maps(allm[slab_index(k, world, n_local)], h, w) for k, img in enumerate(ids)}
+    filter_stats = None
+    if geometric_filter is not None:
+        if geometric_filter not in ("adjust", "strict"):
+            raise ValueError("densify_scene: geometric_filter is None, 'adjust' or 'strict', not %r" % (geometric_filter,))
+        filter_stats = ctx.filter_sequence(ids, adjust=geometric_filter == "adjust", **(gf_kw or {}))   # in place, synchronised on return
     # the cloud's buffers: as given, or counted -- a counting fusion first (no buffers), then the real one with exactly what it needs,
     # instead of half a point per pixel of the scene on every rank (66 GB of device and of host memory each at BASELINE configs[3]); a
     # fusion repeated on the maps a fusion has left makes the same decisions, so the cloud is the single pass's
@@ -266,6 +277,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     if capacity is None and hasattr(ctx, "fuse_count"):
         cloud["n_depths"] = counted[1]                     # the depths the fusion visited before it invalidated any (SceneDensify.cpp:3461 logs that number)
     cloud["maps"] = maps
+    if filter_stats is not None:
+        cloud["filter"] = filter_stats
     if viewspread:
         ctx.set_viewspread(False)
         for img in ids:

@@ -74,6 +74,8 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	                              // the results of every existing command line
 	int postFilterInterleave = 0; // --n-postfilter-interleave 1: estimate(k) -> post-filter(k) -> estimate(k + 1), the reference's own order
 	                              // (SceneDensify.cpp:3889-3965), one image per launch; 0: estimate all, then filter all
+	int nFilter = 0;              // --n-filter 0|1|2: the depth-map filter stage before the fusion (Scene::DenseReconstructionFilter, SceneDensify.cpp:4100-4185, which the
+	                              // fork switched off with if(0) at :3721): 0 off, 1 adjust (bFilterAdjust = 1), 2 strict.  --n-nOptimize bit 4 (ADJUST_FILTER) stays inert
 	int resume = 1;               // skip-if-exists (SceneDensify.cpp:3865-3880): an image whose final depth map is already in the working folder is not estimated again
 	int restoreHypothesis = 0;    // 1: the `restore` binary's extra last-sweep hypothesis from the previous level's maps
 	                              // (restore/libs/MVS/DepthMap.cpp:1527-1549); needs the previous level's maps in the working folder
@@ -747,7 +749,7 @@ int main(int argc, char** argv) {
 		"--n-usegeoconsistency", "--n-initTriangulate", "--n-viewspread", "--n-opticalflow", "--n-adapthalfwin",
 		"--n-propagatehalfwin", "--n-propagatestep",
 		// this driver's own
-		"--min-views-trust-point", "--fuse-order", "--fuse-count", "--device", "--devices", "--batch", "--seed", "--restore-hypothesis", "--n-postfilter", "--n-postfilter-interleave", "--resume"};
+		"--min-views-trust-point", "--fuse-order", "--fuse-count", "--device", "--devices", "--batch", "--seed", "--restore-hypothesis", "--n-postfilter", "--n-postfilter-interleave", "--resume", "--n-filter"};
 	for (int i = 1; i < argc; ++i) {
 		std::string a = argv[i], val;
 		if (a == "-h" || a == "--help") { kv["--help"] = "1"; continue; }
@@ -776,7 +778,7 @@ int main(int argc, char** argv) {
 	geti("--n-propagatehalfwin", o.propagateHalfWin); geti("--n-propagatestep", o.propagateStep);
 	getf("--n-photometric_flow", o.photometricFlow); getf("--depthweight", o.depthweight); getf("--normalweight", o.normalweight);
 	geti("--n-initTriangulate", o.initTriangulate); geti("--min-views-trust-point", o.minViewsTrustPoint);
-	geti("--fuse-order", o.fuseOrder); geti("--fuse-count", o.fuseCount); geti("--restore-hypothesis", o.restoreHypothesis); geti("--n-postfilter", o.postFilter); geti("--n-postfilter-interleave", o.postFilterInterleave); geti("--n-nOptimize", o.nOptimize); geti("--resume", o.resume); geti("--n-viewspread", o.viewspread);
+	geti("--fuse-order", o.fuseOrder); geti("--fuse-count", o.fuseCount); geti("--restore-hypothesis", o.restoreHypothesis); geti("--n-postfilter", o.postFilter); geti("--n-postfilter-interleave", o.postFilterInterleave); geti("--n-nOptimize", o.nOptimize); geti("--resume", o.resume); geti("--n-viewspread", o.viewspread); geti("--n-filter", o.nFilter);
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -802,6 +804,9 @@ int main(int argc, char** argv) {
 		                "[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n"
 		                "       --n-viewspread 0|1   from outer iteration 1 on every pixel also tries what its source views' depth maps hold where it projects to\n"
 		                "                            (default 0; the reference's default is 1 -- 0 keeps the results of command lines written before it existed)\n"
+		                "       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
+		                "                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
+		                "                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
 		                "       DensifyPointCloud -i dense.mvs [-o out.mvs] --filter-point-cloud <negative threshold>   (visibility filter of the cloud only:\n"
 		                "       writes <out>_filtered.mvs and <out>_filtered.ply)\n");
 		return EXIT_FAILURE;
@@ -810,6 +815,7 @@ int main(int argc, char** argv) {
 	if (o.output.empty()) o.output = o.input.substr(0, o.input.rfind('.')) + "_dense.mvs";
 	if (thFilterPointCloud < 0) return run_point_cloud_filter(o, thFilterPointCloud);
 	if (o.fusionMode < 0) { fprintf(stderr, "error: SGM fusion modes are not available\n"); return EXIT_FAILURE; }
+	if (o.nFilter < 0 || o.nFilter > 2) { fprintf(stderr, "error: --n-filter expects 0 (off), 1 (adjust) or 2 (strict)\n"); return EXIT_FAILURE; }
 	if (o.batch < 1) o.batch = 1;
 	if (o.batch > HCMVS_MAX_BATCH) o.batch = HCMVS_MAX_BATCH;
 	if (o.estimationItersExternal < 1) o.estimationItersExternal = 1;
@@ -943,6 +949,7 @@ int main(int argc, char** argv) {
 
 	// What has to fit into a device (bytes per pixel of an image): resident per reference image of the device -- maps 20, hint maps 16
 	// (restore variant), gray + colour + gradient 8; per source view the 2 x 2 footprints 16; per image of a batch the working state 24.
+	// With --n-filter the first device also holds the stage's staging slabs and one image's z-buffer keys.
 	// The first device also holds colour + gradient (4) and, with several devices, a copy of the maps (20) of EVERY image, the per-pass
 	// tables of the fusion (12 B per pixel and neighbour of the largest image + 40 B per pixel) and the device copy of the cloud
 	// (about half a point per pixel: 31 B, + 8 B per view entry).  The batch shrinks until the first device fits; a scene that does
@@ -962,6 +969,9 @@ int main(int argc, char** argv) {
 				size_t maxNb = 1;
 				for (uint32_t id : todo) maxNb = std::max(maxNb, std::min<size_t>(images[id].neighbors.size(), 31));
 				resident += allPx * 4 + (nDev > 1 ? allPx * 20 : 0) + maxPx * (12 * maxNb + 40);
+				// --n-filter: the staging of the filtered maps (8 B per pixel of the scene) and the z-buffer keys of a batch of one image with 8
+				// neighbours (the stage takes more images per batch when more memory is free)
+				if (o.nFilter) resident += allPx * 8 + maxPx * 8 * 8;
 				// the cloud: counted first when large (see the fusion below), so what is reserved is what it holds -- taken here as 0.2
 				// points per pixel (the reference reserves 0.15, SceneDensify.cpp:3298) with 3 view entries each
 				if (o.fusionMode != 1) resident += (allPx * 39 > ((size_t)4 << 30) && o.fuseCount != 0) ? allPx / 5 * (31 + 3 * 8) : allPx / 2 * 31 + allPx * 8;
@@ -1435,7 +1445,7 @@ int main(int argc, char** argv) {
 					if (it == 0 && !wait_prepared(b)) { fail_run("initialisation failed"); return; }
 					std::string err;
 					if (!estimate_images(d, batches[b].ids, pr, err)) { fail_run(err); return; }
-					if (last && !filterOnLast) saver_submit(batches[b].ids); // final maps of this batch: off to the host while the next batch runs
+					if (last && !filterOnLast && !o.nFilter) saver_submit(batches[b].ids); // final maps of this batch: off to the host while the next batch runs
 				}
 			}
 			if (filtered || serial) { // meet the others; the main thread filters
@@ -1504,7 +1514,7 @@ int main(int argc, char** argv) {
 			                            (unsigned long long)filledAll, now_s() - tp);
 		}
 		if (!exchange_maps(false)) { fprintf(stderr, "error: handing the filtered depth maps back to their devices failed\n"); return EXIT_FAILURE; }
-		if (last) saver_submit(work);
+		if (last && !o.nFilter) saver_submit(work); // (--n-filter: the files are written after the filter stage)
 		{ std::lock_guard<std::mutex> g(runMu); released = it; }
 		runCv.notify_all();
 	}
@@ -1523,6 +1533,25 @@ int main(int argc, char** argv) {
 		       "loading + view selection %.2f s, set-up %.2f s\n",
 		       work.size(), todo.size() - work.size(), o.estimationItersExternal, o.estimationIters, tEstimated - tInit,
 		       pixels * o.estimationItersExternal / std::max(1e-9, tEstimated - tInit - tPostfilter) / 1e6, tPostfilter, tLoaded - tStart, tInit - tLoaded);
+	// --n-filter: the filter stage (Scene::DenseReconstructionFilter, SceneDensify.cpp:4100-4185 -- the block the fork switched off at :3721-3756):
+	// every image that has maps, the ones loaded through skip-if-exists included, against the first 8 of its neighbours that have maps
+	// (:4116-4131), all from the maps as the estimates left them; then the filtered maps are saved (:4173) and the fusion works on them.
+	// On the first device, after the gather that also precedes the fusion.
+	if (o.nFilter && !todo.empty()) {
+		const double tf = now_s();
+		if (!exchange_maps(true)) { fprintf(stderr, "error: gathering the depth maps on device %d failed\n", devs[0].ordinal); return EXIT_FAILURE; }
+		if (!register_maps()) return EXIT_FAILURE;
+		// nMinViewsFilter 2, nMinViewsFilterAdjust 1, clamped to the calibrated images - 1 (SceneDensify.cpp:3014-3015)
+		const int nMinViewsFilter = std::min<int>(2, (int)nValid - 1), nMinViewsFilterAdjust = std::min<int>(1, (int)nValid - 1);
+		hcmvs_filter_stats fs;
+		memset(&fs, 0, sizeof fs);
+		CHK(hcmvs_filter_sequence(ctx, todo.data(), (int32_t)todo.size(), 8, o.nFilter == 1 ? 1 : 0, nMinViewsFilter, nMinViewsFilterAdjust, 0.01f, &fs));
+		if (!exchange_maps(false)) { fprintf(stderr, "error: handing the filtered depth maps back to their devices failed\n"); return EXIT_FAILURE; }
+		saver_submit(todo);
+		if (o.verbosity > 1)
+			printf("Depth-maps filtered: %u images, %llu/%llu depths discarded (%u skipped) in %.2f s (%s; %.2f ms on the device, batches of up to %u images)\n", fs.n_filtered,
+			       (unsigned long long)fs.n_discarded, (unsigned long long)fs.n_processed, fs.n_skipped, now_s() - tf, o.nFilter == 1 ? "adjust" : "strict", fs.ms_device, fs.batch);
+	}
 	// the fusion mutates the depth maps: every final map must be on the host first (the files may still be on their way)
 	saver_close();
 	{

@@ -12,6 +12,7 @@
  *           (SceneDensify.h:63, SceneDensify.cpp:758-1072) with DepthEstimator (DepthMap.cpp:386-1738)
  *   hcmvs_filter   <- bool DepthMapsData::FilterDepthMap(DepthData&, const IIndexArr&, bool bAdjust)
  *                     (SceneDensify.h:69, SceneDensify.cpp:3006-3259)
+ *   hcmvs_filter_sequence <- void Scene::DenseReconstructionFilter(void*) (SceneDensify.cpp:4100-4185), the filter stage over all images
  *   hcmvs_fuse     <- void DepthMapsData::FuseDepthMaps(PointCloud&, bool, bool)
  *                     (SceneDensify.h:70, SceneDensify.cpp:3265-3495)
  *   hcmvs_params   <- the OPTDENSE::* globals (DepthMap.cpp:67-143) this path reads
@@ -242,6 +243,39 @@ int hcmvs_set_neighbors(hcmvs_ctx* ctx, uint32_t id, const uint32_t* ids, int32_
 int hcmvs_filter(hcmvs_ctx* ctx, uint32_t ref_id, const uint32_t* neighbor_ids, int32_t n_neighbors, int32_t adjust,
                  int32_t n_min_views, int32_t n_min_views_adjust, float depth_diff_threshold, float* out_depth,
                  float* out_conf, uint64_t* n_processed, uint64_t* n_discarded);
+
+/* counters of one hcmvs_filter_sequence call */
+typedef struct {
+	uint64_t n_processed;      /* valid depths of the filtered images (the sum of what SceneDensify.cpp:3255 logs per image) */
+	uint64_t n_discarded;      /* ... that the filter removed */
+	uint32_t n_filtered;       /* images filtered */
+	uint32_t n_skipped;        /* images of ids left untouched: no maps, or fewer usable neighbours than the filter needs */
+	uint32_t batch;            /* reference images the largest batch held */
+	float ms_device;           /* device time of the stage, first fill to commit (HIP events on the context's stream) */
+	uint64_t device_bytes;     /* z-buffer keys of the largest batch + staging + tables */
+	uint64_t* image_processed; /* in: NULL, or n_ids entries; out: per entry of ids its processed depths (0 for a skipped image) */
+	uint64_t* image_discarded; /* the same for the discarded depths */
+} hcmvs_filter_stats;
+/* The depth-map filter STAGE: Scene::DenseReconstructionFilter (SceneDensify.cpp:4100-4185, queued at :3721-3756) on the registered
+ * maps (hcmvs_set_depthmap_device, or hcmvs_set_depthmap: the context's copies), updated in place like hcmvs_postfilter does;
+ * hcmvs_get_depthmap reads them back.
+ *   - Every image of ids that has maps is filtered (FilterDepthMap, the arithmetic of hcmvs_filter) against the first max_neighbors
+ *     entries of its hcmvs_set_neighbors list that have maps themselves; entries without maps are passed over, not counted
+ *     (:4116-4131; the reference's numMaxNeighbors is 8).  1 <= max_neighbors <= 64.
+ *   - Every image is filtered from the maps as they stood when the call began -- "load the filtered maps after all depth-maps were
+ *     filtered" (:4134-4135: with one thread every EVT_FILTERDEPTHMAP precedes every EVT_ADJUSTDEPTHMAP).  The new depth and
+ *     confidence wait in a staging area (8 B per pixel of the listed images) and replace the registered maps after the last vote.
+ *   - An image with fewer usable neighbours than n_min_views or n_min_views_adjust (or with none) keeps its maps (:3016-3019:
+ *     FilterDepthMap returns false, no adjust event); so does an image of ids without maps (:4110-4113).  Both are counted in
+ *     stats->n_skipped; neither is an error.
+ *   - Only depth and confidence change; the normal map is not touched, as in the reference.
+ * The images are processed in batches (one z-buffer fill, one splat launch over all (image, neighbour) pairs, one vote launch per
+ * batch, one commit launch at the end) on the context's stream, with no host synchronisation between the batches: like the other filter / fuse entries the call waits for
+ * the stream and uploads its map table when it begins, and it waits once more at the end, to read the counters.  The
+ * batch is as large as the z-buffer keys (images x neighbours x pixels x 8 B) fit into half of the free device memory;
+ * HCMVS_FILTER_BATCH=<n>|all in the environment forces it.  The result does not depend on it.  stats may be NULL. */
+int hcmvs_filter_sequence(hcmvs_ctx* ctx, const uint32_t* ids, int32_t n_ids, int32_t max_neighbors, int32_t adjust, int32_t n_min_views,
+                          int32_t n_min_views_adjust, float depth_diff_threshold, hcmvs_filter_stats* stats);
 
 /* Order in which the pixels of ONE image are visited by hcmvs_fuse (the image order is always the caller's).
  * 0 (default): raster order, the reference's (SceneDensify.cpp:3355-3358); the cloud equals the sequential one bit for bit.
