@@ -5,8 +5,9 @@
  * CGAL::pca_estimate_normals(points, k = 16): for every point the k nearest points (the point itself among them) are fitted
  * with a plane by principal component analysis and the plane normal becomes the point normal; the reference then flips it
  * towards the camera centre of the point's first view.  CGAL is absent: the k-nearest search and the PCA (covariance about
- * the centroid, smallest eigenvector by Jacobi rotations, double precision) are restated here; parity unpinned, the result
- * is defined up to the eigen-solver's rounding and ties in the k-th distance.
+ * the centroid, smallest eigenvector by Jacobi rotations, double precision) are restated here; parity with CGAL unpinned.  The
+ * neighbours are the k smallest by (squared distance in double, original index), so the result is defined up to the eigen-solver's
+ * rounding; the coordinates are finite (the C-ABI entry refuses others: the grid below is undefined for them).
  *
  * Layout: the points are binned into a uniform grid (cell edge ~ sqrt(k/2 * surface area / n): a cloud is a surface, so about
  * k/2 points per occupied cell and the k nearest of a surface point lie within one cell of it) and sorted by the Morton code

@@ -1568,6 +1568,11 @@ int hcmvs_estimate_point_normals(hcmvs_ctx* c, uint64_t n, const float* xyz, con
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!xyz || !n_views || !view_ids || !normal || k < 3 || k > 32) return fail(c, HCMVS_ERR_INVALID, "estimate_point_normals: bad arguments (3 <= k <= 32)");
 	if (n == 0) return HCMVS_OK;
+	// a NaN or an infinite coordinate leaves the bounding box, and with it the grid of the k-nearest search (cell size, dimensions, the
+	// levels of the climb), undefined: refused here, before anything reaches the device
+	for (uint64_t i = 0; i < n; ++i)
+		if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !std::isfinite(xyz[3 * i + 2]))
+			return fail(c, HCMVS_ERR_INVALID, "estimate_point_normals: point %llu has a coordinate that is not finite", (unsigned long long)i);
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	uint32_t maxId = 0;

@@ -354,7 +354,10 @@ int hcmvs_estimate_point_colors(hcmvs_ctx* ctx, uint64_t n_points, const float* 
 /* MVS::EstimatePointNormals (DepthMap.cpp:2221-2269; --estimate-normals 1): normal of the plane fitted by PCA to the
  * n_neighbors nearest points of every point (the reference calls CGAL::pca_estimate_normals with 16), oriented towards the first
  * view of the point.  Computed on the device (exact k-nearest search + PCA, 3 <= n_neighbors <= 32, fewer than 2^31 points);
- * CGAL is absent, so the PCA is restated (parity unpinned).  Host arrays in and out. */
+ * CGAL is absent, so the PCA is restated (parity unpinned).  Host arrays in and out.  The neighbours of a point are the
+ * min(n_neighbors, n_points) points with the smallest (squared distance in double, index), the point itself among them.
+ * HCMVS_ERR_INVALID, before anything reaches the device, when a coordinate is NaN or infinite (the message names the first
+ * such point), when a point has no view or when its first view is not registered; n_points == 0 succeeds and writes nothing. */
 int hcmvs_estimate_point_normals(hcmvs_ctx* ctx, uint64_t n_points, const float* xyz, const uint32_t* n_views, const uint32_t* view_ids,
                                  int32_t n_neighbors, float* normal);
 
