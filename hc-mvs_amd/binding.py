@@ -48,6 +48,11 @@ class VisibilityStats(C.Structure):
                 ("hits", C.c_uint64), ("device_bytes", C.c_uint64), ("ms_device", C.c_float)]
 
 
+class MeshSampleStats(C.Structure):
+    _fields_ = [("n_faces", C.c_uint64), ("n_zero_area_faces", C.c_uint64), ("n_points", C.c_uint64), ("area", C.c_double), ("density", C.c_double),
+                ("ms_device", C.c_float), ("device_bytes", C.c_uint64)]
+
+
 class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
@@ -73,7 +78,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_filter_sequence", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
-           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
+           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
 
@@ -166,6 +171,8 @@ def lib():
         L.hcmvs_estimate_point_normals.argtypes = [vp, C.c_uint64, fp, u32p, u32p, C.c_int32, fp]
         L.hcmvs_point_cloud_filter.argtypes = [vp, C.c_uint64, fp, u32p, u32p, C.c_uint32, C.POINTER(C.c_int32), dp, dp, dp, C.c_int32,
                                                C.POINTER(C.c_int32), u32p, u64p, C.POINTER(VisibilityStats)]
+        L.hcmvs_sample_mesh.argtypes = [vp, C.c_uint32, fp, C.c_uint32, u32p, fp, u8p, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, fp, u32p, u8p,
+                                        u64p, C.POINTER(MeshSampleStats)]
         L.hcmvs_resize_area_up.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
@@ -495,6 +502,36 @@ class Context:
                                                  kept.ctypes.data_as(u32), C.byref(nk), C.byref(st)))
         self.visibility_stats = {k: getattr(st, k) for k, _ in VisibilityStats._fields_}
         return vis, kept[:nk.value].copy()
+
+    def sample_mesh(self, vertices, faces, sample, seed=0, texcoords=None, texture_bgr=None, count_only=False):
+        """Mesh::SamplePoints on the device (DensifyPointCloud --sample-mesh): sample > 0 points per square unit, < 0 minus the number of
+        points; texcoords (n_faces, 3, 2) and texture_bgr (h, w, 3) both or neither.  Returns (xyz (n, 3) f32, face_ids (n,) u32, bgr (n, 3)
+        u8 or None, stats); count_only: no cloud is produced, xyz and face_ids are None and stats["n_points"] says how many points it has"""
+        V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        Fc = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+        u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        tc = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32).reshape(-1, 6)
+        tex = None if texture_bgr is None else np.ascontiguousarray(texture_bgr, np.uint8)
+        if tc is not None and len(tc) != len(Fc):
+            raise ValueError("texcoords: 6 values per face expected")
+        if tex is not None and (tex.ndim != 3 or tex.shape[2] != 3):
+            raise ValueError("texture_bgr: (h, w, 3) expected")
+        th, tw = (0, 0) if tex is None else tex.shape[:2]
+        head = (self._h, len(V), _f(V), len(Fc), Fc.ctypes.data_as(u32), None if tc is None else _f(tc), None if tex is None else tex.ctypes.data_as(u8),
+                tw, th, C.c_float(sample), C.c_uint64(seed))
+        n = C.c_uint64(); st = MeshSampleStats()
+        self._chk(lib().hcmvs_sample_mesh(*head, 0, None, None, None, C.byref(n), C.byref(st)))
+        if count_only or n.value == 0:
+            stats = {k: getattr(st, k) for k, _ in MeshSampleStats._fields_}
+            if count_only:
+                return None, None, None, stats
+            return np.zeros((0, 3), np.float32), np.zeros(0, np.uint32), None if tex is None else np.zeros((0, 3), np.uint8), stats
+        cap = n.value
+        xyz = np.empty((cap, 3), np.float32); fid = np.empty(cap, np.uint32)
+        bgr = None if tex is None else np.empty((cap, 3), np.uint8)
+        self._chk(lib().hcmvs_sample_mesh(*head, cap, _f(xyz), fid.ctypes.data_as(u32), None if bgr is None else bgr.ctypes.data_as(u8), C.byref(n), C.byref(st)))
+        assert n.value == cap
+        return xyz, fid, bgr, {k: getattr(st, k) for k, _ in MeshSampleStats._fields_}
 
     def postfilter(self, vid, order, n_min_views_fuse=2, depth_diff_threshold=0.01, normal_diff_deg=25.0, gap_size=7):
         """RemoveSmallSegments (fork version) + GapInterpolation on the registered device maps of view vid; returns pixels filled"""

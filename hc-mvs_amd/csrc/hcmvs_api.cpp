@@ -14,6 +14,7 @@
 #include "tri_init.h"
 #include "cloud_kernels.h"
 #include "vis_kernels.h"
+#include "mesh_kernels.h"
 #include "dev_buf.h"
 
 #include <cmath>
@@ -1621,6 +1622,49 @@ int hcmvs_point_cloud_filter(hcmvs_ctx* c, uint64_t n, const float* xyz, const u
 		stats->pairs = st.pairs; stats->skipped_pairs = st.skipped; stats->fallback_pairs = st.fallback; stats->candidates = st.candidates;
 		stats->hits = st.hits; stats->device_bytes = st.deviceBytes; stats->ms_device = st.ms;
 	}
+	return HCMVS_OK;
+}
+
+int hcmvs_sample_mesh(hcmvs_ctx* c, uint32_t n_vertices, const float* vertices, uint32_t n_faces, const uint32_t* faces, const float* texcoords,
+                      const uint8_t* texture, int32_t tex_w, int32_t tex_h, float sample, uint64_t seed, uint64_t capacity, float* xyz, uint32_t* face_of_point,
+                      uint8_t* bgr, uint64_t* n_points, hcmvs_mesh_sample_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (n_points) *n_points = 0;
+	if (stats) memset(stats, 0, sizeof *stats);
+	if (!n_points) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: null argument");
+	if (n_faces == 0) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: the mesh has no faces");
+	if (!faces || (n_vertices && !vertices)) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: null argument");
+	if (n_faces >= 0x7FFFFFFFu) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: 2^31 - 1 faces or more");
+	if (!(sample != 0.f) || !(sample > -2147483648.f)) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: sample is %g (a density > 0 or minus a number of points expected)", (double)sample);
+	if (texture && !texcoords) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: a texture without texture coordinates");
+	if (texcoords && !texture) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: texture coordinates without a texture");
+	if (texture && (tex_w <= 0 || tex_h <= 0)) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: texture of %d x %d pixels", tex_w, tex_h);
+	// a NaN or an infinite coordinate makes the areas, and with them the counts, undefined: refused here, before anything reaches the device
+	for (uint32_t i = 0; i < n_vertices; ++i)
+		if (!std::isfinite(vertices[3 * (size_t)i]) || !std::isfinite(vertices[3 * (size_t)i + 1]) || !std::isfinite(vertices[3 * (size_t)i + 2]))
+			return fail(c, HCMVS_ERR_INVALID, "sample_mesh: vertex %u has a coordinate that is not finite", i);
+	for (uint32_t f = 0; f < n_faces; ++f)
+		for (int q = 0; q < 3; ++q)
+			if (faces[3 * (size_t)f + q] >= n_vertices)
+				return fail(c, HCMVS_ERR_INVALID, "sample_mesh: face %u names vertex %u of %u", f, faces[3 * (size_t)f + q], n_vertices);
+	if (texcoords)
+		for (uint32_t f = 0; f < n_faces; ++f)
+			for (int q = 0; q < 6; ++q)
+				if (!std::isfinite(texcoords[6 * (size_t)f + q])) return fail(c, HCMVS_ERR_INVALID, "sample_mesh: face %u has a texture coordinate that is not finite", f);
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	hcmvs::MeshSampleInput in;
+	in.nVertices = n_vertices; in.nFaces = n_faces; in.vertices = vertices; in.faces = faces; in.texcoords = texcoords; in.texture = texture;
+	in.texW = tex_w; in.texH = tex_h; in.sample = sample; in.seed = seed;
+	hcmvs::MeshSampleCounters st;
+	std::string err;
+	const int rc = hcmvs::sample_mesh_device(in, capacity, xyz, face_of_point, bgr, stats != nullptr, st, c, c->stream, err);
+	*n_points = st.points;
+	if (stats) {
+		stats->n_faces = n_faces; stats->n_zero_area_faces = st.zeroAreaFaces; stats->n_points = st.points; stats->area = st.area; stats->density = st.density;
+		stats->ms_device = st.ms; stats->device_bytes = st.deviceBytes;
+	}
+	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
 	return HCMVS_OK;
 }
 

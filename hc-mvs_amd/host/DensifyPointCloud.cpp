@@ -7,7 +7,8 @@
  * (Scene::DenseReconstruction, SceneDensify.cpp:3532-3574, 3684), writes raw 'DR' depth maps
  * (DepthMap.cpp:2781-2846), fuses them (SceneDensify.cpp:3265-3495) and saves `<out>.ply` + `<out>.mvs`
  * (DensifyPointCloud.cpp:447-449).  With --filter-point-cloud < 0 it only filters the cloud of the input scene by visibility
- * (Scene::PointCloudFilter, DensifyPointCloud.cpp:399-414) and saves `<out>_filtered.mvs` + `.ply`.
+ * (Scene::PointCloudFilter, DensifyPointCloud.cpp:399-414) and saves `<out>_filtered.mvs` + `.ply`.  With --sample-mesh != 0 the input is a
+ * PLY triangle mesh: a point cloud is sampled on it (Mesh::SamplePoints, DensifyPointCloud.cpp:384-398) and saved as `<out>.ply`.
  *
  * Deliberately narrower than the reference ("defined subset"): images are read from binary
  * PPM/PGM files (no PNG/JPEG codecs here); the initial maps come from the Delaunay triangulation of the sparse points
@@ -27,6 +28,7 @@
  *   resume   an image whose final depth map is already in the working folder is not estimated again (SceneDensify.cpp:3865-3880)
  */
 #include "../../include/hcmvs_hip.h"
+#include "ply_mesh.h"
 
 #include <hip/hip_runtime.h>
 
@@ -729,6 +731,60 @@ int run_point_cloud_filter(const Options& o, int th) {
 	return EXIT_SUCCESS;
 }
 
+// --sample-mesh != 0 (DensifyPointCloud.cpp:384-398): Mesh::Load, Mesh::SamplePoints on the first device of --devices, then <output base>.ply;
+// nothing else runs.  > 0: points per square unit, < 0: minus the number of points.  The input is a PLY triangle mesh (host/ply_mesh.h); the
+// draws are the counter-based ones of DESIGN.md section 5 (D11) under --seed.  Colours when the mesh has texture coordinates and its
+// "comment TextureFile" names a binary PPM.
+int run_sample_mesh(const Options& o, float sample, unsigned long long seed) {
+	const size_t dot = o.input.rfind('.');
+	std::string ext = dot == std::string::npos ? std::string() : o.input.substr(dot);
+	for (char& ch : ext) ch = (char)tolower((unsigned char)ch);
+	if (ext == ".obj") { fprintf(stderr, "error: --sample-mesh reads PLY meshes only: OBJ input '%s' is not supported\n", o.input.c_str()); return EXIT_FAILURE; }
+	plymesh::Mesh mesh;
+	std::string err;
+	if (!plymesh::load(o.input, mesh, err)) { fprintf(stderr, "error: can not load the mesh '%s': %s\n", o.input.c_str(), err.c_str()); return EXIT_FAILURE; }
+	const size_t nV = mesh.vertices.size() / 3, nF = mesh.faces.size() / 3;
+	if (nF == 0) { fprintf(stderr, "error: the mesh '%s' has no faces\n", o.input.c_str()); return EXIT_FAILURE; }
+	std::vector<uint8_t> tex;
+	int tw = 0, th = 0;
+	bool textured = false;
+	if (mesh.texcoords.size() == 6 * nF && !mesh.textureFile.empty()) {
+		const std::string path = mesh.textureFile[0] == '/' ? mesh.textureFile : dirname_of(o.input) + "/" + mesh.textureFile;
+		textured = load_pnm(path, tw, th, tex) && tw > 0 && th > 0;
+		if (!textured && o.verbosity > 1) fprintf(stderr, "note: the texture '%s' is not a readable binary PPM: positions only\n", path.c_str());
+	} else if (o.verbosity > 1 && (!mesh.texcoords.empty() || !mesh.textureFile.empty()))
+		fprintf(stderr, "note: the mesh has %s: positions only\n", mesh.texcoords.empty() ? "a texture but no texture coordinates" : "texture coordinates but no texture");
+	hcmvs_ctx* ctx = nullptr;
+	if (hcmvs_create(o.devices[0], &ctx) != HCMVS_OK) { fprintf(stderr, "error: device %d is not a usable MI355X (there is no CPU path)\n", o.devices[0]); return EXIT_FAILURE; }
+	const double t0 = now_s();
+	const float* tc = textured ? mesh.texcoords.data() : nullptr;
+	const uint8_t* tx = textured ? tex.data() : nullptr;
+	uint64_t n = 0;
+	hcmvs_mesh_sample_stats st;
+	auto bail = [&](const char* what) {
+		fprintf(stderr, "error: %s: %s\n", what, hcmvs_last_error(ctx));
+		hcmvs_destroy(ctx);
+		return EXIT_FAILURE;
+	};
+	// counted first, so that the host buffers are exactly as large as the cloud
+	if (hcmvs_sample_mesh(ctx, (uint32_t)nV, mesh.vertices.data(), (uint32_t)nF, mesh.faces.data(), tc, tx, tw, th, sample, seed, 0, nullptr, nullptr, nullptr, &n, &st) != HCMVS_OK)
+		return bail("sampling the mesh failed");
+	RawArray<float> xyz(3 * n), nrm(0);
+	RawArray<uint8_t> bgr(textured ? 3 * n : 0);
+	if (xyz.size() != 3 * n || (textured && bgr.size() != 3 * n)) { fprintf(stderr, "error: out of host memory for %llu points\n", (unsigned long long)n); hcmvs_destroy(ctx); return EXIT_FAILURE; }
+	if (n && hcmvs_sample_mesh(ctx, (uint32_t)nV, mesh.vertices.data(), (uint32_t)nF, mesh.faces.data(), tc, tx, tw, th, sample, seed, n, xyz.data(), nullptr,
+	                           textured ? bgr.data() : nullptr, &n, &st) != HCMVS_OK)
+		return bail("sampling the mesh failed");
+	hcmvs_destroy(ctx);
+	if (o.verbosity > 0) printf("Sample mesh completed: %llu points (%.0f ms)\n", (unsigned long long)n, (now_s() - t0) * 1e3);
+	if (o.verbosity > 2)
+		printf("Mesh sampling: %zu faces (%llu of zero area), area %g, density %g, %.1f MiB device memory, %.2f ms device time\n", nF,
+		       (unsigned long long)st.n_zero_area_faces, st.area, st.density, st.device_bytes / 1048576.0, st.ms_device);
+	const std::string base = o.output.substr(0, o.output.rfind('.'));
+	if (!save_ply(base + ".ply", xyz, nrm, bgr)) { fprintf(stderr, "error: can not write '%s.ply'\n", base.c_str()); return EXIT_FAILURE; }
+	return EXIT_SUCCESS;
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -798,7 +854,7 @@ int main(int argc, char** argv) {
 		if (kv.count(k) && atoi(kv[k].c_str()) != 0 && o.verbosity > 1)
 			fprintf(stderr, "note: %s is not available in this build (defined subset); treated as 0\n", k);
 	const int thFilterPointCloud = kv.count("--filter-point-cloud") ? atoi(kv["--filter-point-cloud"].c_str()) : 0; // >= 0: no effect, as in the reference
-	if (kv.count("--sample-mesh") && atof(kv["--sample-mesh"].c_str()) != 0) { fprintf(stderr, "error: --sample-mesh is not available\n"); return EXIT_FAILURE; }
+	const float sampleMesh = kv.count("--sample-mesh") ? (float)atof(kv["--sample-mesh"].c_str()) : 0.f; // 0: no effect, as in the reference
 	if (o.input.empty() || kv.count("--help")) {
 		fprintf(stderr, "usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
 		                "[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n"
@@ -808,11 +864,14 @@ int main(int argc, char** argv) {
 		                "                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 		                "                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
 		                "       DensifyPointCloud -i dense.mvs [-o out.mvs] --filter-point-cloud <negative threshold>   (visibility filter of the cloud only:\n"
-		                "       writes <out>_filtered.mvs and <out>_filtered.ply)\n");
+		                "       writes <out>_filtered.mvs and <out>_filtered.ply)\n"
+		                "       DensifyPointCloud -i mesh.ply [-o out.mvs] --sample-mesh <d> [--seed n]   (samples a point cloud on a PLY triangle mesh and writes\n"
+		                "       <out>.ply: d > 0 points per square unit, d < 0 minus the number of points; colours when the mesh is textured by a binary PPM)\n");
 		return EXIT_FAILURE;
 	}
 	if (o.workdir.empty()) o.workdir = dirname_of(o.input);
 	if (o.output.empty()) o.output = o.input.substr(0, o.input.rfind('.')) + "_dense.mvs";
+	if (sampleMesh != 0) return run_sample_mesh(o, sampleMesh, kv.count("--seed") ? strtoull(kv["--seed"].c_str(), nullptr, 10) : (unsigned long long)o.seed);
 	if (thFilterPointCloud < 0) return run_point_cloud_filter(o, thFilterPointCloud);
 	if (o.fusionMode < 0) { fprintf(stderr, "error: SGM fusion modes are not available\n"); return EXIT_FAILURE; }
 	if (o.nFilter < 0 || o.nFilter > 2) { fprintf(stderr, "error: --n-filter expects 0 (off), 1 (adjust) or 2 (strict)\n"); return EXIT_FAILURE; }

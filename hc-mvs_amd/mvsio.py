@@ -166,6 +166,107 @@ def read_ply(path):
         return np.frombuffer(f.read(), np.dtype(props), count=n)
 
 
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4",
+              "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def write_ply_mesh(path, vertices, faces, texcoords=None, texture_file=None, ascii=False, index_type="int", list_name="vertex_indices"):
+    """PLY triangle mesh as Mesh::SavePLY writes it (Mesh.cpp:1513-1600): vertex x y z f32, face list uchar <index_type> <list_name>,
+    optionally list uchar float texcoord (6 per face: u v of the three corners) and "comment TextureFile <texture_file>"; binary
+    little-endian or ascii (floats with 9 significant digits: they read back exactly)"""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    Fc = np.ascontiguousarray(faces).reshape(-1, 3)
+    T = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32).reshape(-1, 6)
+    assert T is None or len(T) == len(Fc)
+    it = _PLY_TYPES[index_type]
+    head = "ply\nformat %s 1.0\n" % ("ascii" if ascii else "binary_little_endian")
+    if texture_file:
+        head += "comment TextureFile %s\n" % texture_file
+    head += "element vertex %d\nproperty float x\nproperty float y\nproperty float z\nelement face %d\nproperty list uchar %s %s\n" % (len(V), len(Fc), index_type, list_name)
+    if T is not None:
+        head += "property list uchar float texcoord\n"
+    head += "end_header\n"
+    with open(path, "wb") as f:
+        f.write(head.encode())
+        if ascii:
+            for v in V:
+                f.write(("%.9g %.9g %.9g\n" % tuple(v.tolist())).encode())
+            for k, fc in enumerate(Fc):
+                ln = "3 %d %d %d" % tuple(int(i) for i in fc)
+                if T is not None:
+                    ln += " 6 " + " ".join("%.9g" % t for t in T[k].tolist())
+                f.write((ln + "\n").encode())
+        else:
+            f.write(V.astype("<f4").tobytes())
+            fields = [("n", "u1"), ("i", it, 3)] + ([("m", "u1"), ("t", "<f4", 6)] if T is not None else [])
+            rec = np.zeros(len(Fc), np.dtype(fields))
+            rec["n"] = 3; rec["i"] = Fc
+            if T is not None:
+                rec["m"] = 6; rec["t"] = T
+            f.write(rec.tobytes())
+
+
+def read_ply_mesh(path):
+    """-> dict(vertices (n, 3) f32, faces (m, 3) u32, texcoords (m, 3, 2) f32 or None, texture_file or None); ascii or binary little-endian,
+    vertex properties beyond x y z are skipped; a face that is not a triangle is an error"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header")
+    end = data.index(b"\n", end) + 1
+    lines = [ln.strip() for ln in data[:end].decode("latin-1").split("\n")]
+    if lines[0] != "ply":
+        raise ValueError("not a PLY file")
+    fmt, tex_file, elements = None, None, []
+    for ln in lines[1:]:
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "comment" and len(w) >= 3 and w[1] == "TextureFile":
+            tex_file = ln.split("TextureFile", 1)[1].strip()
+        elif w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property":
+            elements[-1][2].append((w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]) if w[1] == "list" else (w[2], None, _PLY_TYPES[w[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError("unsupported PLY format %r" % fmt)
+    out = dict(vertices=None, faces=None, texcoords=None, texture_file=tex_file)
+    pos = end
+    tokens = iter(data[end:].split()) if fmt == "ascii" else None
+
+    def take(t, n=1):
+        nonlocal pos
+        if tokens is not None:
+            return [float(next(tokens)) for _ in range(n)]
+        a = np.frombuffer(data, t, n, pos)
+        pos += a.nbytes
+        return a.tolist()
+
+    for name, count, props in elements:
+        if name == "vertex" and fmt != "ascii" and all(c is None for _, c, _ in props):
+            rec = np.frombuffer(data, np.dtype([(nm, t) for nm, _, t in props]), count, pos)
+            pos += rec.nbytes
+            out["vertices"] = np.stack([rec["x"], rec["y"], rec["z"]], -1).astype(np.float32)
+            continue
+        rows = {nm: [] for nm, _, _ in props}
+        for _ in range(count):
+            for nm, ct, t in props:
+                rows[nm].append(take(t)[0] if ct is None else take(t, int(take(ct)[0])))
+        if name == "vertex":
+            out["vertices"] = np.stack([np.asarray(rows[k], np.float64) for k in "xyz"], -1).astype(np.float32).reshape(-1, 3)
+        elif name == "face":
+            key = "vertex_indices" if "vertex_indices" in rows else "vertex_index"
+            if any(len(r) != 3 for r in rows[key]):
+                raise ValueError("a face that is not a triangle")
+            out["faces"] = np.asarray(rows[key], np.float64).astype(np.uint32).reshape(-1, 3)
+            if "texcoord" in rows:
+                out["texcoords"] = np.asarray(rows["texcoord"], np.float64).astype(np.float32).reshape(-1, 3, 2)
+    if out["vertices"] is None or out["faces"] is None:
+        raise ValueError("the PLY file has no vertex or no face element")
+    return out
+
+
 def write_pgm(path, gray_u8):
     h, w = gray_u8.shape
     with open(path, "wb") as f:

@@ -383,6 +383,33 @@ int hcmvs_point_cloud_filter(hcmvs_ctx* ctx, uint64_t n_points, const float* xyz
                              uint32_t n_images, const int32_t* wh, const double* K, const double* R, const double* C, int32_t th_remove,
                              int32_t* visibility_or_null, uint32_t* kept, uint64_t* n_kept, hcmvs_visibility_stats* stats_or_null);
 
+/* counters of the last hcmvs_sample_mesh call */
+typedef struct {
+	uint64_t n_faces;           /* faces of the mesh */
+	uint64_t n_zero_area_faces; /* faces whose double area is exactly 0 (repeated or collinear vertices) */
+	uint64_t n_points;          /* points of the cloud */
+	double area;                /* Mesh::ComputeArea: the float32 face areas summed into a double in face order */
+	double density;             /* points per square unit the counts were drawn with (0: the area was below ZEROTOLERANCE<float>) */
+	float ms_device;            /* device time from the first kernel to the last (HIP events) */
+	uint64_t device_bytes;      /* device memory the call allocated */
+} hcmvs_mesh_sample_stats;
+/* Mesh::SamplePoints (Mesh.cpp:3444-3527; DensifyPointCloud --sample-mesh): a point cloud sampled uniformly on a triangle mesh, on the
+ * device.  sample > 0 is a density (points per square unit), sample < 0 a number of points (ROUND2INT(-sample), density = that / the
+ * mesh area).  Face f gets (unsigned)(area_f * density) points plus one more with the probability of the fractional part; the cloud
+ * comes out in the reference's order (faces ascending).  The reference's random stream is unseeded, so the draws are defined here
+ * (counter-based): the cloud depends on (mesh, sample, seed) only.  Host arrays in and out: vertices
+ * n_vertices*3, faces n_faces*3 (fewer than 2^31 - 1 faces); texcoords (n_faces*6: u v of the three corners) and texture (tex_h*tex_w*3, B,G,R)
+ * both or neither; out xyz capacity*3, face_of_point capacity or NULL, bgr capacity*3 or NULL (written only with a texture); fewer than
+ * 2^32 points.  With xyz == NULL the call only COUNTS (*n_points; the same seed gives the same count in the call that fills).
+ * capacity < the points needed: HCMVS_ERR_INVALID, *n_points = what is needed.  HCMVS_ERR_INVALID before anything reaches the device,
+ * with a message naming the first offender: a vertex coordinate or texture coordinate that is not finite, a vertex index >= n_vertices,
+ * n_faces == 0, sample == 0 (or NaN, or below -2^31), a texture without texcoords or texcoords without a texture.  Zero points is success.
+ * The work space of the mesh is checked against the free device memory before the first launch, the cloud's before the point pass. */
+int hcmvs_sample_mesh(hcmvs_ctx* ctx, uint32_t n_vertices, const float* vertices, uint32_t n_faces, const uint32_t* faces,
+                      const float* texcoords_or_null, const uint8_t* texture_bgr_or_null, int32_t tex_w, int32_t tex_h, float sample, uint64_t seed,
+                      uint64_t capacity, float* xyz_or_null, uint32_t* face_of_point_or_null, uint8_t* bgr_or_null, uint64_t* n_points,
+                      hcmvs_mesh_sample_stats* stats_or_null);
+
 #ifdef __cplusplus
 }
 #endif
