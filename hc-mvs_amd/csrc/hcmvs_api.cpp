@@ -32,6 +32,7 @@ using namespace hcmvs;
 namespace {
 
 constexpr int kMaxBatch = HCMVS_MAX_BATCH; // reference images estimated by one call
+constexpr uint32_t kMaxViewId = 65536;      // view ids, and the ids a neighbour list may name, lie below it
 
 struct View {
 	View() = default;
@@ -318,7 +319,7 @@ static int set_view(hcmvs_ctx* c, uint32_t id, int w, int h, const float* gray, 
 	if (!c) return HCMVS_ERR_INVALID;
 	// gray may be null when a colour image is given: a view that is only fused / filtered (camera, colours, gradient map), never the
 	// reference or a source view of an estimate -- what a rank of a multi-GPU job holds of the images other ranks estimate
-	if ((!gray && !bgr) || !K || !R || !C || w < 2 * kHalfWindow + 2 || h < 2 * kHalfWindow + 2 || w > 32768 || h > 32768 || id >= 65536)
+	if ((!gray && !bgr) || !K || !R || !C || w < 2 * kHalfWindow + 2 || h < 2 * kHalfWindow + 2 || w > 32768 || h > 32768 || id >= kMaxViewId)
 		return fail(c, HCMVS_ERR_INVALID, "upload_view: bad arguments (id %u, %dx%d)", id, w, h);
 	HIPCHK(c, hipSetDevice(c->device));
 	auto it = c->views.find(id);
@@ -359,7 +360,7 @@ int hcmvs_set_view_device(hcmvs_ctx* c, uint32_t id, int32_t w, int32_t h, const
 int hcmvs_rescale_view(hcmvs_ctx* c, uint32_t src_id, uint32_t dst_id, float scale) {
 	if (!c) return HCMVS_ERR_INVALID;
 	auto it = c->views.find(src_id);
-	if (it == c->views.end() || dst_id >= 65536 || dst_id == src_id) return fail(c, HCMVS_ERR_INVALID, "rescale_view: bad view ids %u -> %u", src_id, dst_id);
+	if (it == c->views.end() || dst_id >= kMaxViewId || dst_id == src_id) return fail(c, HCMVS_ERR_INVALID, "rescale_view: bad view ids %u -> %u", src_id, dst_id);
 	if (!(scale > 0.f) || fabsf(scale - 1.f) < 0.15f) return fail(c, HCMVS_ERR_INVALID, "rescale_view: scale %g is within 15 %% of 1 (DepthMap.h:234: not resampled)", scale);
 	const View& src = it->second;
 	if (!src.gray) return fail(c, HCMVS_ERR_INVALID, "rescale_view: view %u has no gray image (fuse-only view)", src_id);
@@ -969,6 +970,11 @@ int hcmvs_set_neighbors(hcmvs_ctx* c, uint32_t id, const uint32_t* ids, int32_t 
 	if (!c) return HCMVS_ERR_INVALID;
 	auto it = c->views.find(id);
 	if (it == c->views.end() || n < 0 || n > 64 || (n > 0 && !ids)) return fail(c, HCMVS_ERR_INVALID, "set_neighbors: bad arguments for view %u", id);
+	// any id a view could be registered under is taken (a neighbour need not be registered, nor have maps: the fuse, post-filter and filter
+	// entries pass such an entry over); an id no view can have is refused here, so that the map table, which covers every id a list names,
+	// stays within kMaxViewId entries
+	for (int k = 0; k < n; ++k)
+		if (ids[k] >= kMaxViewId) return fail(c, HCMVS_ERR_INVALID, "set_neighbors: neighbour id %u of view %u is not below %u", ids[k], id, kMaxViewId);
 	View& v = it->second;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -994,10 +1000,15 @@ static void fill_devmap(uint32_t id, const View& v, DevMap& m) {
 	m.depth = v.mDepth; m.normal = v.mNormal; m.conf = v.mConf; m.bgr = v.bgr;
 	m.neighbors = v.dNeighbors.get<uint32_t>(); m.dMin = v.dMin; m.dMax = v.dMax;
 }
-// device table indexed by image id (views without maps have depth == null)
+// device table indexed by image id (views without maps have depth == null).  It covers every id a registered neighbour list names as
+// well: the fuse and post-filter kernels index it (and the chain's PfImage table, which has the same size) with A.neighbors[q] before
+// they test depth, and the zeroed entry of an id that is not a registered view reads as "no maps".  hcmvs_set_neighbors bounds the ids.
 static int build_map_table(hcmvs_ctx* c, std::vector<DevMap>& host) {
 	uint32_t maxId = 0;
-	for (auto& kv : c->views) if (kv.first > maxId) maxId = kv.first;
+	for (auto& kv : c->views) {
+		if (kv.first > maxId) maxId = kv.first;
+		for (uint32_t nb : kv.second.neighbors) if (nb > maxId) maxId = nb;
+	}
 	host.assign((size_t)maxId + 1, DevMap());
 	for (auto& m : host) memset(&m, 0, sizeof m);
 	for (auto& kv : c->views) fill_devmap(kv.first, kv.second, host[kv.first]);

@@ -234,7 +234,12 @@ int hcmvs_set_depthmap_device(hcmvs_ctx* ctx, uint32_t id, float* d_depth, const
                               const float* d_conf, float d_min, float d_max);
 /* read the (possibly mutated) maps back; any pointer may be NULL */
 int hcmvs_get_depthmap(hcmvs_ctx* ctx, uint32_t id, float* depth, float* normal, float* conf);
-/* DepthData::neighbors of view `id`: image ids in decreasing importance (Scene.cpp:545-678), at most 31 for fuse */
+/* DepthData::neighbors of view `id`: image ids in decreasing importance (Scene.cpp:545-678), at most 31 for fuse.
+ * An entry need not be a registered view, nor one with maps: hcmvs_fuse, hcmvs_fuse_cloud, hcmvs_postfilter, hcmvs_postfilter_sequence and
+ * hcmvs_filter_sequence pass such an entry over, as the reference does with an image without a depth map (SceneDensify.cpp:3383-3385) --
+ * the result is that of the list without it (the entry still counts towards the 31).  The entry takes part as soon as a view with that id
+ * is registered and given maps.  Every entry must be below 65536, the bound on view ids (hcmvs_upload_view): a larger one is refused with
+ * HCMVS_ERR_INVALID and the list of the view stays as it was. */
 int hcmvs_set_neighbors(hcmvs_ctx* ctx, uint32_t id, const uint32_t* ids, int32_t n);
 
 /* bool DepthMapsData::FilterDepthMap(DepthData&, const IIndexArr&, bool bAdjust) (SceneDensify.cpp:3006-3259).

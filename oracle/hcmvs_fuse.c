@@ -197,6 +197,7 @@ int hcor_fuse_depthmaps(hcor_depthmap* maps, int n_maps, const uint32_t* order, 
 	const float thDepth = fDepthDiffThreshold * depthweight;
 	cloud->n_points = 0; cloud->n_depths = 0; cloud->n_view_entries = 0;
 	int rc = 0;
+	uint64_t* passEnd = cloud->owner ? (uint64_t*)calloc((size_t)n_order + 1, sizeof(uint64_t)) : NULL; /* point ids of pass oi: [passEnd[oi-1], passEnd[oi]) */
 	for (int oi = 0; oi < n_order && !rc; ++oi) {
 		const uint32_t A = order[oi];
 		hcor_depthmap* dA = &maps[A];
@@ -309,6 +310,19 @@ int hcor_fuse_depthmaps(hcor_depthmap* maps, int n_maps, const uint32_t* order, 
 			}
 		}
 		free(perm);
+		if (passEnd) passEnd[oi] = cloud->n_points;
+	}
+	if (passEnd) { /* the owner maps: per estimate the position in the fusion order of the pass that seeded its point */
+		for (int m = 0; m < n_maps; ++m) {
+			if (!claim[m] || !cloud->owner[m]) continue;
+			const size_t area = (size_t)maps[m].width * maps[m].height;
+			for (size_t i = 0; i < area; ++i) {
+				int oi = 0;
+				while (claim[m][i] != NO_ID && oi < n_order && (uint64_t)claim[m][i] >= passEnd[oi]) ++oi;
+				cloud->owner[m][i] = claim[m][i] == NO_ID ? (uint16_t)0xFFFF : (uint16_t)oi;
+			}
+		}
+		free(passEnd);
 	}
 	if (cloud->claim_mask && (int)cloud->claim_image < n_maps && claim[cloud->claim_image]) {
 		const size_t area = (size_t)maps[cloud->claim_image].width * maps[cloud->claim_image].height;
@@ -420,6 +434,11 @@ static uint64_t gap_line(float* dF, float* nF, float* conf, const uint8_t* gra, 
 
 int hcor_postfilter(hcor_depthmap* maps, int n_maps, uint32_t id, const uint8_t* gra, const uint32_t* order, int n_order, int nMinViewsFuse,
                     float fDepthDiffThreshold, float fNormalDiffDeg, int gap, int mode, uint64_t* n_filled) {
+	return hcor_postfilter_owners(maps, n_maps, id, gra, order, n_order, nMinViewsFuse, fDepthDiffThreshold, fNormalDiffDeg, gap, mode, n_filled, NULL);
+}
+
+int hcor_postfilter_owners(hcor_depthmap* maps, int n_maps, uint32_t id, const uint8_t* gra, const uint32_t* order, int n_order, int nMinViewsFuse,
+                           float fDepthDiffThreshold, float fNormalDiffDeg, int gap, int mode, uint64_t* n_filled, uint16_t** owner) {
 	if ((int)id >= n_maps || !maps[id].depth || !maps[id].normal) return 1;
 	hcor_depthmap* A = &maps[id];
 	const int W = A->width, H = A->height;
@@ -431,6 +450,7 @@ int hcor_postfilter(hcor_depthmap* maps, int n_maps, uint32_t id, const uint8_t*
 	memset(&cl, 0, sizeof cl);
 	cl.claim_image = id;
 	cl.claim_mask = (uint8_t*)calloc(area, 1);
+	cl.owner = owner;
 	hcor_fuse_depthmaps(maps, n_maps, order, n_order, nMinViewsFuse, fDepthDiffThreshold, fNormalDiffDeg, 1.f, 1.f, &cl); /* SD.cpp:2083, 2177: unweighted */
 	float* dF = (float*)malloc(area * sizeof(float));
 	float* nF = (float*)malloc(area * 3 * sizeof(float));

@@ -221,6 +221,9 @@ typedef struct {
 	/* optional: which pixels of image claim_image ended up in a fused point (arrDepthIdx != NO_ID), W*H bytes */
 	uint32_t claim_image;
 	uint8_t* claim_mask;
+	/* optional (NULL: not wanted): n_maps pointers, each NULL or W*H values of that image -- per estimate the position in the fusion
+	 * order of the pass whose point holds it when the fusion ends (the pass of the point's seed pixel), 0xFFFF = it belongs to no point */
+	uint16_t** owner;
 } hcor_cloud;
 
 /* MVS::EstimatePointColors (DM.cpp:2125-2161): colour of the closest view of each point, bilinear over 8-bit pixels with every
@@ -254,6 +257,9 @@ int hcor_fuse_depthmaps(hcor_depthmap* maps, int n_maps, const uint32_t* order, 
  * RemoveSmallSegments uses the plain thresholds (SD.cpp:2083, 2177), not the --depthweight / --normalweight ones of FuseDepthMaps. */
 int hcor_postfilter(hcor_depthmap* maps, int n_maps, uint32_t id, const uint8_t* gra, const uint32_t* order, int n_order, int n_min_views_fuse,
                     float depth_diff_threshold, float normal_diff_deg, int gap_size, int mode, uint64_t* n_filled);
+/* the same, with the owner maps (hcor_cloud::owner) of the fusion inside RemoveSmallSegments: owner NULL = hcor_postfilter */
+int hcor_postfilter_owners(hcor_depthmap* maps, int n_maps, uint32_t id, const uint8_t* gra, const uint32_t* order, int n_order, int n_min_views_fuse,
+                           float depth_diff_threshold, float normal_diff_deg, int gap_size, int mode, uint64_t* n_filled, uint16_t** owner);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,7 @@ class Cloud(C.Structure):
                 ("normal", C.POINTER(C.c_float)), ("bgr", C.POINTER(C.c_uint8)), ("n_views", C.POINTER(C.c_uint32)),
                 ("n_depths", C.c_uint64), ("views_capacity", C.c_uint64), ("n_view_entries", C.c_uint64),
                 ("view_ids", C.POINTER(C.c_uint32)), ("view_weights", C.POINTER(C.c_float)), ("claim_image", C.c_uint32),
-                ("claim_mask", C.POINTER(C.c_uint8))]
+                ("claim_mask", C.POINTER(C.c_uint8)), ("owner", C.POINTER(C.POINTER(C.c_uint16)))]
 
 
 _lib = None
@@ -124,6 +124,8 @@ def lib():
         L.hcor_postfilter.argtypes = [C.POINTER(DepthMap), C.c_int, C.c_uint32, u8p, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_float, C.c_float,
                                       C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.hcor_postfilter.restype = C.c_int
+        L.hcor_postfilter_owners.argtypes = L.hcor_postfilter.argtypes + [C.POINTER(C.POINTER(C.c_uint16))]
+        L.hcor_postfilter_owners.restype = C.c_int
     return _lib
 
 
@@ -339,8 +341,17 @@ def estimate_point_colors(maps, xyz, n_views, view_ids):
     return out
 
 
-def postfilter(maps, vid, gra, order, mode=ARITH_DEVICE, n_min_views_fuse=2, thr=0.01, normal_deg=25.0, gap=7):
-    """RemoveSmallSegments (fork) + GapInterpolation on image vid; maps are copied.  Returns (maps' depth copies, normal, conf of vid, n_filled)"""
+def owner_arrays(maps):
+    """per image a (h, w) uint16 owner map for hcor_cloud::owner, and the ctypes pointer array over them"""
+    own = [np.full(np.asarray(m["depth"]).shape, 0xFFFF, np.uint16) for m in maps]
+    ptrs = (C.POINTER(C.c_uint16) * max(len(maps), 1))(*[o.ctypes.data_as(C.POINTER(C.c_uint16)) for o in own])
+    return own, ptrs
+
+
+def postfilter(maps, vid, gra, order, mode=ARITH_DEVICE, n_min_views_fuse=2, thr=0.01, normal_deg=25.0, gap=7, owners=False):
+    """RemoveSmallSegments (fork) + GapInterpolation on image vid; maps are copied.  Returns (maps' depth copies, normal, conf of vid, n_filled);
+    owners=True appends the owner maps of the fusion inside it: per image a (h, w) uint16 map, for every estimate the position in `order`
+    of the pass whose point holds it, 0xFFFF = free"""
     maps = [dict(m) for m in maps]
     maps[vid]["normal"] = np.ascontiguousarray(maps[vid]["normal"], np.float32).copy()
     maps[vid]["conf"] = np.ascontiguousarray(maps[vid]["conf"], np.float32).copy()
@@ -349,6 +360,12 @@ def postfilter(maps, vid, gra, order, mode=ARITH_DEVICE, n_min_views_fuse=2, thr
     ids = (C.c_uint32 * len(order))(*order)
     nf = C.c_uint64()
     g = np.ascontiguousarray(gra, np.uint8)
+    if owners:
+        own, ptrs = owner_arrays(maps)
+        rc = lib().hcor_postfilter_owners(arr, len(maps), vid, u8ptr(g), ids, len(order), n_min_views_fuse, thr, normal_deg, gap, mode,
+                                          C.byref(nf), ptrs)
+        assert rc == 0
+        return depths, maps[vid]["normal"], maps[vid]["conf"], nf.value, own
     rc = lib().hcor_postfilter(arr, len(maps), vid, u8ptr(g), ids, len(order), n_min_views_fuse, thr, normal_deg, gap, mode,
                                C.byref(nf))
     assert rc == 0

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from chain_scenes import chain_maps
 from fusion_scene import make_maps
 
 pytestmark = pytest.mark.gpu
@@ -256,7 +257,11 @@ def test_postfilter_gradient_ratio_literal(ctx, pairs):
 def test_postfilter_sequence_equals_image_after_image(ctx, capfd, monkeypatch):
     """hcmvs_postfilter_sequence (all passes of a fusion enqueued without host synchronisation, one synchronisation per image)
     against the oracle run image after image, as the reference does over an outer iteration (SceneDensify.cpp:3939-3958): every
-    image's fusion sees the maps the images before it left.  Depth, normal, confidence of every image: bit for bit."""
+    image's fusion sees the maps the images before it left.  Depth, normal, confidence of every image: bit for bit.
+    One scene, compared after the whole chain.  tests/test_gpu_postfilter_chain.py compares after EVERY prefix of a chain (so that a wrong
+    owner map of fusion k shows in the image it masks), over scenes with nMinViewsFuse 3, images of different sizes, a target-only image,
+    17 neighbours, unregistered neighbour ids and a 500-step change inside an incremental fusion; tests/test_postfilter_chain_scenarios.py
+    establishes on the oracle's owner maps that those chains release, steal and re-link estimates at all."""
     maps, order = make_maps(w=144, h=112, f=130.0, n_views=5, noise=0.002, outliers=0.05, holes=0.12)
     for m in maps:
         m["conf"] = np.where(m["depth"] > 0, 1.3 - m["conf"], 0).astype(np.float32)
@@ -307,30 +312,6 @@ def test_postfilter_sequence_equals_image_after_image(ctx, capfd, monkeypatch):
         d, n, c = c2.get_depthmap(i, with_normal=True)
         assert np.array_equal(d, cur[i]["depth"]) and np.array_equal(n, cur[i]["normal"]) and np.array_equal(c, cur[i]["conf"]), i
     c2.close()
-
-
-def chain_maps(w=512, h=24, depth=5.0):
-    """three views of a fronto-parallel plane from ONE camera position: A at full horizontal resolution, B and C at half of it, their
-    pixel grids shifted by a quarter pixel either way, so that A's pixels 2j, 2j+1 land on B's pixel j and 2j-1, 2j on C's pixel j.
-    With nMinViewsFuse = 3 a pixel of A becomes a point only when BOTH its targets are still free: x = 0 is one (it claims B0 and
-    C0), so x = 1 (shares B0) is not, so C1 stays free and x = 2 is one ... -- the answer of every pixel of a row hangs on the answer
-    of the pixel before it, over the whole row, and it ALTERNATES: the worst case for an iteration that starts from "every pixel is a
-    point" (its changes travel one pixel per step)."""
-    f = 300.0
-    def view(width, fx, cx):
-        K = np.array([[fx, 0, cx], [0, f, (h - 1) / 2.0], [0, 0, 1]], np.float64)
-        d = np.full((h, width), depth, np.float32)
-        n = np.zeros((h, width, 3), np.float32); n[..., 2] = -1
-        g = np.full((h, width), 0.5, np.float32)
-        g8 = np.full((h, width), 128, np.uint8)
-        return dict(K=K, R=np.eye(3), C=np.zeros(3), gray=g, depth=d, normal=n, conf=np.full((h, width), 0.8, np.float32),
-                    bgr=np.stack([g8, g8, g8], -1).copy(), d_min=1.0, d_max=10.0, neighbors=[])
-    cxA = (w - 1) / 2.0
-    A = view(w, f, cxA)
-    B = view(w // 2 + 1, f / 2, cxA / 2 - 0.25)
-    Cm = view(w // 2 + 1, f / 2, cxA / 2 + 0.25)
-    A["neighbors"] = [1, 2]
-    return [A, B, Cm], [0, 1, 2]
 
 
 def test_fuse_alternating_chain_through_the_settle_loop(ctx):
