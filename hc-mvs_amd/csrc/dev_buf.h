@@ -1,9 +1,10 @@
 /* hc-mvs_amd/csrc/dev_buf.h -- the one owner of the library's device memory: a grow-only buffer, the out-of-memory hook, the carving
- * of one allocation into pieces */
+ * of one allocation into pieces (carve.h) */
 #ifndef HCMVS_DEV_BUF_H
 #define HCMVS_DEV_BUF_H
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "carve.h"
 namespace hcmvs {
 
 // Gives device memory back when an allocation fails; returns whether it freed anything (the allocation is then tried once more)
@@ -52,12 +53,6 @@ private:
 	void* p_ = nullptr;
 	size_t cap_ = 0;
 	Reclaimer* rec_ = nullptr;
-};
-
-// Offsets of the pieces of one allocation, each rounded up to 256 bytes; size is what the allocation needs
-struct Carve {
-	size_t size = 0;
-	size_t operator()(size_t bytes) { const size_t o = size; size += (bytes + 255) & ~(size_t)255; return o; }
 };
 
 } // namespace hcmvs

@@ -6,10 +6,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fuse_plan.h" // kFuseMaxViews
 
 namespace hcmvs {
-
-constexpr int kFuseMaxViews = 32; // views merged into one point / estimates one point can invalidate
 
 // one image's estimated maps + camera as the filter / fuse kernels see it (DepthMap.h:214-262 DepthData)
 struct DevMap {

@@ -11,6 +11,7 @@
 #include "fuse_common.h"
 #include "pf_chain.h"
 #include "filter_plan.h"
+#include "fuse_plan.h"
 #include "tri_init.h"
 #include "cloud_kernels.h"
 #include "vis_kernels.h"
@@ -134,6 +135,14 @@ static int fail(hcmvs_ctx* c, int code, const char* fmt, ...) {
 		hipError_t e_ = (call);                                                                     \
 		if (e_ != hipSuccess) return fail(c, HCMVS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
 	} while (0)
+
+// the registered view `id`, or null with the failure (HCMVS_ERR_INVALID) recorded for the entry point `who`
+static View* find_view(hcmvs_ctx* c, const char* who, uint32_t id) {
+	auto it = c->views.find(id);
+	if (it != c->views.end()) return &it->second;
+	fail(c, HCMVS_ERR_INVALID, "%s: unknown view %u", who, id);
+	return nullptr;
+}
 
 static void mat3_mul(const double* a, const double* b, double* c) {
 	for (int i = 0; i < 3; ++i)
@@ -386,30 +395,30 @@ int hcmvs_rescale_view(hcmvs_ctx* c, uint32_t src_id, uint32_t dst_id, float sca
 }
 int hcmvs_get_view_info(hcmvs_ctx* c, uint32_t id, int32_t* w, int32_t* h, double K[9]) {
 	if (!c) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "get_view_info: unknown view %u", id);
-	if (w) *w = it->second.w;
-	if (h) *h = it->second.h;
-	if (K) memcpy(K, it->second.K, sizeof(double) * 9);
+	const View* v = find_view(c, "get_view_info", id);
+	if (!v) return HCMVS_ERR_INVALID;
+	if (w) *w = v->w;
+	if (h) *h = v->h;
+	if (K) memcpy(K, v->K, sizeof(double) * 9);
 	return HCMVS_OK;
 }
 int hcmvs_get_view_gray(hcmvs_ctx* c, uint32_t id, float* out) {
 	if (!c || !out) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end() || !it->second.gray) return fail(c, HCMVS_ERR_INVALID, "get_view_gray: unknown view %u (or a fuse-only view)", id);
+	const View* v = find_view(c, "get_view_gray", id);
+	if (!v) return HCMVS_ERR_INVALID;
+	if (!v->gray) return fail(c, HCMVS_ERR_INVALID, "get_view_gray: view %u was registered without a gray image (fuse-only view)", id);
 	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipMemcpyAsync(out, it->second.gray, (size_t)it->second.w * it->second.h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(out, v->gray, (size_t)v->w * v->h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return HCMVS_OK;
 }
 
 int hcmvs_release_view(hcmvs_ctx* c, uint32_t id) {
 	if (!c) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "release_view: unknown view %u", id);
+	if (!find_view(c, "release_view", id)) return HCMVS_ERR_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	c->views.erase(it);
+	c->views.erase(id);
 	return HCMVS_OK;
 }
 
@@ -447,12 +456,12 @@ static int ensure_quads(hcmvs_ctx* c, View& v) {
 
 int hcmvs_get_gradient_map(hcmvs_ctx* c, uint32_t id, uint8_t* out) {
 	if (!c || !out) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "get_gradient_map: unknown view %u", id);
+	View* v = find_view(c, "get_gradient_map", id);
+	if (!v) return HCMVS_ERR_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	int rc = ensure_gradient(c, it->second);
+	int rc = ensure_gradient(c, *v);
 	if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(out, it->second.gra.get(), (size_t)it->second.w * it->second.h, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(out, v->gra.get(), (size_t)v->w * v->h, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return HCMVS_OK;
 }
@@ -462,9 +471,9 @@ int hcmvs_get_gradient_map(hcmvs_ctx* c, uint32_t id, uint8_t* out) {
 static int set_ignore_mask(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, const int32_t* ignore, int32_t nIgnore,
                            bool device) {
 	if (!c) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "set_ignore_mask: unknown view %u", id);
-	View& v = it->second;
+	View* pv = find_view(c, "set_ignore_mask", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	View& v = *pv;
 	HIPCHK(c, hipSetDevice(c->device));
 	if (!labels) { // (an estimate in flight may still read the old mask)
 		HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -505,9 +514,9 @@ int hcmvs_set_ignore_mask_device(hcmvs_ctx* c, uint32_t id, const uint16_t* d_la
 }
 int hcmvs_get_ignore_mask(hcmvs_ctx* c, uint32_t id, uint8_t* keep) {
 	if (!c || !keep) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "get_ignore_mask: unknown view %u", id);
-	const View& v = it->second;
+	const View* pv = find_view(c, "get_ignore_mask", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
 	if (!v.keep.capacity()) { memset(keep, 1, (size_t)v.w * v.h); return HCMVS_OK; } // no mask: every pixel is estimated
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipMemcpyAsync(keep, v.keep.get(), (size_t)v.w * v.h, hipMemcpyDeviceToHost, c->stream));
@@ -523,9 +532,9 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	// d_min == 0 is what the `restore` variant ends up with (its range takes the enlarged previous-level map in, zeros included,
 	// restore/libs/MVS/SceneDensify.cpp:526-532)
 	if (!(it.d_min >= 0.f) || !(it.d_max > it.d_min)) return fail(c, HCMVS_ERR_INVALID, "estimate: bad depth range [%g,%g)", it.d_min, it.d_max);
-	auto rit = c->views.find(it.ref_id);
-	if (rit == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "estimate: unknown reference view %u", it.ref_id);
-	View& ref = rit->second;
+	View* pref = find_view(c, "estimate", it.ref_id);
+	if (!pref) return HCMVS_ERR_INVALID;
+	View& ref = *pref;
 	if (!ref.gray) return fail(c, HCMVS_ERR_INVALID, "estimate: view %u was registered without a gray image (fuse-only view)", it.ref_id);
 	int rc = ensure_slot(c, slot, (size_t)ref.w * ref.h, ref.h);
 	if (rc) return rc;
@@ -545,10 +554,11 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	DevView* hv = c->hViews.data() + (size_t)slot * kMaxViews;
 	memset(hv, 0, sizeof(DevView) * kMaxViews);
 	uintptr_t lo = ~(uintptr_t)0, hi = 0;
+	View* src[HCMVS_MAX_VIEWS]; // the source views, looked up once
 	for (int v = 0; v < n_src; ++v) {
-		auto sit = c->views.find(it.src_ids[v]);
-		if (sit == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "estimate: unknown source view %u", it.src_ids[v]);
-		View& s = sit->second;
+		src[v] = find_view(c, "estimate", it.src_ids[v]);
+		if (!src[v]) return HCMVS_ERR_INVALID;
+		View& s = *src[v];
 		if (!s.gray) return fail(c, HCMVS_ERR_INVALID, "estimate: source view %u was registered without a gray image (fuse-only view)", it.src_ids[v]);
 		rc = ensure_quads(c, s);
 		if (rc) return rc;
@@ -569,15 +579,15 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	// compact slab owned by the context.
 	if (hi - lo < 0xFFFF0000ull) {
 		k.imgBase = (const char*)lo;
-		for (int v = 0; v < n_src; ++v) hv[v].byteOff = (uint32_t)((uintptr_t)c->views.find(it.src_ids[v])->second.quads.get() - lo);
+		for (int v = 0; v < n_src; ++v) hv[v].byteOff = (uint32_t)((uintptr_t)src[v]->quads.get() - lo);
 	} else {
 		Carve slab;
-		for (int v = 0; v < n_src; ++v) { const View& s = c->views.find(it.src_ids[v])->second; hv[v].byteOff = (uint32_t)slab((size_t)s.w * s.h * sizeof(float4)); }
+		for (int v = 0; v < n_src; ++v) { const View& s = *src[v]; hv[v].byteOff = (uint32_t)slab((size_t)s.w * s.h * sizeof(float4)); }
 		if (slab.size >= 0xFFFF0000ull) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
 		DevBuf& srcSlab = c->slots[slot].srcSlab;
 		HIPCHK(c, srcSlab.reserve(slab.size, c->stream));
 		for (int v = 0; v < n_src; ++v) {
-			const View& s = c->views.find(it.src_ids[v])->second;
+			const View& s = *src[v];
 			HIPCHK(c, hipMemcpyAsync(srcSlab.get() + hv[v].byteOff, s.quads.get(), (size_t)s.w * s.h * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 		}
 		k.imgBase = srcSlab.get();
@@ -610,7 +620,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const 
 	if (c->viewspread && p->it_external >= 1) {
 		bool any = false;
 		for (int v = 0; v < n_src; ++v) {
-			const View& s = c->views.find(it.src_ids[v])->second;
+			const View& s = *src[v];
 			if (!s.sDepth || s.rescaled) continue;
 			any = true;
 			hs[v].depth = s.sDepth; hs[v].normal = s.sNormal; hs[v].conf = s.sConf;
@@ -768,9 +778,9 @@ int hcmvs_set_viewspread(hcmvs_ctx* c, int32_t on) {
 }
 int hcmvs_set_spread_maps_device(hcmvs_ctx* c, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf) {
 	if (!c) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: unknown view %u", id);
-	View& v = it->second;
+	View* pv = find_view(c, "set_spread_maps", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	View& v = *pv;
 	if (!d_depth && !d_normal && !d_conf) { v.sDepth = v.sNormal = v.sConf = nullptr; return HCMVS_OK; }
 	if (!d_depth || !d_normal || !d_conf) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: view %u: depth, normal and conf are all needed (or all NULL)", id);
 	if (v.rescaled) return fail(c, HCMVS_ERR_INVALID, "set_spread_maps: view %u was made by hcmvs_rescale_view: a resampled view has no maps of its size and never spreads", id);
@@ -794,10 +804,10 @@ int hcmvs_estimate(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* src_ids, int32
                    float d_max, float* depth, float* normal, float* conf) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!depth || !normal || !conf) return fail(c, HCMVS_ERR_INVALID, "estimate: null map buffer");
-	auto rit = c->views.find(ref_id);
-	if (rit == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "estimate: unknown reference view %u", ref_id);
+	const View* ref = find_view(c, "estimate", ref_id);
+	if (!ref) return HCMVS_ERR_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	const size_t n = (size_t)rit->second.w * rit->second.h;
+	const size_t n = (size_t)ref->w * ref->h;
 	hipStream_t s = c->stream;
 	HIPCHK(c, c->sDepth.reserve(n * 4, s));
 	HIPCHK(c, c->sNormal.reserve(n * 12, s));
@@ -847,9 +857,9 @@ int hcmvs_splat_init(hcmvs_ctx* c, uint32_t id, const float* pts, int32_t n, flo
                      float* d_max) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!pts || !depth || !normal || !d_min || !d_max || n < 1) return fail(c, HCMVS_ERR_INVALID, "splat_init: bad arguments");
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "splat_init: unknown view %u", id);
-	const View& v = it->second;
+	const View* pv = find_view(c, "splat_init", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
 	return hcmvs_splat_points(v.w, v.h, v.K, v.R, v.C, pts, n, depth, normal, d_min, d_max);
 }
 
@@ -866,9 +876,9 @@ int hcmvs_triangulate_init(hcmvs_ctx* c, uint32_t id, const float* pts, int32_t 
                            float* normal, float* d_min, float* d_max) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!pts || !depth || !normal || !d_min || !d_max || n < 1) return fail(c, HCMVS_ERR_INVALID, "triangulate_init: bad arguments");
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "triangulate_init: unknown view %u", id);
-	const View& v = it->second;
+	const View* pv = find_view(c, "triangulate_init", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
 	if (hcmvs_triangulate_points(v.w, v.h, v.K, v.R, v.C, pts, n, avg_depth, add_corners, depth, normal, d_min, d_max) != HCMVS_OK)
 		return fail(c, HCMVS_ERR_INVALID, "triangulate_init: no sparse point in front of view %u", id);
 	return HCMVS_OK;
@@ -919,10 +929,10 @@ int hcmvs_resize_area_up(const float* src, int32_t sw, int32_t sh, int32_t ch, f
 
 static int set_maps(hcmvs_ctx* c, uint32_t id, const float* depth, const float* normal, const float* conf, float dmin, float dmax, bool copy) {
 	if (!c) return HCMVS_ERR_INVALID;
-	auto it = c->views.find(id);
-	if (it == c->views.end()) return fail(c, HCMVS_ERR_INVALID, "set_depthmap: unknown view %u", id);
+	View* pv = find_view(c, "set_depthmap", id);
+	if (!pv) return HCMVS_ERR_INVALID;
 	if (!depth || !conf) return fail(c, HCMVS_ERR_INVALID, "set_depthmap: null map");
-	View& v = it->second;
+	View& v = *pv;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	v.mDepth = v.mNormal = v.mConf = nullptr;
@@ -1003,7 +1013,10 @@ static void fill_devmap(uint32_t id, const View& v, DevMap& m) {
 // device table indexed by image id (views without maps have depth == null).  It covers every id a registered neighbour list names as
 // well: the fuse and post-filter kernels index it (and the chain's PfImage table, which has the same size) with A.neighbors[q] before
 // they test depth, and the zeroed entry of an id that is not a registered view reads as "no maps".  hcmvs_set_neighbors bounds the ids.
-static int build_map_table(hcmvs_ctx* c, std::vector<DevMap>& host) {
+// What the scene-level entries open with: the device, an idle stream, the table.
+static int scene_prologue(hcmvs_ctx* c, std::vector<DevMap>& host) {
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
 	uint32_t maxId = 0;
 	for (auto& kv : c->views) {
 		if (kv.first > maxId) maxId = kv.first;
@@ -1018,16 +1031,70 @@ static int build_map_table(hcmvs_ctx* c, std::vector<DevMap>& host) {
 	return HCMVS_OK;
 }
 
+// the map table as the plans of fuse_plan.h see it
+static std::vector<PlanMap> plan_maps(const hcmvs_ctx* c, const std::vector<DevMap>& host) {
+	std::vector<PlanMap> maps(host.size());
+	for (auto& kv : c->views) {
+		PlanMap& m = maps[kv.first];
+		m.pixels = (size_t)kv.second.w * kv.second.h; m.hasMaps = kv.second.mDepth != nullptr;
+		m.nNeighbors = (int)kv.second.neighbors.size(); m.neighbors = kv.second.neighbors.data();
+	}
+	return maps;
+}
+// the dimensions of a fusion over `order` for the entry point `who`, or the failure when one of their limits is broken
+static int fuse_call_dims(hcmvs_ctx* c, const char* who, const std::vector<PlanMap>& maps, const uint32_t* order, int n_order, FuseDims& d) {
+	d = fuse_dims(maps, order, n_order);
+	switch (d.broken) {
+	case kFuseOk: return HCMVS_OK;
+	case kFuseNoMaps: return fail(c, HCMVS_ERR_INVALID, "%s: view %u has no maps", who, order[d.at]);
+	case kFuseTooManyNeighbors: return fail(c, HCMVS_ERR_INVALID, "%s: view %u has too many neighbours", who, order[d.at]);
+	case kFuseStrideLimit: return fail(c, HCMVS_ERR_CAPACITY, "%s: maps of %zu pixels exceed the target tables (2^29 pixels)", who, d.stride);
+	case kFuseTableLimit: break;
+	}
+	return fail(c, HCMVS_ERR_CAPACITY, "%s: %d neighbours of %zu pixels exceed the per-pass tables", who, d.maxNb, d.stride);
+}
+
+// the per-pass tables of a fusion from scratch (fuse_plan.h FuseCore) in device memory, and what every pass of the call has in common
+struct FusePass {
+	FusePass(char* b, const FuseCore& o, size_t stride)
+	    : pending((uint32_t*)(b + o.pending)), settle(b + o.settle), ctl((uint32_t*)(b + o.ctl)), counters((unsigned long long*)(b + o.counters)),
+	      status((uint32_t*)(b + o.status)), merged((uint32_t*)(b + o.merged)), flag((uint8_t*)(b + o.flag)), nv((uint32_t*)(b + o.nv)),
+	      tb(fuse_tables((int32_t*)(b + o.targets), (uint32_t*)(b + o.head), (uint32_t*)(b + o.next), stride)) {}
+	uint32_t* pending; void* settle; uint32_t* ctl; unsigned long long* counters; uint32_t* status; uint32_t* merged; uint8_t* flag; uint32_t* nv;
+	FuseTables tb;
+	float thDepth = 0.f, normalError = 0.f;
+	int nMinViewsFuse = 0, vstride = 0;
+};
+// enqueues the pass of image A of a fusion from scratch.  oxyz .. oweights: where the pass leaves A's points (null: not wanted)
+static int enqueue_fuse_pass(hcmvs_ctx* c, const DevMap& A, const FusePass& t, float* oxyz, float* onormal, uint8_t* obgr, uint32_t* oviews, float* oweights,
+                             int order, bool wantPoints) {
+	hipStream_t s = c->stream;
+	HIPCHK(c, hipMemsetAsync(t.ctl, 0, kCtlBytes, s));
+	HIPCHK(c, hipMemsetAsync(t.tb.head, 0xFF, (size_t)A.nNeighbors * t.tb.stride * 4, s)); // empty bidder lists
+	launch_fuse_begin(A, c->dMaps.get<DevMap>(), t.tb, t.pending, t.ctl, t.flag, t.counters, t.thDepth, t.normalError, s);
+	launch_fuse_pass(A, c->dMaps.get<DevMap>(), t.tb, t.pending, t.settle, t.ctl, oxyz, onormal, obgr, t.nv, t.flag, oviews, oweights, t.vstride, t.merged, t.nMinViewsFuse,
+	                 order, t.counters, t.status, wantPoints, s);
+	return HCMVS_OK;
+}
+// after the last pass of a fusion: the status words and nWords 64-bit words at dWords (counters or totals), once the stream is idle.
+// HCMVS_ERR_TIMEOUT when a pass gave up.
+static int read_fuse_status(hcmvs_ctx* c, const char* who, const uint32_t* status, uint32_t st[4], const unsigned long long* dWords, unsigned long long* words, int nWords) {
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipMemcpyAsync(st, status, 16, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipMemcpyAsync(words, dWords, (size_t)nWords * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (st[0] != 0) return fail(c, HCMVS_ERR_TIMEOUT, "%s: the settle iteration of a fusion pass gave up; the registered depth maps are left partially fused", who);
+	return HCMVS_OK;
+}
+
 int hcmvs_filter(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* nbr, int32_t N, int32_t adjust, int32_t n_min_views,
                  int32_t n_min_views_adjust, float depth_diff_threshold, float* out_depth, float* out_conf, uint64_t* n_processed,
                  uint64_t* n_discarded) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!nbr || !out_depth || !out_conf || N < 1 || N > 64) return fail(c, HCMVS_ERR_INVALID, "filter: bad arguments");
 	if (N < n_min_views || N < n_min_views_adjust) return fail(c, HCMVS_ERR_INVALID, "filter: depth map %u can not be filtered (%d neighbours)", ref_id, N); // SceneDensify.cpp:3016-3019
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	std::vector<DevMap> host;
-	int rc = build_map_table(c, host);
+	int rc = scene_prologue(c, host);
 	if (rc) return rc;
 	if (ref_id >= host.size() || !host[ref_id].depth) return fail(c, HCMVS_ERR_INVALID, "filter: view %u has no maps", ref_id);
 	std::vector<DevMap> nbs((size_t)N);
@@ -1070,10 +1137,8 @@ int hcmvs_filter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, int3
 	uint64_t* const imgDisc = stats ? stats->image_discarded : nullptr;
 	if (stats) { memset(stats, 0, sizeof *stats); stats->image_processed = imgProc; stats->image_discarded = imgDisc; }
 	for (int i = 0; i < n_ids; ++i) { if (imgProc) imgProc[i] = 0; if (imgDisc) imgDisc[i] = 0; }
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	std::vector<DevMap> host;
-	int rc = build_map_table(c, host);
+	int rc = scene_prologue(c, host);
 	if (rc) return rc;
 	// the images to filter and their neighbours: the first max_neighbors of the list that have maps (SceneDensify.cpp:4116-4131)
 	struct Item { int pos; uint32_t id; std::vector<uint32_t> nbs; size_t area; };
@@ -1212,56 +1277,35 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 	if (!cloud) return fail(c, HCMVS_ERR_INVALID, "fuse: null cloud");
 	const uint64_t capacity = cloud->capacity, viewCapacity = cloud->view_ids ? cloud->views_capacity : 0;
 	float* xyz = cloud->xyz; float* normal = cloud->normal; uint8_t* bgr = cloud->bgr; uint32_t* n_views = cloud->n_views;
-	uint64_t* n_points = &cloud->n_points; uint64_t* n_depths = &cloud->n_depths;
 	cloud->n_points = cloud->n_depths = cloud->n_view_entries = 0;
 	if (cloud->view_ids && !cloud->view_weights) return fail(c, HCMVS_ERR_INVALID, "fuse: view_ids without view_weights");
-	if (!c) return HCMVS_ERR_INVALID;
-	if (!order || n_order < 1 || !n_points) return fail(c, HCMVS_ERR_INVALID, "fuse: bad arguments");
+	if (!order || n_order < 1) return fail(c, HCMVS_ERR_INVALID, "fuse: bad arguments");
 	const auto tCall = std::chrono::steady_clock::now();
 	const bool wantCloud = xyz != nullptr; // without xyz only the fusion's side effects (claims, invalidated depths) and counts are produced
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	std::vector<DevMap> host;
-	int rc = build_map_table(c, host);
+	int rc = scene_prologue(c, host);
 	if (rc) return rc;
-	size_t maxArea = 0;
-	for (int i = 0; i < n_order; ++i) {
-		if (order[i] >= host.size() || !host[order[i]].depth) return fail(c, HCMVS_ERR_INVALID, "fuse: view %u has no maps", order[i]);
-		const size_t a = (size_t)host[order[i]].w * host[order[i]].h;
-		if (a > maxArea) maxArea = a;
-		if (host[order[i]].nNeighbors > kFuseMaxViews - 1) return fail(c, HCMVS_ERR_INVALID, "fuse: view %u has too many neighbours", order[i]);
-	}
+	FuseDims dims;
+	rc = fuse_call_dims(c, "fuse", plan_maps(c, host), order, n_order, dims);
+	if (rc) return rc;
+	const size_t maxArea = dims.maxArea;
+	const int maxNb = dims.maxNb;
 	hipStream_t s = c->stream;
 	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // no claim mark may be left over from a fusion that failed half way
-	int maxNb = 1;
-	size_t stride = maxArea; // pixels reserved per neighbour map in the per-target tables
-	for (int i = 0; i < n_order; ++i) maxNb = std::max(maxNb, (int)host[order[i]].nNeighbors);
-	for (const auto& m : host) if (m.depth) stride = std::max(stride, (size_t)m.w * m.h);
-	const size_t tblElems = stride * (size_t)maxNb;
-	if (stride >= ((size_t)1 << 29)) return fail(c, HCMVS_ERR_CAPACITY, "fuse: maps of %zu pixels exceed the target tables (2^29 pixels)", stride);
-	if (tblElems > 0x7FFFFFFFull) return fail(c, HCMVS_ERR_CAPACITY, "fuse: %d neighbours of %zu pixels exceed the per-pass tables", maxNb, stride);
 	const size_t scanBytes = (fuse_scan_temp_bytes((int)maxArea) + 255) & ~(size_t)255;
-	Carve carve;
 	// the device cloud (context scratch) ...
-	const size_t oCX = carve(wantCloud ? capacity * 12 : 0), oCN = carve(normal ? capacity * 12 : 0), oCB = carve(bgr ? capacity * 3 : 0),
-	             oCV = carve(n_views || viewCapacity ? capacity * 4 : 0), oCVI = carve(viewCapacity * 4), oCVW = carve(viewCapacity * 4);
-	HIPCHK(c, c->fuseScratch.reserve(std::max(carve.size, (size_t)256), s));
+	const FuseCloudOut oc = plan_fuse_cloud_out(capacity, viewCapacity, wantCloud, normal != nullptr, bgr != nullptr, n_views != nullptr);
+	HIPCHK(c, c->fuseScratch.reserve(oc.bytes, s));
 	char* cb = c->fuseScratch.get();
-	float* cX = (float*)(cb + oCX); float* cN = normal ? (float*)(cb + oCN) : nullptr; uint8_t* cB = bgr ? (uint8_t*)(cb + oCB) : nullptr;
-	uint32_t* cV = n_views || viewCapacity ? (uint32_t*)(cb + oCV) : nullptr;
-	uint32_t* cVI = viewCapacity ? (uint32_t*)(cb + oCVI) : nullptr; float* cVW = viewCapacity ? (float*)(cb + oCVW) : nullptr;
+	float* cX = (float*)(cb + oc.xyz); float* cN = normal ? (float*)(cb + oc.normal) : nullptr; uint8_t* cB = bgr ? (uint8_t*)(cb + oc.bgr) : nullptr;
+	uint32_t* cV = n_views || viewCapacity ? (uint32_t*)(cb + oc.nViews) : nullptr;
+	uint32_t* cVI = viewCapacity ? (uint32_t*)(cb + oc.viewIds) : nullptr; float* cVW = viewCapacity ? (float*)(cb + oc.viewWeights) : nullptr;
 	// ... and the per-pass tables (sized for the largest image)
-	carve = Carve();
-	const size_t oPending = carve(maxArea * 4), oSettle = carve(fuse_settle_bytes(maxArea)), oTgt = carve(maxArea * 4 * (size_t)maxNb),
-	             oHead = carve(tblElems * 4), oNext = carve(maxArea * 4 * (size_t)maxNb), oCtl = carve(kCtlBytes), oCounters = carve(64), oStatus = carve(64), oTotals = carve(64),
-	             oMerged = carve(maxArea * 4), oFlag = carve(maxArea), oFlag32 = carve(maxArea * 4), oPos = carve(maxArea * 4), oScan = carve(scanBytes),
-	             oXyz = carve(maxArea * 12), oNrm = carve(maxArea * 12), oBgr = carve(maxArea * 3), oNv = carve(maxArea * 4),
-	             oPV = carve(viewCapacity ? maxArea * 4 * (size_t)(maxNb + 1) : 0), oPW = carve(viewCapacity ? maxArea * 4 * (size_t)(maxNb + 1) : 0),
-	             oVoff = carve(viewCapacity ? maxArea * 4 : 0);
-	HIPCHK(c, c->passScratch.reserve(carve.size, s));
+	const FuseCloudPass o = plan_fuse_cloud_pass(dims, fuse_settle_bytes(maxArea), kCtlBytes, scanBytes, viewCapacity != 0);
+	HIPCHK(c, c->passScratch.reserve(o.bytes, s));
 	const int vstride = maxNb + 1;
-	const float normalError = cosf(normal_diff_deg * normalweight * (3.14159274101257324f / 180.f)); // SceneDensify.cpp:3310
-	const float thDepth = depth_diff_threshold * depthweight;                                       // SceneDensify.cpp:3400
+	const float normalError = cosf(fd2r(normal_diff_deg * normalweight)); // SceneDensify.cpp:3310
+	const float thDepth = depth_diff_threshold * depthweight;             // SceneDensify.cpp:3400
 	const bool debug = getenv("HCMVS_FUSE_DEBUG") != nullptr; // per image: a synchronisation and a line on stderr
 
 	// Every pass of the fusion is enqueued on the context's stream, no host synchronisation between the images (stream order is the
@@ -1269,40 +1313,32 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 	// running point / view-entry totals an image's compaction starts from (fuse_advance_kernel), and the word that says a cloud or
 	// view-list capacity was exceeded.
 	char* b = c->passScratch.get();
-	uint32_t* pendingList = (uint32_t*)(b + oPending); uint32_t* ctl = (uint32_t*)(b + oCtl);
-	unsigned long long* counters = (unsigned long long*)(b + oCounters);
-	uint32_t* status = (uint32_t*)(b + oStatus);
-	unsigned long long* totals = (unsigned long long*)(b + oTotals);
-	int32_t* targets = (int32_t*)(b + oTgt);
-	uint32_t *head = (uint32_t*)(b + oHead), *next = (uint32_t*)(b + oNext);
-	uint8_t* flag = (uint8_t*)(b + oFlag);
-	uint32_t* flag32 = (uint32_t*)(b + oFlag32); uint32_t* pos = (uint32_t*)(b + oPos); uint32_t* merged = (uint32_t*)(b + oMerged);
-	float* pxyz = (float*)(b + oXyz); float* pnrm = (float*)(b + oNrm); uint8_t* pbgr = (uint8_t*)(b + oBgr); uint32_t* pnv = (uint32_t*)(b + oNv);
-	uint32_t* pviews = viewCapacity ? (uint32_t*)(b + oPV) : nullptr; float* pweights = viewCapacity ? (float*)(b + oPW) : nullptr;
-	uint32_t* voff = viewCapacity ? (uint32_t*)(b + oVoff) : nullptr;
-	const FuseTables tb = fuse_tables(targets, head, next, stride);
+	FusePass t(b, o, dims.stride);
+	t.thDepth = thDepth; t.normalError = normalError; t.nMinViewsFuse = n_min_views_fuse; t.vstride = vstride;
+	unsigned long long* totals = (unsigned long long*)(b + o.totals);
+	uint32_t* flag32 = (uint32_t*)(b + o.flag32); uint32_t* pos = (uint32_t*)(b + o.pos);
+	float* pxyz = (float*)(b + o.xyz); float* pnrm = (float*)(b + o.nrm); uint8_t* pbgr = (uint8_t*)(b + o.bgr);
+	uint32_t* pviews = viewCapacity ? (uint32_t*)(b + o.pviews) : nullptr; float* pweights = viewCapacity ? (float*)(b + o.pweights) : nullptr;
+	uint32_t* voff = viewCapacity ? (uint32_t*)(b + o.voff) : nullptr;
 	const auto tPasses = std::chrono::steady_clock::now();
-	HIPCHK(c, hipMemsetAsync(status, 0, 64, s));
+	HIPCHK(c, hipMemsetAsync(t.status, 0, 64, s));
 	HIPCHK(c, hipMemsetAsync(totals, 0, 64, s));
 	for (int oi = 0; oi < n_order; ++oi) {
 		const DevMap& A = host[order[oi]];
 		const int n = A.w * A.h;
 		const auto tPass = std::chrono::steady_clock::now();
-		HIPCHK(c, hipMemsetAsync(counters, 0, 64, s));
-		HIPCHK(c, hipMemsetAsync(ctl, 0, kCtlBytes, s));
-		HIPCHK(c, hipMemsetAsync(head, 0xFF, (size_t)A.nNeighbors * stride * 4, s)); // empty bidder lists
-		launch_fuse_begin(A, c->dMaps.get<DevMap>(), tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
-		launch_fuse_pass(A, c->dMaps.get<DevMap>(), tb, pendingList, b + oSettle, ctl, pxyz, cN ? pnrm : nullptr, cB ? pbgr : nullptr, pnv, flag, pviews, pweights, vstride,
-		                 merged, n_min_views_fuse, c->fuseOrder, counters, status, wantCloud, s);
+		HIPCHK(c, hipMemsetAsync(t.counters, 0, 64, s)); // the counters of this image alone
+		rc = enqueue_fuse_pass(c, A, t, pxyz, cN ? pnrm : nullptr, cB ? pbgr : nullptr, pviews, pweights, c->fuseOrder, wantCloud);
+		if (rc) return rc;
 		if (wantCloud)
-			launch_fuse_compact(n, flag, flag32, pos, b + oScan, scanBytes, pxyz, pnrm, pbgr, pnv, 0, capacity, cX, cN, cB, cV, pviews, pweights, vstride,
+			launch_fuse_compact(n, t.flag, flag32, pos, b + o.scan, scanBytes, pxyz, pnrm, pbgr, t.nv, 0, capacity, cX, cN, cB, cV, pviews, pweights, vstride,
 			                    voff, 0, viewCapacity, cVI, cVW, totals, s);
-		launch_fuse_advance(counters, totals, wantCloud ? capacity : 0, wantCloud ? viewCapacity : 0, status, s);
+		launch_fuse_advance(t.counters, totals, wantCloud ? capacity : 0, wantCloud ? viewCapacity : 0, t.status, s);
 		if (debug) {
 			unsigned long long cnt[5] = {0, 0, 0, 0, 0};
 			uint32_t ctlWords[kCtlBytes / 4];
-			HIPCHK(c, hipMemcpyAsync(cnt, counters, 40, hipMemcpyDeviceToHost, s));
-			HIPCHK(c, hipMemcpyAsync(ctlWords, ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
+			HIPCHK(c, hipMemcpyAsync(cnt, t.counters, 40, hipMemcpyDeviceToHost, s));
+			HIPCHK(c, hipMemcpyAsync(ctlWords, t.ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
 			HIPCHK(c, hipStreamSynchronize(s));
 			fprintf(stderr, "fuse: image %u: %u pending pixels, %llu become points; settle iteration: %u steps, work lists", A.id, ctlWords[kCtlPending], cnt[3], ctlWords[kCtlSteps]);
 			for (int k = 0; k <= kSettleSteps; ++k) fprintf(stderr, " %u", ctlWords[kCtlWork + k]);
@@ -1310,13 +1346,10 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 		}
 	}
 	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // the claim marks come off the depth maps
-	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
 	unsigned long long tot[3] = {0, 0, 0};
-	HIPCHK(c, hipMemcpyAsync(st, status, 16, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipMemcpyAsync(tot, totals, 24, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipStreamSynchronize(s));
-	if (st[0] != 0) return fail(c, HCMVS_ERR_TIMEOUT, "fuse: the settle iteration of a pass gave up; the registered depth maps are left partially fused");
+	rc = read_fuse_status(c, "fuse", t.status, st, totals, tot, 3);
+	if (rc) return rc;
 	if (st[3] == 1) return fail(c, HCMVS_ERR_CAPACITY, "fuse: cloud capacity %llu exceeded", (unsigned long long)capacity);
 	if (st[3] == 2) return fail(c, HCMVS_ERR_CAPACITY, "fuse: view-list capacity %llu exceeded", (unsigned long long)viewCapacity);
 	const auto tCopy = std::chrono::steady_clock::now();
@@ -1336,8 +1369,8 @@ int hcmvs_fuse_cloud(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32
 		        std::chrono::duration<double, std::milli>(tPasses - tCall).count(), std::chrono::duration<double, std::milli>(tCopy - tPasses).count(),
 		        std::chrono::duration<double, std::milli>(now - tCopy).count());
 	}
-	*n_points = total;
-	if (n_depths) *n_depths = tot[2];
+	cloud->n_points = total;
+	cloud->n_depths = tot[2];
 	cloud->n_view_entries = wantCloud ? viewTotal : tot[1]; // a counting call (no xyz) reports what the cloud's view lists would hold
 	return HCMVS_OK;
 }
@@ -1360,46 +1393,13 @@ int hcmvs_fuse(hcmvs_ctx* c, const uint32_t* order, int32_t n_order, int32_t n_m
 // each later one only what depends on the estimates that changed since (the pixels the previous image's gap interpolation filled, the
 // estimates the previous fusion zeroed).  Same decisions as a fusion from scratch, fusion after fusion.  Returns -1 when the chain can
 // not run this way (state does not fit the device, an image occurs twice, too many images) -- the caller then fuses from scratch.
-static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>& host, const uint32_t* ids, int32_t n_ids, const uint32_t* order, int32_t n_order,
-                                        int32_t n_min_views_fuse, float depth_diff_threshold, float normal_diff_deg, int32_t gap_size, uint64_t* n_filled) {
-	if (n_ids < 2 || n_ids > 2000 || n_order > 60000) return -1;
-	{ // an image is filled once per chain (a pair of estimates is linked into a bidder list at most twice)
-		std::vector<uint32_t> u(ids, ids + n_ids);
-		std::sort(u.begin(), u.end());
-		if (std::adjacent_find(u.begin(), u.end()) != u.end()) return -1;
-	}
-	std::vector<int> orderIndex(host.size(), -1);
-	for (int i = 0; i < n_order; ++i) { if (orderIndex[order[i]] >= 0) return -1; orderIndex[order[i]] = i; }
-	// layout of the state
-	size_t maxArea = 0, maxIdArea = 0;
-	Carve carve;
-	struct Lay { size_t own, chg, val, tgt, head, next, acc, mm, fm, stamp, touch, stride; };
-	std::vector<Lay> lay(host.size());
-	for (size_t id = 0; id < host.size(); ++id) {
-		const DevMap& m = host[id];
-		if (!m.depth) continue;
-		const size_t n = (size_t)m.w * m.h;
-		if (n >= ((size_t)1 << 26) - 1) return -1;
-		Lay& L = lay[id];
-		L.own = carve(n * 2); L.chg = carve(n); L.val = carve(n);
-		if (orderIndex[id] < 0) continue;
-		size_t stride = 1;
-		for (int q = 0; q < m.nNeighbors; ++q) {
-			const uint32_t nb = c->views.find((uint32_t)id)->second.neighbors[(size_t)q];
-			if (nb < host.size() && host[nb].depth) stride = std::max(stride, (size_t)host[nb].w * host[nb].h);
-		}
-		const size_t nNb = (size_t)std::max(m.nNeighbors, 1);
-		if (2 * nNb * n >= 0xFFFFFFFFull || nNb * stride >= 0xFFFFFFFFull) return -1;
-		L.stride = stride;
-		L.tgt = carve(n * nNb * 4); L.head = carve(nNb * stride * 4); L.next = carve(2 * nNb * n * 4);
-		L.acc = carve(n); L.mm = carve(n * 4); L.fm = carve(n * 4); L.stamp = carve(n * 4); L.touch = carve(n * 4);
-		maxArea = std::max(maxArea, n);
-	}
-	for (int k = 0; k < n_ids; ++k) { const View& v = c->views.find(ids[k])->second; maxIdArea = std::max(maxIdArea, (size_t)v.w * v.h); }
-	const size_t oAny = carve(host.size() * 4);
-	const size_t oTable = carve(host.size() * sizeof(PfImage)), oScratch = carve(pf_pass_scratch_bytes(maxArea)), oCtl = carve(kCtlBytes), oCounters = carve(64),
-	             oStatus = carve(64), oDF = carve(maxIdArea * 4), oDF2 = carve(maxIdArea * 4), oNF = carve(maxIdArea * 12);
-	const size_t off = carve.size, held = c->pfState.capacity();
+static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>& host, const std::vector<PlanMap>& maps, size_t maxArea, size_t maxIdArea,
+                                        const uint32_t* ids, int32_t n_ids, const uint32_t* order, int32_t n_order, int32_t n_min_views_fuse, float depth_diff_threshold,
+                                        float normal_diff_deg, int32_t gap_size, uint64_t* n_filled) {
+	// layout of the state (fuse_plan.h); maxArea: the largest image of the order, maxIdArea: the largest image to filter
+	const PfChainPlan lay = plan_pf_chain(maps, ids, n_ids, order, n_order, maxIdArea, sizeof(PfImage), pf_pass_scratch_bytes(maxArea), kCtlBytes);
+	if (!lay.ok) return -1;
+	const size_t off = lay.bytes, held = c->pfState.capacity();
 	if (held < off) {
 		size_t freeB = 0, totalB = 0;
 		if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return -1;
@@ -1416,13 +1416,13 @@ static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>&
 		const DevMap& m = host[id];
 		if (!m.depth) continue;
 		const size_t n = (size_t)m.w * m.h;
-		const Lay& L = lay[id];
+		const PfImagePlan& L = lay.images[id];
 		PfImage& P = pf[id];
-		P.own = (uint16_t*)(b + L.own); P.chgNow = (uint8_t*)(b + L.chg); P.valNext = (uint8_t*)(b + L.val); P.anyChg = (uint32_t*)(b + oAny) + id;
+		P.own = (uint16_t*)(b + L.own); P.chgNow = (uint8_t*)(b + L.chgNow); P.valNext = (uint8_t*)(b + L.valNext); P.anyChg = (uint32_t*)(b + lay.anyChg) + id;
 		HIPCHK(c, hipMemsetAsync(P.own, 0xFF, n * 2, s));
 		HIPCHK(c, hipMemsetAsync(P.chgNow, 0, n, s));
 		HIPCHK(c, hipMemsetAsync(P.valNext, 0, n, s));
-		if (orderIndex[id] < 0) continue;
+		if (!L.inOrder) continue;
 		const size_t nNb = (size_t)std::max(m.nNeighbors, 1);
 		P.tgt = (uint32_t*)(b + L.tgt); P.head = (uint32_t*)(b + L.head); P.next = (uint32_t*)(b + L.next); P.acc = (uint8_t*)(b + L.acc);
 		P.mm = (uint32_t*)(b + L.mm); P.fm = (uint32_t*)(b + L.fm); P.stamp = (uint32_t*)(b + L.stamp); P.touch = (uint32_t*)(b + L.touch); P.stride = L.stride;
@@ -1432,28 +1432,26 @@ static int postfilter_chain_incremental(hcmvs_ctx* c, const std::vector<DevMap>&
 		HIPCHK(c, hipMemsetAsync(P.mm, 0, n * 4, s)); HIPCHK(c, hipMemsetAsync(P.fm, 0, n * 4, s));
 		HIPCHK(c, hipMemsetAsync(P.stamp, 0, n * 4, s)); HIPCHK(c, hipMemsetAsync(P.touch, 0, n * 4, s));
 	}
-	HIPCHK(c, hipMemsetAsync(b + oAny, 0, host.size() * 4, s));
-	PfImage* dPf = (PfImage*)(b + oTable);
+	uint32_t* anyChg = (uint32_t*)(b + lay.anyChg);
+	HIPCHK(c, hipMemsetAsync(anyChg, 0, host.size() * 4, s));
+	PfImage* dPf = (PfImage*)(b + lay.table);
 	HIPCHK(c, hipMemcpyAsync(dPf, pf.data(), pf.size() * sizeof(PfImage), hipMemcpyHostToDevice, s));
-	uint32_t* ctl = (uint32_t*)(b + oCtl); unsigned long long* counters = (unsigned long long*)(b + oCounters); uint32_t* status = (uint32_t*)(b + oStatus);
-	float* dF = (float*)(b + oDF); float* dF2 = (float*)(b + oDF2); float* nF = (float*)(b + oNF);
+	uint32_t* ctl = (uint32_t*)(b + lay.ctl); unsigned long long* counters = (unsigned long long*)(b + lay.counters); uint32_t* status = (uint32_t*)(b + lay.status);
+	float* dF = (float*)(b + lay.dF); float* dF2 = (float*)(b + lay.dF2); float* nF = (float*)(b + lay.nF);
 	HIPCHK(c, hipMemsetAsync(status, 0, 64, s));
 	HIPCHK(c, hipMemsetAsync(counters, 0, 64, s));
-	const float normalError = cosf(normal_diff_deg * (3.14159274101257324f / 180.f)); // plain thresholds (SceneDensify.cpp:2083, 2177)
+	const float normalError = cosf(fd2r(normal_diff_deg)); // plain thresholds (SceneDensify.cpp:2083, 2177)
 	for (int k = 0; k < n_ids; ++k) {
-		if (k > 0) launch_pf_roll(c->dMaps.get<DevMap>(), dPf, (int)host.size(), (uint32_t*)(b + oAny), s);
+		if (k > 0) launch_pf_roll(c->dMaps.get<DevMap>(), dPf, (int)host.size(), anyChg, s);
 		for (int oi = 0; oi < n_order; ++oi)
-			launch_pf_pass(host[order[oi]], oi, c->dMaps.get<DevMap>(), dPf, pf[order[oi]], k == 0, depth_diff_threshold, normalError, n_min_views_fuse, (uint32_t)k, b + oScratch, ctl, status, s);
+			launch_pf_pass(host[order[oi]], oi, c->dMaps.get<DevMap>(), dPf, pf[order[oi]], k == 0, depth_diff_threshold, normalError, n_min_views_fuse, (uint32_t)k, b + lay.scratch, ctl, status, s);
 		View& v = c->views.find(ids[k])->second;
 		launch_pf_filter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, pf[ids[k]], v.gra.get<uint8_t>(), dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
 	}
-	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
 	unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-	HIPCHK(c, hipMemcpyAsync(st, status, 16, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipMemcpyAsync(cnt, counters, 48, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipStreamSynchronize(s));
-	if (st[0] != 0) return fail(c, HCMVS_ERR_TIMEOUT, "postfilter: the settle iteration of a fusion pass gave up; the registered depth maps are left partially fused");
+	const int rc = read_fuse_status(c, "postfilter", status, st, counters, cnt, 6);
+	if (rc) return rc;
 	if (n_filled) *n_filled = cnt[5];
 	return HCMVS_OK;
 }
@@ -1470,76 +1468,53 @@ int hcmvs_postfilter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, 
 		auto it = c->views.find(ids[k]);
 		if (it == c->views.end() || !it->second.mDepth || !it->second.mNormal) return fail(c, HCMVS_ERR_INVALID, "postfilter: view %u has no registered depth + normal maps", ids[k]);
 	}
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	std::vector<DevMap> host;
-	int rc = build_map_table(c, host);
+	int rc = scene_prologue(c, host);
 	if (rc) return rc;
-	size_t maxArea = 0, stride = 0, maxIdArea = 0;
-	int maxNb = 1;
-	for (int i = 0; i < n_order; ++i) {
-		if (order[i] >= host.size() || !host[order[i]].depth) return fail(c, HCMVS_ERR_INVALID, "postfilter: view %u has no maps", order[i]);
-		maxArea = std::max(maxArea, (size_t)host[order[i]].w * host[order[i]].h);
-		if (host[order[i]].nNeighbors > kFuseMaxViews - 1) return fail(c, HCMVS_ERR_INVALID, "postfilter: view %u has too many neighbours", order[i]);
-		maxNb = std::max(maxNb, (int)host[order[i]].nNeighbors);
-	}
-	stride = maxArea;
-	for (const auto& m : host) if (m.depth) stride = std::max(stride, (size_t)m.w * m.h);
+	const std::vector<PlanMap> maps = plan_maps(c, host);
+	FuseDims dims;
+	rc = fuse_call_dims(c, "postfilter", maps, order, n_order, dims);
+	if (rc) return rc;
+	size_t maxIdArea = 0;
 	for (int k = 0; k < n_ids; ++k) { View& v = c->views.find(ids[k])->second; maxIdArea = std::max(maxIdArea, (size_t)v.w * v.h); rc = ensure_gradient(c, v); if (rc) return rc; }
-	const size_t tblElems = stride * (size_t)maxNb;
-	if (stride >= ((size_t)1 << 29) || tblElems > 0x7FFFFFFFull) return fail(c, HCMVS_ERR_CAPACITY, "postfilter: %d neighbours of %zu pixels exceed the per-pass tables", maxNb, stride);
 	// a chain of two or more images: every fusion after the first is computed incrementally when the state fits the device
 	// (HCMVS_PF_FULL=1: every fusion from scratch, the path of rounds 1-3, kept as the fall-back and for comparison)
 	if (n_ids >= 2 && !getenv("HCMVS_PF_FULL")) {
 		launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), c->stream); // no claim mark may be left over from a fusion that failed half way
-		rc = postfilter_chain_incremental(c, host, ids, n_ids, order, n_order, n_min_views_fuse, depth_diff_threshold, normal_diff_deg, gap_size, n_filled);
+		rc = postfilter_chain_incremental(c, host, maps, dims.maxArea, maxIdArea, ids, n_ids, order, n_order, n_min_views_fuse, depth_diff_threshold, normal_diff_deg,
+		                                  gap_size, n_filled);
 		if (rc >= 0) return rc;
 	}
-	Carve carve;
-	const size_t oPending = carve(maxArea * 4), oSettle = carve(fuse_settle_bytes(maxArea)), oTgt = carve(maxArea * 4 * (size_t)maxNb),
-	             oHead = carve(tblElems * 4), oNext = carve(maxArea * 4 * (size_t)maxNb), oCtl = carve(kCtlBytes), oCounters = carve(64), oStatus = carve(64),
-	             oMerged = carve(maxArea * 4), oFlag = carve(maxArea), oNv = carve(maxArea * 4), oDF = carve(maxIdArea * 4), oDF2 = carve(maxIdArea * 4), oNF = carve(maxIdArea * 12);
-	HIPCHK(c, c->passScratch.reserve(carve.size, c->stream));
+	const FusePostfilterPass o = plan_postfilter_pass(dims, fuse_settle_bytes(dims.maxArea), kCtlBytes, maxIdArea);
+	HIPCHK(c, c->passScratch.reserve(o.bytes, c->stream));
 	char* b = c->passScratch.get();
-	uint32_t* pendingList = (uint32_t*)(b + oPending); uint32_t* ctl = (uint32_t*)(b + oCtl);
-	unsigned long long* counters = (unsigned long long*)(b + oCounters);
-	uint32_t* status = (uint32_t*)(b + oStatus);
-	int32_t* targets = (int32_t*)(b + oTgt);
-	uint32_t *head = (uint32_t*)(b + oHead), *next = (uint32_t*)(b + oNext);
-	uint8_t* flag = (uint8_t*)(b + oFlag); uint32_t* merged = (uint32_t*)(b + oMerged); uint32_t* pnv = (uint32_t*)(b + oNv);
-	float* dF = (float*)(b + oDF); float* dF2 = (float*)(b + oDF2); float* nF = (float*)(b + oNF);
-	const float normalError = cosf(normal_diff_deg * (3.14159274101257324f / 180.f)); // plain thresholds (SceneDensify.cpp:2083, 2177)
-	const float thDepth = depth_diff_threshold;
-	const FuseTables tb = fuse_tables(targets, head, next, stride);
+	FusePass t(b, o, dims.stride);
+	t.thDepth = depth_diff_threshold; t.normalError = cosf(fd2r(normal_diff_deg)); // plain thresholds (SceneDensify.cpp:2083, 2177)
+	t.nMinViewsFuse = n_min_views_fuse; t.vstride = dims.maxNb + 1;
+	float* dF = (float*)(b + o.dF); float* dF2 = (float*)(b + o.dF2); float* nF = (float*)(b + o.nF);
 	hipStream_t s = c->stream;
 	launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // no claim mark may be left over from a fusion or post-filter that failed half way
-	HIPCHK(c, hipMemsetAsync(status, 0, 64, s));
-	HIPCHK(c, hipMemsetAsync(counters, 0, 64, s)); // counters[5]: pixels filled, summed over the sequence
+	HIPCHK(c, hipMemsetAsync(t.status, 0, 64, s));
+	HIPCHK(c, hipMemsetAsync(t.counters, 0, 64, s)); // counters[5]: pixels filled, summed over the sequence
 	for (int k = 0; k < n_ids; ++k) {
 		View& v = c->views.find(ids[k])->second;
 		for (int oi = 0; oi < n_order; ++oi) {
-			const DevMap& A = host[order[oi]];
-			HIPCHK(c, hipMemsetAsync(ctl, 0, kCtlBytes, s));
-			HIPCHK(c, hipMemsetAsync(head, 0xFF, (size_t)A.nNeighbors * stride * 4, s)); // empty bidder lists
-			launch_fuse_begin(A, c->dMaps.get<DevMap>(), tb, pendingList, ctl, flag, counters, thDepth, normalError, s);
-			// the fork's RemoveSmallSegments visits the pixels in raster order (SceneDensify.cpp:2130-2131), whatever hcmvs_set_fuse_order says
-			// about FuseDepthMaps
-			launch_fuse_pass(A, c->dMaps.get<DevMap>(), tb, pendingList, b + oSettle, ctl, nullptr, nullptr, nullptr, pnv, flag, nullptr, nullptr, maxNb + 1, merged, n_min_views_fuse,
-			                 0, counters, status, false, s);
+			// no point outputs; the fork's RemoveSmallSegments visits the pixels in raster order (SceneDensify.cpp:2130-2131), whatever
+			// hcmvs_set_fuse_order says about FuseDepthMaps
+			rc = enqueue_fuse_pass(c, host[order[oi]], t, nullptr, nullptr, nullptr, nullptr, nullptr, 0, false);
+			if (rc) return rc;
 		}
-		launch_postfilter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, c->dMaps.get<DevMap>(), (int)host.size(), v.gra.get<uint8_t>(), dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f, counters + 5, s);
+		launch_postfilter(v.w, v.h, v.mDepth, v.mNormal, v.mConf, c->dMaps.get<DevMap>(), (int)host.size(), v.gra.get<uint8_t>(), dF, dF2, nF, gap_size, depth_diff_threshold * 2.5f,
+		                  t.counters + 5, s);
 	}
-	HIPCHK(c, hipGetLastError());
 	uint32_t st[4] = {0, 0, 0, 0};
 	unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-	HIPCHK(c, hipMemcpyAsync(st, status, 16, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipMemcpyAsync(cnt, counters, 48, hipMemcpyDeviceToHost, s));
-	HIPCHK(c, hipStreamSynchronize(s));
-	if (st[0] != 0) {
+	rc = read_fuse_status(c, "postfilter", t.status, st, t.counters, cnt, 6);
+	if (rc == HCMVS_ERR_TIMEOUT) {
 		launch_unclaim(c->dMaps.get<DevMap>(), (int)host.size(), s); // an estimate or a saved map must never see a claim mark (negative depth)
 		(void)hipStreamSynchronize(s);
-		return fail(c, HCMVS_ERR_TIMEOUT, "postfilter: the settle iteration of a fusion pass gave up; the registered depth maps are left partially fused");
 	}
+	if (rc) return rc;
 	if (n_filled) *n_filled = cnt[5];
 	return HCMVS_OK;
 }
@@ -1553,26 +1528,24 @@ int hcmvs_estimate_point_colors(hcmvs_ctx* c, uint64_t n, const float* xyz, cons
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!xyz || !n_views || !view_ids || !bgr) return fail(c, HCMVS_ERR_INVALID, "estimate_point_colors: null argument");
 	if (n == 0) return HCMVS_OK;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	std::vector<DevMap> host;
-	int rc = build_map_table(c, host);
+	int rc = scene_prologue(c, host);
 	if (rc) return rc;
 	std::vector<unsigned long long> off(n + 1, 0);
 	for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + n_views[i];
 	for (unsigned long long k = 0; k < off[n]; ++k)
-		if (view_ids[k] >= host.size() || !c->views.count(view_ids[k])) return fail(c, HCMVS_ERR_INVALID, "estimate_point_colors: unknown view %u", view_ids[k]);
+		if (!find_view(c, "estimate_point_colors", view_ids[k])) return HCMVS_ERR_INVALID; // (the map table covers every registered view)
 	hipStream_t s = c->stream;
 	DevBuf dX(c), dOff(c), dV(c), dC(c); // freed on return
 	if (dX.reserve(n * 12, s) != hipSuccess || dOff.reserve((n + 1) * 8, s) != hipSuccess || dV.reserve(std::max<unsigned long long>(off[n], 1) * 4, s) != hipSuccess ||
 	    dC.reserve(n * 3, s) != hipSuccess) return fail(c, HCMVS_ERR_HIP, "estimate_point_colors: out of device memory");
-	(void)hipMemcpyAsync(dX.get(), xyz, n * 12, hipMemcpyHostToDevice, s);
-	(void)hipMemcpyAsync(dOff.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s);
-	(void)hipMemcpyAsync(dV.get(), view_ids, off[n] * 4, hipMemcpyHostToDevice, s);
+	HIPCHK(c, hipMemcpyAsync(dX.get(), xyz, n * 12, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipMemcpyAsync(dOff.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+	if (off[n]) HIPCHK(c, hipMemcpyAsync(dV.get(), view_ids, off[n] * 4, hipMemcpyHostToDevice, s));
 	launch_point_colors(n, dX.get<float>(), dOff.get<unsigned long long>(), dV.get<uint32_t>(), c->dMaps.get<DevMap>(), dC.get<uint8_t>(), s);
-	const hipError_t e1 = hipMemcpyAsync(bgr, dC.get(), n * 3, hipMemcpyDeviceToHost, s);
-	const hipError_t e2 = hipStreamSynchronize(s);
-	if (e1 != hipSuccess || e2 != hipSuccess || hipGetLastError() != hipSuccess) return fail(c, HCMVS_ERR_HIP, "estimate_point_colors: device failure");
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipMemcpyAsync(bgr, dC.get(), n * 3, hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipStreamSynchronize(s));
 	return HCMVS_OK;
 }
 
@@ -1595,7 +1568,7 @@ int hcmvs_estimate_point_normals(hcmvs_ctx* c, uint64_t n, const float* xyz, con
 	unsigned long long off = 0;
 	for (uint64_t i = 0; i < n; ++i) {
 		if (n_views[i] < 1) return fail(c, HCMVS_ERR_INVALID, "estimate_point_normals: point %llu has no view", (unsigned long long)i);
-		if (!c->views.count(view_ids[off])) return fail(c, HCMVS_ERR_INVALID, "estimate_point_normals: unknown view %u", view_ids[off]);
+		if (!find_view(c, "estimate_point_normals", view_ids[off])) return HCMVS_ERR_INVALID;
 		first[i] = view_ids[off];
 		off += n_views[i];
 	}
