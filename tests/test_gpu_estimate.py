@@ -322,16 +322,23 @@ def test_full_size_schedule_invariance():
     """BASELINE.json configs[1] at full size (1920x1080, 8 source views, 7x7, 8 sweeps): the oracle cannot run this in seconds, so
     parity is shown through properties that do not depend on the size -- the maps must not depend on how the rows are
     scheduled (one image alone with two waves per row and whole rows == the same image inside a batch with one wave per row, XCD
-    affinity and the rows handed out in stretches of 256 columns), the evaluation count per pixel-sweep is the algorithm's
+    affinity and the rows handed out in stretches of 256 columns == the same batch with all eight sweeps in ONE launch, how 12 or more
+    such images run and what bench.py times), the evaluation count per pixel-sweep is the algorithm's
     (2 propagations + 6 refinements, fewer where a neighbour is already good), and the result converges to the analytic ground truth."""
     torch = pytest.importorskip("torch")
     import os
+    import time
     os.environ["HCMVS_SWEEP_SEGMENT"] = "256"     # (the automatic policy takes stretches for 1 .. 11 images of this size: sweep_plan.h)
     try:
         c = binding.Context(0)
     finally:
         os.environ.pop("HCMVS_SWEEP_SEGMENT", None)
     c1 = binding.Context(0)
+    os.environ["HCMVS_SWEEP_LAUNCHES"] = "one"
+    try:
+        c2 = binding.Context(0)
+    finally:
+        os.environ.pop("HCMVS_SWEEP_LAUNCHES", None)
     try:
         W, H = 1920, 1080
         scenes = [_scene(W, H, 1600.0, 8, seed=61, n_pts=2000), _scene(W, H, 1600.0, 8, seed=62, n_pts=2000),
@@ -340,6 +347,15 @@ def test_full_size_schedule_invariance():
         pg = binding.default_params(adapthalfwin=6, n_estimation_iters=SWEEPS, seed=4321)
         got3, keep = _batch_run(c, torch, scenes, pg, [0, 1, 2])
         evals3 = c.stats().evals
+        # the same batch, every image going through its eight sweeps independently of the others in one launch
+        t0 = time.perf_counter()
+        one3, _ = _batch_run(c2, torch, scenes, pg, [0, 1, 2])
+        st = c2.stats()
+        print("one-launch leg: %.3f s wall, %.1f ms on the device" % (time.perf_counter() - t0, st.ms_total))
+        assert st.n_sweep_launches == 1 and st.evals == evals3
+        for si, (g, a) in enumerate(zip(got3, one3)):
+            for gm, am, n in zip(g, a, ("depth", "normal", "conf")):
+                assert np.array_equal(gm, am), (si, n)
         # item 1 alone (two waves per row, whole rows, no interleaving), in a context of its own
         views, pts = scenes[1]
         k = keep[1]
@@ -363,6 +379,7 @@ def test_full_size_schedule_invariance():
     finally:
         c.close()
         c1.close()
+        c2.close()
 
 
 def test_batch_mixed_view_counts(ctx):
