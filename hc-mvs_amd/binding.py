@@ -53,6 +53,23 @@ class MeshSampleStats(C.Structure):
                 ("ms_device", C.c_float), ("device_bytes", C.c_uint64)]
 
 
+class ViewSelectParams(C.Structure):
+    _fields_ = [("n_min_views", C.c_int32), ("n_min_point_views", C.c_int32), ("n_max_views", C.c_int32), ("number_views", C.c_int32),
+                ("optim_angle_deg", C.c_float), ("min_angle_deg", C.c_float), ("max_angle_deg", C.c_float), ("min_area", C.c_float),
+                ("min_scale", C.c_float), ("max_scale", C.c_float), ("min_score_ratio", C.c_float), ("min_score", C.c_float)]
+
+
+class ViewSelection(C.Structure):
+    _U32, _F32 = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("n_seen", _U32), ("avg_depth", _F32), ("n_candidates", _U32), ("n_neighbors", _U32), ("n_srcs", _U32),
+                ("nb_id", _U32), ("nb_points", _U32), ("nb_scale", _F32), ("nb_angle", _F32), ("nb_area", _F32), ("nb_score", _F32), ("src_scale", _F32),
+                ("points_first", C.POINTER(C.c_uint64)), ("point_ids", _U32)]
+
+
+class ViewSelectStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("chunks", C.c_uint64), ("device_bytes", C.c_uint64), ("ms_device", C.c_float)]
+
+
 class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
@@ -78,7 +95,8 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
            "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_filter_sequence", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
-           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
+           "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_default_view_select_params", "hcmvs_select_views",
+           "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
 
@@ -173,6 +191,10 @@ def lib():
                                                C.POINTER(C.c_int32), u32p, u64p, C.POINTER(VisibilityStats)]
         L.hcmvs_sample_mesh.argtypes = [vp, C.c_uint32, fp, C.c_uint32, u32p, fp, u8p, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, fp, u32p, u8p,
                                         u64p, C.POINTER(MeshSampleStats)]
+        L.hcmvs_default_view_select_params.argtypes = [C.POINTER(ViewSelectParams)]
+        L.hcmvs_default_view_select_params.restype = None
+        L.hcmvs_select_views.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), dp, dp, dp, C.c_uint64, fp, u32p, u32p, C.POINTER(ViewSelectParams),
+                                         C.POINTER(ViewSelection), C.POINTER(ViewSelectStats)]
         L.hcmvs_resize_area_up.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
@@ -184,6 +206,17 @@ def lib():
 def default_params(**kw):
     p = Params()
     lib().hcmvs_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_view_select_params(**kw):
+    """hcmvs_default_view_select_params: the reference's defaults (DepthMap.cpp:72-86, SceneDensify.cpp:313-322), then the overrides"""
+    p = ViewSelectParams()
+    lib().hcmvs_default_view_select_params(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -532,6 +565,68 @@ class Context:
         self._chk(lib().hcmvs_sample_mesh(*head, cap, _f(xyz), fid.ctypes.data_as(u32), None if bgr is None else bgr.ctypes.data_as(u8), C.byref(n), C.byref(st)))
         assert n.value == cap
         return xyz, fid, bgr, {k: getattr(st, k) for k, _ in MeshSampleStats._fields_}
+
+    def select_views_raw(self, cameras, sizes, xyz, n_views, view_ids, number_views=5, with_points=True, **params):
+        """hcmvs_select_views as arrays: dict(status, n_seen, avg_depth, n_candidates, n_neighbors, n_srcs (n_images each), nb_id, nb_points,
+        nb_scale, nb_angle, nb_area, nb_score, src_scale ((n_images, n_max_views) each), points_first, point_ids (with_points), stats)"""
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nv = np.ascontiguousarray(n_views, np.uint32); vi = np.ascontiguousarray(view_ids, np.uint32)
+        if len(nv) != len(x) or int(nv.sum(dtype=np.uint64)) != len(vi):
+            raise ValueError("select_views: n_views does not describe view_ids")
+        if len(sizes) != len(cameras):
+            raise ValueError("select_views: one size per camera expected")
+        p = default_view_select_params(number_views=int(number_views), **params)
+        m = len(cameras)
+        wh = np.zeros((max(m, 1), 2), np.int32); K = np.zeros((max(m, 1), 9)); R = np.zeros((max(m, 1), 9)); Cc = np.zeros((max(m, 1), 3))
+        for j, cam in enumerate(cameras):
+            if cam is None or cam.get("K") is None or sizes[j] is None or not sizes[j][0]:
+                continue
+            wh[j] = sizes[j][0], sizes[j][1]
+            K[j] = np.asarray(cam["K"], np.float64).ravel(); R[j] = np.asarray(cam["R"], np.float64).ravel(); Cc[j] = np.asarray(cam["C"], np.float64)
+        M = max(int(p.n_max_views), 1)
+        res = dict(status=np.zeros(max(m, 1), np.int32))
+        for k in ("n_seen", "n_candidates", "n_neighbors", "n_srcs"):
+            res[k] = np.zeros(max(m, 1), np.uint32)
+        res["avg_depth"] = np.zeros(max(m, 1), np.float32)
+        for k in ("nb_id", "nb_points"):
+            res[k] = np.zeros((max(m, 1), M), np.uint32)
+        for k in ("nb_scale", "nb_angle", "nb_area", "nb_score", "src_scale"):
+            res[k] = np.zeros((max(m, 1), M), np.float32)
+        if with_points:
+            res["points_first"] = np.zeros(m + 1, np.uint64); res["point_ids"] = np.zeros(max(len(vi), 1), np.uint32)
+        sel = ViewSelection()
+        for k, a in res.items():
+            setattr(sel, k, a.ctypes.data_as(dict(ViewSelection._fields_)[k]))
+        st = ViewSelectStats()
+        u32, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        self._chk(lib().hcmvs_select_views(self._h, m, wh.ctypes.data_as(C.POINTER(C.c_int32)), K.ctypes.data_as(dp), R.ctypes.data_as(dp), Cc.ctypes.data_as(dp),
+                                           len(x), _f(x), nv.ctypes.data_as(u32), vi.ctypes.data_as(u32), C.byref(p), C.byref(sel), C.byref(st)))
+        n_ids = int(res["points_first"][m]) if with_points else 0
+        res = {k: a[:n_ids] if k == "point_ids" else a if k == "points_first" else a[:m] for k, a in res.items()}
+        res["stats"] = {k: getattr(st, k) for k, _ in ViewSelectStats._fields_}
+        return res
+
+    def select_views(self, cameras, sizes, xyz, n_views, view_ids, number_views=5, **params):
+        """DepthMapsData::SelectViews (SceneDensify.cpp:307-327) + the cut of DepthMapsData::InitViews (:362-367) for every image of a scene, on
+        the device (hcmvs_select_views).  cameras: one dict(K, R, C) per image at the image's size (None = uncalibrated); sizes: (width, height)
+        per image; the sparse cloud as CSR (xyz (n, 3) f32, n_views (n,), view_ids ascending per point); params: the fields of
+        hcmvs_view_select_params (n_max_views, min_angle_deg, ...).  Returns one entry per image: None when no views could be selected, else
+        dict(points [indices into xyz], neighbors [dict(id, points, scale, angle, area, score)] in decreasing score, srcs [(id, scale)],
+        avg_depth, status).  The counters and the per-image status / n_seen / n_candidates arrays are left in self.view_select_stats"""
+        r = self.select_views_raw(cameras, sizes, xyz, n_views, view_ids, number_views=number_views, with_points=True, **params)
+        self.view_select_stats = dict(r["stats"], status=r["status"], n_seen=r["n_seen"], n_candidates=r["n_candidates"], avg_depth=r["avg_depth"])
+        out = []
+        pf = r["points_first"]
+        for i in range(len(cameras)):
+            if r["status"][i] != 0:
+                out.append(None)
+                continue
+            nn, ns = int(r["n_neighbors"][i]), int(r["n_srcs"][i])
+            nbs = [dict(id=int(r["nb_id"][i, k]), points=int(r["nb_points"][i, k]), scale=float(r["nb_scale"][i, k]), angle=float(r["nb_angle"][i, k]),
+                        area=float(r["nb_area"][i, k]), score=float(r["nb_score"][i, k])) for k in range(nn)]
+            out.append(dict(points=[int(q) for q in r["point_ids"][int(pf[i]):int(pf[i + 1])]], neighbors=nbs,
+                            srcs=[(int(r["nb_id"][i, k]), float(r["src_scale"][i, k])) for k in range(ns)], avg_depth=float(r["avg_depth"][i]), status=0))
+        return out
 
     def postfilter(self, vid, order, n_min_views_fuse=2, depth_diff_threshold=0.01, normal_diff_deg=25.0, gap_size=7):
         """RemoveSmallSegments (fork version) + GapInterpolation on the registered device maps of view vid; returns pixels filled"""

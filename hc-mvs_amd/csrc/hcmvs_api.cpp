@@ -16,6 +16,7 @@
 #include "cloud_kernels.h"
 #include "vis_kernels.h"
 #include "mesh_kernels.h"
+#include "view_kernels.h"
 #include "dev_buf.h"
 
 #include <cmath>
@@ -1648,6 +1649,44 @@ int hcmvs_sample_mesh(hcmvs_ctx* c, uint32_t n_vertices, const float* vertices, 
 		stats->n_faces = n_faces; stats->n_zero_area_faces = st.zeroAreaFaces; stats->n_points = st.points; stats->area = st.area; stats->density = st.density;
 		stats->ms_device = st.ms; stats->device_bytes = st.deviceBytes;
 	}
+	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
+	return HCMVS_OK;
+}
+
+void hcmvs_default_view_select_params(hcmvs_view_select_params* p) {
+	if (!p) return;
+	const hcmvs::ViewSelectParams d; // DepthMap.cpp:72-86, SceneDensify.cpp:313-322
+	p->n_min_views = d.nMinViews; p->n_min_point_views = d.nMinPointViews; p->n_max_views = d.nMaxViews; p->number_views = d.numberViews;
+	p->optim_angle_deg = d.optimAngleDeg; p->min_angle_deg = d.minAngleDeg; p->max_angle_deg = d.maxAngleDeg; p->min_area = d.minArea;
+	p->min_scale = d.minScale; p->max_scale = d.maxScale; p->min_score_ratio = d.minScoreRatio; p->min_score = d.minScore;
+}
+
+int hcmvs_select_views(hcmvs_ctx* c, uint32_t n_images, const int32_t* wh, const double* K, const double* R, const double* C, uint64_t n, const float* xyz,
+                       const uint32_t* n_views, const uint32_t* view_ids, const hcmvs_view_select_params* params, const hcmvs_view_selection* o,
+                       hcmvs_view_select_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (stats) memset(stats, 0, sizeof *stats);
+	if (!params || !o || (n_images && (!wh || !K || !R || !C)) || (n && (!xyz || !n_views || !view_ids)))
+		return fail(c, HCMVS_ERR_INVALID, "select_views: null argument");
+	if (!o->status || !o->n_seen || !o->avg_depth || !o->n_candidates || !o->n_neighbors || !o->n_srcs || !o->nb_id || !o->nb_points || !o->nb_scale ||
+	    !o->nb_angle || !o->nb_area || !o->nb_score || !o->src_scale)
+		return fail(c, HCMVS_ERR_INVALID, "select_views: null output array");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	hcmvs::ViewSelectInput in;
+	in.nImages = n_images; in.wh = wh; in.K = K; in.R = R; in.C = C; in.nPoints = n; in.xyz = xyz; in.nViews = n_views; in.viewIds = view_ids;
+	hcmvs::ViewSelectParams p;
+	p.nMinViews = params->n_min_views; p.nMinPointViews = params->n_min_point_views; p.nMaxViews = params->n_max_views; p.numberViews = params->number_views;
+	p.optimAngleDeg = params->optim_angle_deg; p.minAngleDeg = params->min_angle_deg; p.maxAngleDeg = params->max_angle_deg; p.minArea = params->min_area;
+	p.minScale = params->min_scale; p.maxScale = params->max_scale; p.minScoreRatio = params->min_score_ratio; p.minScore = params->min_score;
+	hcmvs::ViewSelectOutput out;
+	out.status = o->status; out.nSeen = o->n_seen; out.avgDepth = o->avg_depth; out.nCandidates = o->n_candidates; out.nNeighbors = o->n_neighbors;
+	out.nSrcs = o->n_srcs; out.nbId = o->nb_id; out.nbPoints = o->nb_points; out.nbScale = o->nb_scale; out.nbAngle = o->nb_angle; out.nbArea = o->nb_area;
+	out.nbScore = o->nb_score; out.srcScale = o->src_scale; out.pointsFirst = (unsigned long long*)o->points_first; out.pointIds = o->point_ids;
+	hcmvs::ViewSelectCounters st;
+	std::string err;
+	const int rc = hcmvs::select_views_device(in, p, out, st, c, c->stream, err);
+	if (stats) { stats->pairs = st.pairs; stats->skipped = st.skipped; stats->chunks = st.chunks; stats->device_bytes = st.deviceBytes; stats->ms_device = st.ms; }
 	if (rc) return fail(c, rc == 1 ? HCMVS_ERR_INVALID : HCMVS_ERR_HIP, "%s", err.c_str());
 	return HCMVS_OK;
 }

@@ -18,6 +18,28 @@ def shard_order(order, world):
     return [list(order[r::world]) for r in range(world)]
 
 
+def plan_order(ids, n_neighbors):
+    """the fusion order (SceneDensify.cpp:3285-3302): the images `ids` by decreasing number of neighbours, equal counts in the order
+    given (a stable sort).  n_neighbors: {id: count} or a sequence indexed by id"""
+    return sorted(ids, key=lambda i: -int(n_neighbors[i]))
+
+
+def plan_scene(ctx, cameras, sizes, xyz, n_views, view_ids, number_views=5, **params):
+    """What densify_scene expects from the caller, from the cameras and the sparse cloud alone: binding.Context.select_views
+    (DepthMapsData::SelectViews + the InitViews cut, on the device) for every image, then the fusion order.  Arguments as select_views.
+    Returns (srcs, neighbors, order, points) over the images that got views: srcs {id: [source view ids]}, neighbors {id: [neighbour
+    ids, decreasing score]}, order = plan_order of those images, points {id: indices into xyz of the image's points} -- xyz[points[id]]
+    is what triangulate_init takes.  A source view whose scale differs from 1 is reported by select_views (srcs as (id, scale));
+    densify_scene estimates against the views as uploaded."""
+    import numpy as np
+    sel = ctx.select_views(cameras, sizes, xyz, n_views, view_ids, number_views=number_views, **params)
+    done = [i for i, s in enumerate(sel) if s is not None]
+    srcs = {i: [j for j, _ in sel[i]["srcs"]] for i in done}
+    neighbors = {i: [n["id"] for n in sel[i]["neighbors"]] for i in done}
+    points = {i: np.asarray(sel[i]["points"], np.int64) for i in done}
+    return srcs, neighbors, plan_order(done, {i: len(neighbors[i]) for i in done}), points
+
+
 def slab_index(k, world, n_local):
     """row of order position k in the gathered [world * n_local, ...] tensor (rank-major)"""
     return (k % world) * n_local + k // world

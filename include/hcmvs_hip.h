@@ -415,6 +415,67 @@ int hcmvs_sample_mesh(hcmvs_ctx* ctx, uint32_t n_vertices, const float* vertices
                       uint64_t capacity, float* xyz_or_null, uint32_t* face_of_point_or_null, uint8_t* bgr_or_null, uint64_t* n_points,
                       hcmvs_mesh_sample_stats* stats_or_null);
 
+/* the parameters of hcmvs_select_views; hcmvs_default_view_select_params fills the reference's defaults */
+typedef struct {
+	int32_t n_min_views;        /* OPTDENSE::nMinViews 2: neighbours an image needs before the filter (at most calibrated images - 1) */
+	int32_t n_min_point_views;  /* views a point needs to enter an image's points list: nMinViewsTrustPoint > 1 ? it : 2 -> 2 */
+	int32_t n_max_views;        /* OPTDENSE::nMaxViews 12: neighbours kept per image, 1..64 */
+	int32_t number_views;       /* --number-views 5: source views per image, 0 = all neighbours */
+	float optim_angle_deg;      /* OPTDENSE::fOptimAngle 10 */
+	float min_angle_deg;        /* OPTDENSE::fMinAngle 3 */
+	float max_angle_deg;        /* OPTDENSE::fMaxAngle 65 */
+	float min_area;             /* OPTDENSE::fMinArea 0.01 */
+	float min_scale;            /* 0.2 (SceneDensify.cpp:319) */
+	float max_scale;            /* 3.2 */
+	float min_score_ratio;      /* OPTDENSE::fViewMinScoreRatio 0.3 */
+	float min_score;            /* OPTDENSE::fViewMinScore 0 */
+} hcmvs_view_select_params;
+void hcmvs_default_view_select_params(hcmvs_view_select_params* p);
+
+/* what hcmvs_select_views writes: host arrays of the caller, M = n_max_views.  The per-neighbour rows are in decreasing score (ties by
+ * ascending image id); the source views of image i are its first n_srcs[i] neighbours.  Rows past n_neighbors[i] are zero. */
+typedef struct {
+	int32_t* status;          /* n_images: 0 selected; 1 SelectNeighborViews false (<= 3 points, or fewer than min(n_min_views, calibrated - 1)
+	                             candidates); 2 no candidate survives FilterNeighborViews, or no source view is left; 3 uncalibrated */
+	uint32_t* n_seen;         /* n_images: points seen by the image (nPoints) */
+	float* avg_depth;         /* n_images: Image::avgDepth (Scene.cpp:575, :603); 0 for an image that sees no point */
+	uint32_t* n_candidates;   /* n_images: neighbours before the filter */
+	uint32_t* n_neighbors;    /* n_images: neighbours kept, <= M; 0 unless status is 0 or 2 */
+	uint32_t* n_srcs;         /* n_images: source views, <= n_neighbors; 0 unless status is 0 */
+	uint32_t* nb_id;          /* n_images * M */
+	uint32_t* nb_points;      /* n_images * M: points shared */
+	float* nb_scale;          /* n_images * M: average footprint ratio */
+	float* nb_angle;          /* n_images * M: average viewing angle, radians */
+	float* nb_area;           /* n_images * M: covered area = occupied cells / 256 */
+	float* nb_score;          /* n_images * M */
+	float* src_scale;         /* n_images * M: of the source views; 1 unless |nb_scale - 1| >= 0.15 (the view is resampled, DepthMap.h:233-238) */
+	uint64_t* points_first;   /* n_images + 1, or NULL: the points lists (DepthData::points) as CSR ... */
+	uint32_t* point_ids;      /* ... into point_ids (the sum of n_views entries always suffices), or NULL; ascending per image */
+} hcmvs_view_selection;
+/* counters of the last hcmvs_select_views call */
+typedef struct {
+	uint64_t pairs;          /* ordered (image, other image, point) records scored */
+	uint64_t skipped;        /* view entries naming an image >= n_images or an uncalibrated one: skipped */
+	uint64_t chunks;         /* ranges of images the call was split into */
+	uint64_t device_bytes;   /* device memory the call allocated */
+	float ms_device;         /* device time from the first kernel to the last (HIP events) */
+} hcmvs_view_select_stats;
+/* DepthMapsData::SelectViews (SceneDensify.cpp:307-327: Scene::SelectNeighborViews, Scene.cpp:545-661, then Scene::FilterNeighborViews,
+ * :665-678) and the cut of DepthMapsData::InitViews (SceneDensify.cpp:362-367) for EVERY image of a scene in one call, on the device: the
+ * sparse cloud is walked once, not once per image.  Cameras as in hcmvs_point_cloud_filter (wh: width, height, width 0 = uncalibrated;
+ * K, R 9 f64 each at that size; C 3 f64; 1 <= n_images < 65 536); the sparse cloud as CSR (xyz n_points*3, n_views, view_ids strictly
+ * ascending per point, fewer than 2^32 entries).  The arithmetic is stated in DESIGN.md section 5 (D12): float32 where the reference
+ * computes in float32, every sum taken sequentially in ascending point index, so the call is bit-identical run to run and does not depend
+ * on how it was split.  A view entry naming an image >= n_images or an uncalibrated one is skipped for scoring (stats->skipped) but still
+ * counts towards the point's number of views.  HCMVS_ERR_INVALID before anything reaches the device, with a message naming the first
+ * offender: a coordinate or an entry of a calibrated camera that is not finite, view ids that are not strictly ascending, n_max_views
+ * outside 1..64, n_images 0 or >= 65 536, 2^32 view entries or more.  n_points == 0 succeeds: every calibrated image gets status 1.
+ * The records of the ordered pairs (32 B each with the sort's buffers) are checked against the free device memory; beyond half of it the
+ * images are processed in ranges (HCMVS_SELECT_CHUNK=<images>, read at every call, forces the size of a range). */
+int hcmvs_select_views(hcmvs_ctx* ctx, uint32_t n_images, const int32_t* wh, const double* K, const double* R, const double* C,
+                       uint64_t n_points, const float* xyz, const uint32_t* n_views, const uint32_t* view_ids,
+                       const hcmvs_view_select_params* params, const hcmvs_view_selection* out, hcmvs_view_select_stats* stats_or_null);
+
 #ifdef __cplusplus
 }
 #endif
