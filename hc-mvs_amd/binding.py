@@ -70,6 +70,11 @@ class ViewSelectStats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("chunks", C.c_uint64), ("device_bytes", C.c_uint64), ("ms_device", C.c_float)]
 
 
+class InitStats(C.Structure):
+    _fields_ = [("n_used", C.c_uint64), ("n_faces", C.c_uint64), ("n_tile_entries", C.c_uint64), ("covered_pixels", C.c_uint64),
+                ("cover_hits", C.c_uint64), ("ms_host", C.c_float), ("ms_device", C.c_float), ("device_bytes", C.c_uint64)]
+
+
 class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
@@ -93,7 +98,8 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_synchronize", "hcmvs_upload_view", "hcmvs_set_view_device", "hcmvs_release_view", "hcmvs_rescale_view", "hcmvs_get_view_info",
            "hcmvs_get_view_gray",
            "hcmvs_get_gradient_map", "hcmvs_estimate", "hcmvs_estimate_device", "hcmvs_estimate_batch_device", "hcmvs_get_stats",
-           "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
+           "hcmvs_splat_init", "hcmvs_splat_points", "hcmvs_triangulate_init", "hcmvs_triangulate_points",
+           "hcmvs_triangulate_init_device", "hcmvs_splat_init_device", "hcmvs_get_init_stats", "hcmvs_set_depthmap", "hcmvs_set_depthmap_device", "hcmvs_get_depthmap",
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_filter_sequence", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
            "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_default_view_select_params", "hcmvs_select_views",
            "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
@@ -171,6 +177,9 @@ def lib():
         L.hcmvs_triangulate_init.argtypes = [vp, C.c_uint32, fp, C.c_int32, C.c_float, C.c_int32, fp, fp, fp, fp]
         dp = C.POINTER(C.c_double)
         L.hcmvs_triangulate_points.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, fp, C.c_int32, C.c_float, C.c_int32, fp, fp, fp, fp]
+        L.hcmvs_triangulate_init_device.argtypes = [vp, C.c_uint32, fp, C.c_int32, C.c_float, C.c_int32, vp, vp, fp, fp]
+        L.hcmvs_splat_init_device.argtypes = [vp, C.c_uint32, fp, C.c_int32, vp, vp, fp, fp]
+        L.hcmvs_get_init_stats.argtypes = [vp, C.POINTER(InitStats)]
         u64p = C.POINTER(C.c_uint64)
         L.hcmvs_set_depthmap.argtypes = [vp, C.c_uint32, fp, fp, fp, C.c_float, C.c_float]
         L.hcmvs_set_depthmap_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_float]
@@ -350,6 +359,30 @@ class Context:
         self._chk(lib().hcmvs_triangulate_init(self._h, vid, _f(pts), len(pts), C.c_float(avg_depth), int(add_corners), _f(depth),
                                                _f(normal), C.byref(dmin), C.byref(dmax)))
         return depth, normal, dmin.value, dmax.value
+
+    def triangulate_init_device(self, vid, points_xyz, d_depth_ptr, d_normal_ptr, avg_depth=0.0, add_corners=True):
+        """triangulate_init with the pixel loop on the device: points_xyz is a host array (n, 3), d_depth_ptr (h*w f32) and d_normal_ptr
+        (h*w*3 f32) are device addresses, every pixel of which is written on the context's stream (not synchronised; ordered before a
+        following estimate*_device).  Bit-identical to triangulate_init.  Returns (d_min, d_max)."""
+        pts = np.ascontiguousarray(points_xyz, np.float32).reshape(-1, 3)
+        dmin = C.c_float(); dmax = C.c_float()
+        self._chk(lib().hcmvs_triangulate_init_device(self._h, vid, _f(pts), len(pts), C.c_float(avg_depth), int(add_corners),
+                                                      C.c_void_p(d_depth_ptr), C.c_void_p(d_normal_ptr), C.byref(dmin), C.byref(dmax)))
+        return dmin.value, dmax.value
+
+    def splat_init_device(self, vid, points_xyz, d_depth_ptr, d_normal_ptr):
+        """splat_init on the device, arguments and return value as triangulate_init_device; the normals are 0 everywhere"""
+        pts = np.ascontiguousarray(points_xyz, np.float32).reshape(-1, 3)
+        dmin = C.c_float(); dmax = C.c_float()
+        self._chk(lib().hcmvs_splat_init_device(self._h, vid, _f(pts), len(pts), C.c_void_p(d_depth_ptr), C.c_void_p(d_normal_ptr),
+                                                C.byref(dmin), C.byref(dmax)))
+        return dmin.value, dmax.value
+
+    def init_stats(self):
+        """hcmvs_get_init_stats: the counters of the last *_init_device call, as a dict; waits for the context's stream"""
+        st = InitStats()
+        self._chk(lib().hcmvs_get_init_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in InitStats._fields_}
 
     def estimate(self, ref_id, src_ids, params, d_min, d_max, depth, normal, conf=None):
         """EstimateDepthMap on host maps (copied); returns (depth, normal, conf)."""

@@ -17,6 +17,7 @@
 #include "vis_kernels.h"
 #include "mesh_kernels.h"
 #include "view_kernels.h"
+#include "init_kernels.h"
 #include "dev_buf.h"
 
 #include <cmath>
@@ -111,6 +112,15 @@ struct hcmvs_ctx final : Reclaimer {
 	hipEvent_t upEv[2] = {nullptr, nullptr};
 	char* pinned = nullptr; size_t capPinned = 0; // page-locked staging of the host-buffer uploads (a pageable hipMemcpy crawls at ~1.3 GB/s here)
 	int wavesPerRow = 0; // HCMVS_WAVES_PER_ROW: 1..4 requested, 0 = automatic by the batch's rows (sweep_plan.h)
+	// hcmvs_*_init_device: the counters, the table and the tile lists of a call (init_plan.h InitLayout) on the device, and their page-locked
+	// staging; initCopied marks the copy out of the staging, which is rewritten only after it
+	DevBuf initBuf{this};
+	char* initPinned = nullptr; size_t capInitPinned = 0;
+	hipEvent_t initCopied = nullptr;
+	bool initInFlight = false;
+	hipEvent_t initEv[2] = {nullptr, nullptr};
+	hcmvs_init_stats initStats = {};
+	bool haveInitStats = false;
 
 	bool reclaim() override {
 		if (!pfState.capacity()) return false;
@@ -254,6 +264,9 @@ void hcmvs_destroy(hcmvs_ctx* c) {
 	for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	for (auto& e : c->upEv) if (e) (void)hipEventDestroy(e);
+	if (c->initPinned) (void)hipHostFree(c->initPinned);
+	if (c->initCopied) (void)hipEventDestroy(c->initCopied);
+	for (auto& e : c->initEv) if (e) (void)hipEventDestroy(e);
 	if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
 	delete c;
 }
@@ -830,25 +843,18 @@ int hcmvs_estimate(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* src_ids, int32
 int hcmvs_splat_points(int32_t W, int32_t H, const double K[9], const double R[9], const double C[3], const float* pts, int32_t n, float* depth,
                        float* normal, float* d_min, float* d_max) {
 	if (!K || !R || !C || !pts || !depth || !normal || !d_min || !d_max || n < 1 || W < 1 || H < 1) return HCMVS_ERR_INVALID;
+	std::vector<InitSplat> table; // the per-point set-up (init_plan.h); the device form rasterises the same table
+	float dmin, dmax;
+	splat_plan(K, R, C, pts, n, table, &dmin, &dmax);
 	memset(depth, 0, sizeof(float) * (size_t)W * H);
-	float dmin = 3.402823466e+38f, dmax = 0.f;
-	for (int i = 0; i < n; ++i) { // SceneDensify.cpp:789-806
-		const double X[3] = {pts[3 * i] - C[0], pts[3 * i + 1] - C[1], pts[3 * i + 2] - C[2]};
-		double cam[3];
-		for (int r = 0; r < 3; ++r) cam[r] = R[r * 3] * X[0] + R[r * 3 + 1] * X[1] + R[r * 3 + 2] * X[2];
-		const int x = (int)std::floor(K[2] + K[0] * (cam[0] / cam[2]) + .5);
-		const int y = (int)std::floor(K[5] + K[4] * (cam[1] / cam[2]) + .5);
-		const float d = (float)cam[2];
-		const int sx = x - 2 > 0 ? x - 2 : 0, sy = y - 2 > 0 ? y - 2 : 0;
-		const int ex = x + 2 < W - 1 ? x + 2 : W - 1, ey = y + 2 < H - 1 ? y + 2 : H - 1;
-		for (int yy = sy; yy <= ey; ++yy)
-			for (int xx = sx; xx <= ex; ++xx) {
-				depth[(size_t)yy * W + xx] = d;
+	for (const InitSplat& p : table) { // SceneDensify.cpp:789-806
+		const InitBox bx = splat_box(p, W, H);
+		for (int yy = bx.y0; yy < bx.y1; ++yy)
+			for (int xx = bx.x0; xx < bx.x1; ++xx) {
+				depth[(size_t)yy * W + xx] = p.d;
 				float* nn = normal + 3 * ((size_t)yy * W + xx);
 				nn[0] = nn[1] = nn[2] = 0.f;
 			}
-		if (dmin > d) dmin = d;
-		if (dmax < d) dmax = d;
 	}
 	*d_min = dmin * 0.9f;
 	*d_max = dmax * 1.1f;
@@ -882,6 +888,137 @@ int hcmvs_triangulate_init(hcmvs_ctx* c, uint32_t id, const float* pts, int32_t 
 	const View& v = *pv;
 	if (hcmvs_triangulate_points(v.w, v.h, v.K, v.R, v.C, pts, n, avg_depth, add_corners, depth, normal, d_min, d_max) != HCMVS_OK)
 		return fail(c, HCMVS_ERR_INVALID, "triangulate_init: no sparse point in front of view %u", id);
+	return HCMVS_OK;
+}
+
+// what the two device initialisations refuse before any work: the view, or null with the failure recorded
+static const View* init_device_args(hcmvs_ctx* c, const char* who, uint32_t id, const float* pts, int32_t n, const float* d_depth, const float* d_normal,
+                                    const float* d_min, const float* d_max) {
+	if (!pts || !d_depth || !d_normal || !d_min || !d_max || n < 1) { fail(c, HCMVS_ERR_INVALID, "%s: bad arguments (null pointer or n_points < 1)", who); return nullptr; }
+	const View* v = find_view(c, who, id);
+	if (!v) return nullptr;
+	for (size_t i = 0; i < (size_t)n * 3; ++i)
+		if (!std::isfinite(pts[i])) { fail(c, HCMVS_ERR_INVALID, "%s: coordinate %d of point %zu is not finite", who, (int)(i % 3), i / 3); return nullptr; }
+	return v;
+}
+
+// The device half of the two initialisations: the table (tableBytes at `table`) and the tile lists go through the context's page-locked
+// staging into its grow-only buffer, then one kernel writes every pixel of the caller's maps.  Enqueued on the context's stream, not
+// synchronised; the staging is rewritten only after the event that marks its copy.
+static int init_enqueue(hcmvs_ctx* c, const char* who, bool triangles, const View& v, const void* table, size_t tableBytes, const InitTiling& t,
+                        float fx, float fy, float cx, float cy, float* d_depth, float* d_normal) {
+	HIPCHK(c, hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	const size_t nTiles = (size_t)t.tilesX * t.tilesY;
+	const InitLayout l = init_layout(tableBytes, nTiles, t.items.size());
+	if (!c->initCopied) HIPCHK(c, hipEventCreateWithFlags(&c->initCopied, hipEventDisableTiming));
+	for (auto& e : c->initEv) if (!e) HIPCHK(c, hipEventCreate(&e));
+	if (c->initInFlight) { HIPCHK(c, hipEventSynchronize(c->initCopied)); c->initInFlight = false; } // the previous call's tables have left the staging
+	if (c->capInitPinned < l.bytes) {
+		if (c->initPinned) (void)hipHostFree(c->initPinned);
+		c->initPinned = nullptr; c->capInitPinned = 0;
+		const size_t cap = std::max(l.bytes + l.bytes / 2, (size_t)1 << 20);
+		if (hipHostMalloc((void**)&c->initPinned, cap, hipHostMallocDefault) != hipSuccess) {
+			(void)hipGetLastError();
+			c->initPinned = nullptr;
+			return fail(c, HCMVS_ERR_HIP, "%s: no page-locked staging of %zu bytes", who, cap);
+		}
+		c->capInitPinned = cap;
+	}
+	HIPCHK(c, c->initBuf.reserve(l.bytes, s));
+	char* h = c->initPinned;
+	memset(h + l.counters, 0, 2 * sizeof(uint64_t));
+	if (tableBytes) memcpy(h + l.table, table, tableBytes);
+	memcpy(h + l.first, t.first.data(), (nTiles + 1) * sizeof(uint32_t));
+	if (!t.items.empty()) memcpy(h + l.items, t.items.data(), t.items.size() * sizeof(uint32_t));
+	char* d = c->initBuf.get();
+	HIPCHK(c, hipMemcpyAsync(d, h, l.bytes, hipMemcpyHostToDevice, s)); // same stream: the previous call's kernel is done with the buffer
+	HIPCHK(c, hipEventRecord(c->initCopied, s));
+	c->initInFlight = true;
+	InitRaster r;
+	r.W = v.w; r.H = v.h; r.tilesX = t.tilesX; r.tilesY = t.tilesY;
+	r.fx = fx; r.fy = fy; r.cx = cx; r.cy = cy;
+	r.first = (const uint32_t*)(d + l.first); r.items = (const uint32_t*)(d + l.items);
+	r.depth = d_depth; r.normal = d_normal;
+	r.counters = (unsigned long long*)(d + l.counters);
+	HIPCHK(c, hipEventRecord(c->initEv[0], s));
+	if (triangles) launch_init_triangles(r, (const InitFace*)(d + l.table), s);
+	else launch_init_splats(r, (const InitSplatBox*)(d + l.table), s);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(c->initEv[1], s));
+	c->initStats.n_tile_entries = t.items.size();
+	c->initStats.device_bytes = l.bytes;
+	c->haveInitStats = true;
+	return HCMVS_OK;
+}
+
+static float ms_since(std::chrono::steady_clock::time_point t0) {
+	return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int hcmvs_triangulate_init_device(hcmvs_ctx* c, uint32_t id, const float* pts, int32_t n, float avg_depth, int32_t add_corners, float* d_depth,
+                                  float* d_normal, float* d_min, float* d_max) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const View* pv = init_device_args(c, "triangulate_init_device", id, pts, n, d_depth, d_normal, d_min, d_max);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
+	const auto t0 = std::chrono::steady_clock::now();
+	InitTriTable tab;
+	if (!hcmvs::triangulate_plan(v.w, v.h, v.K, v.R, v.C, pts, n, avg_depth, add_corners != 0, tab))
+		return fail(c, HCMVS_ERR_INVALID, "triangulate_init_device: no sparse point in front of view %u", id);
+	InitTiling tiles;
+	if (!bin_tiles(v.w, v.h, tab.faces.size(), [&](size_t i) { return face_box(tab.faces[i]); }, tiles))
+		return fail(c, HCMVS_ERR_INVALID, "triangulate_init_device: the tile lists of view %u pass 2^31 entries", id);
+	c->haveInitStats = false;
+	c->initStats = hcmvs_init_stats();
+	c->initStats.n_used = (uint64_t)tab.nUsed; c->initStats.n_faces = tab.faces.size();
+	c->initStats.ms_host = ms_since(t0);
+	const int rc = init_enqueue(c, "triangulate_init_device", true, v, tab.faces.data(), tab.faces.size() * sizeof(InitFace), tiles, tab.fx, tab.fy, tab.cx,
+	                            tab.cy, d_depth, d_normal);
+	if (rc) return rc;
+	*d_min = tab.lo * 0.9f; // SceneDensify.cpp:524-525
+	*d_max = tab.hi * 1.1f;
+	return HCMVS_OK;
+}
+
+int hcmvs_splat_init_device(hcmvs_ctx* c, uint32_t id, const float* pts, int32_t n, float* d_depth, float* d_normal, float* d_min, float* d_max) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const View* pv = init_device_args(c, "splat_init_device", id, pts, n, d_depth, d_normal, d_min, d_max);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
+	const auto t0 = std::chrono::steady_clock::now();
+	std::vector<InitSplat> tab;
+	float dmin, dmax;
+	splat_plan(v.K, v.R, v.C, pts, n, tab, &dmin, &dmax);
+	std::vector<InitSplatBox> boxes(tab.size());
+	for (size_t i = 0; i < tab.size(); ++i) {
+		const InitBox b = splat_box(tab[i], v.w, v.h);
+		boxes[i] = {b.x0, b.y0, b.x1, b.y1, tab[i].d};
+	}
+	InitTiling tiles;
+	if (!bin_tiles(v.w, v.h, boxes.size(), [&](size_t i) { return InitBox{boxes[i].x0, boxes[i].y0, boxes[i].x1, boxes[i].y1}; }, tiles))
+		return fail(c, HCMVS_ERR_INVALID, "splat_init_device: the tile lists of view %u pass 2^31 entries", id);
+	c->haveInitStats = false;
+	c->initStats = hcmvs_init_stats();
+	c->initStats.n_used = tab.size();
+	c->initStats.ms_host = ms_since(t0);
+	const int rc = init_enqueue(c, "splat_init_device", false, v, boxes.data(), boxes.size() * sizeof(InitSplatBox), tiles, 0.f, 0.f, 0.f, 0.f, d_depth, d_normal);
+	if (rc) return rc;
+	*d_min = dmin * 0.9f;
+	*d_max = dmax * 1.1f;
+	return HCMVS_OK;
+}
+
+int hcmvs_get_init_stats(hcmvs_ctx* c, hcmvs_init_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	if (!c->haveInitStats) return fail(c, HCMVS_ERR_INVALID, "get_init_stats: no device initialisation has run on this context");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	unsigned long long counters[2] = {0, 0};
+	HIPCHK(c, hipMemcpy(counters, c->initBuf.get(), sizeof counters, hipMemcpyDeviceToHost)); // InitLayout: the counters open the buffer
+	HIPCHK(c, hipEventElapsedTime(&c->initStats.ms_device, c->initEv[0], c->initEv[1]));
+	c->initStats.covered_pixels = counters[0]; c->initStats.cover_hits = counters[1];
+	*out = c->initStats;
 	return HCMVS_OK;
 }
 

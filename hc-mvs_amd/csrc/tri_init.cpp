@@ -5,6 +5,8 @@
  * this step with CGAL on the CPU once per image, before the first sweep; here the triangulation is a plain
  * Bowyer-Watson insertion that starts from the image rectangle (the four corner support points of
  * OPTDENSE::bAddCorners are its convex hull), so no CGAL and no points at infinity are needed.
+ * triangulate_plan is all of it up to the pixel loop and yields the face table of init_plan.h; raster_triangles is the pixel loop on the
+ * host, init_kernels.hip the same loop on the device.
  */
 #include "tri_init.h"
 
@@ -113,8 +115,9 @@ inline void i2c(const double* K, double x, double y, double z, double* o) { // C
 
 } // namespace
 
-bool triangulate_init(int W, int H, const double* K, const double* R, const double* C, const float* xyz, int n, float avgDepth,
-                      bool addCorners, float* depth, float* normal, float* dMin, float* dMax) {
+bool triangulate_plan(int W, int H, const double* K, const double* R, const double* C, const float* xyz, int n, float avgDepth,
+                      bool addCorners, InitTriTable& out) {
+	out = InitTriTable();
 	// DepthMap.cpp:1796-1808: project, keep (x/z, y/z, z); CGAL keeps the first of two points at the same position
 	double Pm[12];
 	for (int r = 0; r < 3; ++r) {
@@ -200,11 +203,12 @@ bool triangulate_init(int W, int H, const double* K, const double* R, const doub
 		}
 	}
 
-	// DepthMap.cpp:1886-1931: one plane per face, rasterised with the 28.4 fixed-point half-space rule
-	std::fill(depth, depth + (size_t)W * H, 0.f);
-	std::fill(normal, normal + (size_t)W * H * 3, 0.f);
-	const float fx = (float)K[0], fy = (float)K[4], cx = (float)K[2], cy = (float)K[5];
-	for (const Tri& T : tris) {
+	// DepthMap.cpp:1886-1931: one plane per face, with what the 28.4 fixed-point half-space rule needs of it
+	out.nUsed = nUsed; out.lo = lo; out.hi = hi;
+	out.fx = (float)K[0]; out.fy = (float)K[4]; out.cx = (float)K[2]; out.cy = (float)K[5];
+	out.faces.reserve(tris.size());
+	for (size_t ti = 0; ti < tris.size(); ++ti) {
+		const Tri& T = tris[ti];
 		if (!addCorners && (T.v[0] < 4 || T.v[1] < 4 || T.v[2] < 4)) continue;
 		float c[3][3];
 		for (int k = 0; k < 3; ++k) { // Point3f(i_k) then TransformPointI2C
@@ -217,7 +221,8 @@ bool triangulate_init(int W, int H, const double* K, const double* R, const doub
 		if (!(nl > 0.f)) continue;
 		for (float& v : nn) v /= nl;
 		const float dn = 1.f / (nn[0] * c[0][0] + nn[1] * c[0][1] + nn[2] * c[0][2]);
-		const float np[3] = {nn[0] * dn, nn[1] * dn, nn[2] * dn};
+		InitFace f;
+		for (int k = 0; k < 3; ++k) { f.nn[k] = nn[k]; f.np[k] = nn[k] * dn; }
 		// the reference passes the counter-clockwise face reversed: (v2, v1, v0)
 		const P3 &v1 = pts[T.v[2]], &v2 = pts[T.v[1]], &v3 = pts[T.v[0]];
 		auto r16 = [](double v) { return (int64_t)std::floor(16.0 * (double)(float)v + 0.5); }; // ROUND2INT(16 * v), v as float
@@ -231,8 +236,25 @@ bool triangulate_init(int W, int H, const double* K, const double* R, const doub
 		if (DY23 < 0 || (DY23 == 0 && DX23 > 0)) C2++;
 		if (DY31 < 0 || (DY31 == 0 && DX31 > 0)) C3++;
 		const int yEnd = miny + ((maxy - miny + 7) / 8) * 8, xEnd = minx + ((maxx - minx + 7) / 8) * 8; // whole 8x8 blocks
-		for (int y = std::max(miny, 0); y < std::min(yEnd, H); ++y)
-			for (int x = std::max(minx, 0); x < std::min(xEnd, W); ++x) {
+		f.X[0] = X1; f.X[1] = X2; f.X[2] = X3; f.Y[0] = Y1; f.Y[1] = Y2; f.Y[2] = Y3;
+		f.C[0] = C1; f.C[1] = C2; f.C[2] = C3;
+		f.x0 = std::max(minx, 0); f.y0 = std::max(miny, 0); f.x1 = std::min(xEnd, W); f.y1 = std::min(yEnd, H);
+		f.index = (int32_t)ti; f.pad_ = 0;
+		out.faces.push_back(f);
+	}
+	return true;
+}
+
+void raster_triangles(const InitTriTable& t, int W, int H, float* depth, float* normal) {
+	std::fill(depth, depth + (size_t)W * H, 0.f);
+	std::fill(normal, normal + (size_t)W * H * 3, 0.f);
+	const float fx = t.fx, fy = t.fy, cx = t.cx, cy = t.cy;
+	for (const InitFace& f : t.faces) {
+		const int64_t DX12 = f.X[0] - f.X[1], DX23 = f.X[1] - f.X[2], DX31 = f.X[2] - f.X[0], DY12 = f.Y[0] - f.Y[1], DY23 = f.Y[1] - f.Y[2], DY31 = f.Y[2] - f.Y[0];
+		const int64_t C1 = f.C[0], C2 = f.C[1], C3 = f.C[2];
+		const float np[3] = {f.np[0], f.np[1], f.np[2]}, nn[3] = {f.nn[0], f.nn[1], f.nn[2]};
+		for (int y = f.y0; y < f.y1; ++y)
+			for (int x = f.x0; x < f.x1; ++x) {
 				const int64_t xs = (int64_t)x << 4, ys = (int64_t)y << 4;
 				if (!(C1 + DX12 * ys - DY12 * xs > 0 && C2 + DX23 * ys - DY23 * xs > 0 && C3 + DX31 * ys - DY31 * xs > 0)) continue;
 				const float X0x = ((float)x - cx) / fx, X0y = ((float)y - cy) / fy; // TransformPointI2C(Point2f)
@@ -243,7 +265,14 @@ bool triangulate_init(int W, int H, const double* K, const double* R, const doub
 				o[0] = nn[0]; o[1] = nn[1]; o[2] = nn[2];
 			}
 	}
-	*dMin = lo; *dMax = hi;
+}
+
+bool triangulate_init(int W, int H, const double* K, const double* R, const double* C, const float* xyz, int n, float avgDepth,
+                      bool addCorners, float* depth, float* normal, float* dMin, float* dMax) {
+	InitTriTable t;
+	if (!triangulate_plan(W, H, K, R, C, xyz, n, avgDepth, addCorners, t)) return false;
+	raster_triangles(t, W, H, depth, normal);
+	*dMin = t.lo; *dMax = t.hi;
 	return true;
 }
 

@@ -28,8 +28,8 @@ def plan_scene(ctx, cameras, sizes, xyz, n_views, view_ids, number_views=5, **pa
     """What densify_scene expects from the caller, from the cameras and the sparse cloud alone: binding.Context.select_views
     (DepthMapsData::SelectViews + the InitViews cut, on the device) for every image, then the fusion order.  Arguments as select_views.
     Returns (srcs, neighbors, order, points) over the images that got views: srcs {id: [source view ids]}, neighbors {id: [neighbour
-    ids, decreasing score]}, order = plan_order of those images, points {id: indices into xyz of the image's points} -- xyz[points[id]]
-    is what triangulate_init takes.  A source view whose scale differs from 1 is reported by select_views (srcs as (id, scale));
+    ids, decreasing score]}, order = plan_order of those images, points {id: indices into xyz of the image's points} -- densify_scene
+    takes init = {id: dict(points=xyz[points[id]])} and triangulates on the rank's device.  A source view whose scale differs from 1 is reported by select_views (srcs as (id, scale));
     densify_scene estimates against the views as uploaded."""
     import numpy as np
     sel = ctx.select_views(cameras, sizes, xyz, n_views, view_ids, number_views=number_views, **params)
@@ -138,7 +138,11 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     srcs:      {image id: [source view ids]}            (DepthMapsData::InitViews, SceneDensify.cpp:336-397)
     neighbors: {image id: [neighbour ids]}              (DepthData::neighbors, decreasing importance)
     order:     fusion order, best connected first       (SceneDensify.cpp:3302)
-    init:      {image id: (depth0 (H,W), normal0 (H,W,3), d_min, d_max)} numpy, at least for this rank's images
+    init:      {image id: entry}, at least for this rank's images.  An entry is (depth0 (H,W), normal0 (H,W,3), d_min, d_max) numpy -- maps
+               made on the host, copied in -- or a dict: dict(points=xyz (n,3) [, avg_depth=, add_corners=]) for the triangulation,
+               dict(splat=xyz (n,3)) for the splat; the rank's context then rasterises the maps straight into its slab
+               (binding.Context.triangulate_init_device / splat_init_device: only the face / point tables travel) and d_min, d_max come
+               from that call.  Same bits either way; the two kinds may be mixed
     params:    binding.Params of the estimate; it_external / n_external_iters are set here
     masks:     optional {image id: (labels (h, w) u16 of any size, [ignored labels])}: --ignore-mask-label for those reference images
                (binding.Context.set_ignore_mask on the rank that estimates them)
@@ -180,10 +184,23 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             ctx.set_ignore_mask(img, masks[img][0], masks[img][1])
     slabs = torch.zeros(n_local, FLOATS_PER_PIXEL * hw, dtype=torch.float32, device=dev)
     rng = torch.zeros(n_local, 2, dtype=torch.float32, device=dev)      # (d_min, d_max) travel with the maps
+    zeroed = False      # the context writes a dict entry's row on its own stream: torch's zero fill of the slabs must have landed first
     for j, img in enumerate(mine):
-        d0, n0, dmin, dmax = init[img]
-        slabs[j, :hw] = torch.from_numpy(np.ascontiguousarray(d0, np.float32)).reshape(-1).to(dev)
-        slabs[j, hw:4 * hw] = torch.from_numpy(np.ascontiguousarray(n0, np.float32)).reshape(-1).to(dev)
+        if isinstance(init[img], dict):
+            e = init[img]
+            if not zeroed:
+                _device_sync(dev)
+                zeroed = True
+            base = slabs[j].data_ptr()
+            if "splat" in e:
+                dmin, dmax = ctx.splat_init_device(img, e["splat"], base, base + 4 * hw)
+            else:
+                dmin, dmax = ctx.triangulate_init_device(img, e["points"], base, base + 4 * hw, avg_depth=e.get("avg_depth", 0.0),
+                                                         add_corners=e.get("add_corners", True))
+        else:
+            d0, n0, dmin, dmax = init[img]
+            slabs[j, :hw] = torch.from_numpy(np.ascontiguousarray(d0, np.float32)).reshape(-1).to(dev)
+            slabs[j, hw:4 * hw] = torch.from_numpy(np.ascontiguousarray(n0, np.float32)).reshape(-1).to(dev)
         rng[j, 0], rng[j, 1] = float(dmin), float(dmax)
     allr = allgather_maps(rng, group)
     gathered = torch.empty(world * n_local, FLOATS_PER_PIXEL * hw, dtype=torch.float32, device=dev) if world > 1 else None

@@ -213,6 +213,31 @@ int hcmvs_triangulate_points(int32_t width, int32_t height, const double K[9], c
                              const float* points_xyz, int32_t n_points, float avg_depth, int32_t add_corners, float* depth,
                              float* normal, float* d_min, float* d_max);
 
+/* counters of the last hcmvs_triangulate_init_device / hcmvs_splat_init_device call */
+typedef struct {
+	uint64_t n_used;          /* points that entered the triangulation / were splatted */
+	uint64_t n_faces;         /* faces rasterised (splat: 0) */
+	uint64_t n_tile_entries;  /* sum of the tile lists' lengths */
+	uint64_t covered_pixels;  /* pixels with depth > 0 */
+	uint64_t cover_hits;      /* (pixel, face|point) hits; hits - pixels = overwrites the order rule decided */
+	float ms_host;            /* set-up on the host (Delaunay, planes, binning) */
+	float ms_device;          /* HIP events around the kernel */
+	uint64_t device_bytes;    /* the tables and tile lists on the device */
+} hcmvs_init_stats;
+/* The two initialisations above with the pixel loop on the device: points_xyz is a HOST array, d_depth (w*h) and d_normal (w*h*3) are
+ * DEVICE pointers; every pixel of both is written (0 where nothing covers; the splat's normals are 0 everywhere), bit-identical to the
+ * host forms called with zero-filled normals.  The per-point / per-face set-up (projection, Delaunay, planes: double precision) runs on
+ * the host, only its tables travel -- through page-locked staging of the context.  *d_min / *d_max are final on return; the raster is
+ * enqueued on the context's stream, ordered before a following hcmvs_estimate*_device, and NOT synchronised.  Refused before anything
+ * reaches the device: null pointers, n_points < 1, an unknown view, a non-finite coordinate, no point in front of the view
+ * (triangulation). */
+int hcmvs_triangulate_init_device(hcmvs_ctx* ctx, uint32_t id, const float* points_xyz, int32_t n_points, float avg_depth,
+                                  int32_t add_corners, float* d_depth, float* d_normal, float* d_min, float* d_max);
+int hcmvs_splat_init_device(hcmvs_ctx* ctx, uint32_t id, const float* points_xyz, int32_t n_points, float* d_depth,
+                            float* d_normal, float* d_min, float* d_max);
+/* waits for the context's stream, then reads the counters of the last of the two calls */
+int hcmvs_get_init_stats(hcmvs_ctx* ctx, hcmvs_init_stats* out);
+
 /* cv::resize(src, dst, Size(dst_w, dst_h), 0, 0, INTER_AREA) for an ENLARGING resize of an f32 image with `channels` interleaved
  * channels -- how the fork's `restore` variant brings the previous pyramid level's depth and normal maps to the current size before
  * offering them as the extra hypothesis (restore/libs/MVS/SceneDensify.cpp:523-524; d_hint_depth / d_hint_normal above).  OpenCV's
