@@ -1,5 +1,5 @@
-/* hc-mvs_amd/csrc/dev_buf.h -- the one owner of the library's device memory: a grow-only buffer, the out-of-memory hook, the carving
- * of one allocation into pieces (carve.h) */
+/* hc-mvs_amd/csrc/dev_buf.h -- the owners of what the library takes from the runtime: a grow-only device buffer with the out-of-memory
+ * hook and the carving of one allocation into pieces (carve.h), a grow-only page-locked host buffer, an event */
 #ifndef HCMVS_DEV_BUF_H
 #define HCMVS_DEV_BUF_H
 #include <hip/hip_runtime.h>
@@ -53,6 +53,65 @@ private:
 	void* p_ = nullptr;
 	size_t cap_ = 0;
 	Reclaimer* rec_ = nullptr;
+};
+
+// A page-locked host allocation, freed when the buffer goes.  reserve() only grows, to exactly the bytes asked for; the contents are
+// not kept, and whoever grows it knows that no copy out of it is in flight.
+class PinnedBuf {
+public:
+	PinnedBuf() = default;
+	PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+	PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+		if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+		return *this;
+	}
+	PinnedBuf(const PinnedBuf&) = delete;
+	PinnedBuf& operator=(const PinnedBuf&) = delete;
+	~PinnedBuf() { reset(); }
+
+	hipError_t reserve(size_t bytes) {
+		if (bytes <= cap_) return hipSuccess;
+		reset();
+		const hipError_t e = hipHostMalloc(&p_, bytes, hipHostMallocDefault);
+		if (e != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return e; }
+		cap_ = bytes;
+		return hipSuccess;
+	}
+	void reset() {
+		if (p_) (void)hipHostFree(p_);
+		p_ = nullptr; cap_ = 0;
+	}
+	char* get() const { return (char*)p_; }
+	size_t capacity() const { return cap_; }
+
+private:
+	void* p_ = nullptr;
+	size_t cap_ = 0;
+};
+
+// An event, created with its flags when it is first asked for and destroyed when the owner goes
+class Event {
+public:
+	explicit Event(unsigned flags = hipEventDefault) : flags_(flags) {}
+	Event(Event&& o) noexcept : e_(o.e_), flags_(o.flags_) { o.e_ = nullptr; }
+	Event& operator=(Event&& o) noexcept {
+		if (this != &o) { reset(); e_ = o.e_; flags_ = o.flags_; o.e_ = nullptr; }
+		return *this;
+	}
+	Event(const Event&) = delete;
+	Event& operator=(const Event&) = delete;
+	~Event() { reset(); }
+
+	hipError_t ensure() { return e_ ? hipSuccess : hipEventCreateWithFlags(&e_, flags_); }
+	void reset() {
+		if (e_) (void)hipEventDestroy(e_);
+		e_ = nullptr;
+	}
+	hipEvent_t get() const { return e_; }
+
+private:
+	hipEvent_t e_ = nullptr;
+	unsigned flags_;
 };
 
 } // namespace hcmvs

@@ -1,13 +1,14 @@
 /*
  * hc-mvs_amd/csrc/hcmvs_api.cpp -- host side of the C-ABI declared in include/hcmvs_hip.h.
  *
- * Holds the per-device context (views resident in HBM, working maps, row-progress words), derives the
- * per-call constants the way DepthEstimator's constructor does (DepthMap.cpp:386-439, DepthMap.h:412-444)
- * and enqueues the kernels of pm_kernels.hip.  No compute happens on the host; without a usable HIP
+ * Holds the per-device context (views resident in HBM, working maps, row-progress words), hands the
+ * per-call constants of est_plan.h (DepthEstimator's constructor, DepthMap.cpp:386-439, DepthMap.h:412-444)
+ * the device pointers and enqueues the kernels of pm_kernels.hip.  No compute happens on the host; without a usable HIP
  * device every entry point fails.
  */
 #include "../../include/hcmvs_hip.h"
 #include "pm_common.h"
+#include "est_plan.h"
 #include "fuse_common.h"
 #include "pf_chain.h"
 #include "filter_plan.h"
@@ -91,15 +92,12 @@ struct hcmvs_ctx final : Reclaimer {
 	int viewspread = 0;                   // hcmvs_set_viewspread
 	bool haveSpreadStats = false;         // the last estimate ran with view spread in effect
 	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
-	int sweepPerLaunch = 0;               // HCMVS_SWEEP_LAUNCHES: 0 automatic, 1 per-sweep, 2 one (sweep_plan.h)
+	SweepKnobs knobs;                     // the HCMVS_* tuning knobs of the environment (sweep_plan.h)
 	DevBuf evals{this};                   // unsigned long long [4]
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	Event ev[4];                          // timing: before the init score, the sweeps, the end pass, and after it
 	int lastSweeps = 0, lastSweepLaunches = 0;
 	bool haveStats = false;
-	int sweepLag = 1;
-	int sweepSegment = -1; // columns per ticket of the sweep worker: -1 = automatic (sweep_plan.h), 0 = whole rows
 	int fuseOrder = 0; // hcmvs_set_fuse_order
-	int xcdAffinity = 1; // rows of an image prefer the workgroups of one XCD (HCMVS_XCD_AFFINITY=0 turns it off)
 	// filter / fuse scratch
 	DevBuf dMaps{this};       // DevMap per view id
 	DevBuf counters{this};    // unsigned long long [8]
@@ -109,16 +107,15 @@ struct hcmvs_ctx final : Reclaimer {
 	DevBuf pfState;           // the post-filter chain's state kept from fusion to fusion (pf_kernels.hip); never reserved with the reclaimer
 	bool errPending = false; // an estimate was enqueued since the error word was last read
 	int nCU = 0;          // compute units of the device (sweep_plan.h)
-	hipEvent_t upEv[2] = {nullptr, nullptr};
-	char* pinned = nullptr; size_t capPinned = 0; // page-locked staging of the host-buffer uploads (a pageable hipMemcpy crawls at ~1.3 GB/s here)
-	int wavesPerRow = 0; // HCMVS_WAVES_PER_ROW: 1..4 requested, 0 = automatic by the batch's rows (sweep_plan.h)
+	PinnedBuf pinned; // page-locked staging of the host-buffer uploads (a pageable hipMemcpy crawls at ~1.3 GB/s here), in two halves
+	Event upEv[2] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming)}; // a half has left for the device
 	// hcmvs_*_init_device: the counters, the table and the tile lists of a call (init_plan.h InitLayout) on the device, and their page-locked
 	// staging; initCopied marks the copy out of the staging, which is rewritten only after it
 	DevBuf initBuf{this};
-	char* initPinned = nullptr; size_t capInitPinned = 0;
-	hipEvent_t initCopied = nullptr;
+	PinnedBuf initPinned;
+	Event initCopied{hipEventDisableTiming};
 	bool initInFlight = false;
-	hipEvent_t initEv[2] = {nullptr, nullptr};
+	Event initEv[2]; // timing: around the kernel
 	hcmvs_init_stats initStats = {};
 	bool haveInitStats = false;
 
@@ -154,38 +151,6 @@ static View* find_view(hcmvs_ctx* c, const char* who, uint32_t id) {
 	fail(c, HCMVS_ERR_INVALID, "%s: unknown view %u", who, id);
 	return nullptr;
 }
-
-static void mat3_mul(const double* a, const double* b, double* c) {
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j) {
-			double s = 0;
-			for (int k = 0; k < 3; ++k) s += a[i * 3 + k] * b[k * 3 + j];
-			c[i * 3 + j] = s;
-		}
-}
-static void mat3_mul_bt(const double* a, const double* b, double* c) {
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j) {
-			double s = 0;
-			for (int k = 0; k < 3; ++k) s += a[i * 3 + k] * b[j * 3 + k];
-			c[i * 3 + j] = s;
-		}
-}
-static void mat3_inv(const double* m, double* r) {
-	const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
-	                 m[2] * (m[3] * m[7] - m[4] * m[6]);
-	const double id = 1.0 / d;
-	r[0] = (m[4] * m[8] - m[5] * m[7]) * id;
-	r[1] = (m[2] * m[7] - m[1] * m[8]) * id;
-	r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-	r[3] = (m[5] * m[6] - m[3] * m[8]) * id;
-	r[4] = (m[0] * m[8] - m[2] * m[6]) * id;
-	r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-	r[6] = (m[3] * m[7] - m[4] * m[6]) * id;
-	r[7] = (m[1] * m[6] - m[0] * m[7]) * id;
-	r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-static inline float fd2r(float d) { return d * (3.14159274101257324f / 180.f); }
 
 #ifdef HCMVS_STAMPS
 namespace hcmvs { void debug_read_stamps(unsigned long long* out, int reset); }
@@ -233,8 +198,8 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	c->nCU = prop.multiProcessorCount;
 	if (hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
 	c->stream = c->ownStream;
-	for (auto& e : c->ev)
-		if (hipEventCreate(&e) != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
+	for (Event& e : c->ev)
+		if (e.ensure() != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
 	c->hViews.resize((size_t)kMaxBatch * kMaxViews); c->hItems.resize(kMaxBatch); c->hSpread.resize((size_t)kMaxBatch * kMaxViews);
 	if (c->dViews.reserve(sizeof(DevView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(64, c->stream) != hipSuccess ||
 	    c->dSpread.reserve(sizeof(SpreadView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess ||
@@ -242,17 +207,8 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 		hcmvs_destroy(c);
 		return HCMVS_ERR_NO_DEVICE;
 	}
-	const char* lag = getenv("HCMVS_SWEEP_LAG");
-	if (lag && atoi(lag) >= 1) c->sweepLag = atoi(lag);
-	const char* aff = getenv("HCMVS_XCD_AFFINITY");
-	if (aff) c->xcdAffinity = atoi(aff) != 0;
-	const char* spl = getenv("HCMVS_SWEEP_LAUNCHES");
-	if (spl && strcmp(spl, "per-sweep") == 0) c->sweepPerLaunch = 1;
-	if (spl && strcmp(spl, "one") == 0) c->sweepPerLaunch = 2;
-	const char* sgl = getenv("HCMVS_SWEEP_SEGMENT"); // tuning knob: columns per ticket (0 = whole rows)
-	if (sgl && atoi(sgl) >= 0) c->sweepSegment = atoi(sgl);
-	const char* wpr = getenv("HCMVS_WAVES_PER_ROW"); // tuning knob: 1, 2, 3 or 4 waves cooperate on one image row
-	if (wpr && (atoi(wpr) == 1 || atoi(wpr) == 2 || atoi(wpr) == 3 || atoi(wpr) == 4)) c->wavesPerRow = atoi(wpr);
+	c->knobs = parse_sweep_knobs(getenv("HCMVS_SWEEP_LAG"), getenv("HCMVS_XCD_AFFINITY"), getenv("HCMVS_SWEEP_LAUNCHES"), getenv("HCMVS_SWEEP_SEGMENT"),
+	                             getenv("HCMVS_WAVES_PER_ROW"));
 	*out = c;
 	return HCMVS_OK;
 }
@@ -261,14 +217,9 @@ void hcmvs_destroy(hcmvs_ctx* c) {
 	if (!c) return;
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->stream); // the stream is idle: the device buffers go with the context
-	for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-	if (c->pinned) (void)hipHostFree(c->pinned);
-	for (auto& e : c->upEv) if (e) (void)hipEventDestroy(e);
-	if (c->initPinned) (void)hipHostFree(c->initPinned);
-	if (c->initCopied) (void)hipEventDestroy(c->initCopied);
-	for (auto& e : c->initEv) if (e) (void)hipEventDestroy(e);
-	if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
-	delete c;
+	const hipStream_t own = c->ownStream;
+	delete c; // every buffer and event goes with its owner
+	if (own) (void)hipStreamDestroy(own);
 }
 
 const char* hcmvs_last_error(const hcmvs_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -300,7 +251,7 @@ int hcmvs_synchronize(hcmvs_ctx* c) {
 // host -> device through the context's page-locked staging buffer, in pieces: the caller's buffer is pageable, and a pageable
 // hipMemcpy is an order of magnitude slower than memcpy + a pinned transfer
 static int upload_staged(hcmvs_ctx* c, void* dst, const void* src, size_t bytes) {
-	{ // a caller that already holds the data in page-locked memory (hipHostMalloc / hipHostRegister) needs no staging
+	{ // a caller that already holds the data in page-locked memory (allocated by or registered with the runtime) needs no staging
 		hipPointerAttribute_t at;
 		if (hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost) {
 			HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -310,26 +261,20 @@ static int upload_staged(hcmvs_ctx* c, void* dst, const void* src, size_t bytes)
 		(void)hipGetLastError(); // pageable memory is "invalid value" to the query
 	}
 	const size_t piece = (size_t)32 << 20;
-	if (c->capPinned < 2 * piece) {
-		if (c->pinned) (void)hipHostFree(c->pinned);
-		c->pinned = nullptr; c->capPinned = 0;
-		if (hipHostMalloc((void**)&c->pinned, 2 * piece, hipHostMallocDefault) != hipSuccess) { // no pinned memory to be had: the plain copy
-			(void)hipGetLastError();
-			HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			return HCMVS_OK;
-		}
-		c->capPinned = 2 * piece;
+	if (c->pinned.reserve(2 * piece) != hipSuccess) { // no pinned memory to be had: the plain copy
+		HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		return HCMVS_OK;
 	}
-	for (auto& e : c->upEv) if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-	hipEvent_t done[2] = {c->upEv[0], c->upEv[1]};
+	for (Event& e : c->upEv) HIPCHK(c, e.ensure());
+	const hipEvent_t done[2] = {c->upEv[0].get(), c->upEv[1].get()};
 	bool used[2] = {false, false};
 	int k = 0;
 	for (size_t off = 0; off < bytes; off += piece, k ^= 1) {
 		const size_t n = std::min(piece, bytes - off);
 		if (used[k]) HIPCHK(c, hipEventSynchronize(done[k])); // the half I am about to overwrite has left
-		memcpy(c->pinned + (size_t)k * piece, (const char*)src + off, n);
-		HIPCHK(c, hipMemcpyAsync((char*)dst + off, c->pinned + (size_t)k * piece, n, hipMemcpyHostToDevice, c->stream));
+		memcpy(c->pinned.get() + (size_t)k * piece, (const char*)src + off, n);
+		HIPCHK(c, hipMemcpyAsync((char*)dst + off, c->pinned.get() + (size_t)k * piece, n, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(c, hipEventRecord(done[k], c->stream));
 		used[k] = true;
 	}
@@ -538,145 +483,83 @@ int hcmvs_get_ignore_mask(hcmvs_ctx* c, uint32_t id, uint8_t* keep) {
 	return HCMVS_OK;
 }
 
-// per-item constants: DepthMap.cpp:386-439, DepthMap.h:412-444
-static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item& it, const hcmvs_params* p, EstConst& k) {
-	if (!it.src_ids || !it.d_depth || !it.d_normal || !it.d_conf) return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
+// an estimate call the plan refuses (est_plan.h), in the words of the API.  ref: the reference view of item bad.at (kEstBorder)
+static int refuse_estimate(hcmvs_ctx* c, EstCheck bad, const hcmvs_batch_item* items, int n_items, const hcmvs_params* p, const View* ref = nullptr) {
+	switch (bad.broken) {
+	case kEstOk: return HCMVS_OK;
+	case kEstBatchSize: return fail(c, HCMVS_ERR_INVALID, "estimate: batch size %d not in 1..%d", n_items, kMaxBatch);
+	case kEstHalfWindow: return fail(c, HCMVS_ERR_INVALID, "estimate: adapthalfwin %d not in 1..%d", p->adapthalfwin, kMaxHalfWindow);
+	case kEstIterCounts: return fail(c, HCMVS_ERR_INVALID, "estimate: bad iteration counts");
+	case kEstSrcCount: // (a count outside 1..16 is of neither class)
+	case kEstSrcClass: return fail(c, HCMVS_ERR_INVALID, "estimate: the items of a batch must use source-view counts of one class (1-8 or 9-16)");
+	case kEstNull: return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
+	case kEstDepthRange: return fail(c, HCMVS_ERR_INVALID, "estimate: bad depth range [%g,%g)", items[bad.at].d_min, items[bad.at].d_max);
+	case kEstBorder:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: view %u (%dx%d) has no pixel inside the %d px border", items[bad.at].ref_id, ref->w, ref->h, est_border(*p));
+	}
+	return HCMVS_ERR_INVALID;
+}
+
+static EstCamera camera_of(const View& v) { return {v.K, v.R, v.C, v.w, v.h}; }
+
+// Item `slot` of a batch into hItems / hViews / hSpread: the plan's constants (est_plan.h) and what only the context knows -- the views'
+// device images, made when first needed, the slot's working maps and the caller's pointers
+static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int n_items, const hcmvs_params* p) {
+	const hcmvs_batch_item& it = items[slot];
+	int rc = refuse_estimate(c, est_check_item(items, slot), items, n_items, p);
+	if (rc) return rc;
 	const int n_src = it.n_src;
-	if (n_src < 1 || n_src > HCMVS_MAX_VIEWS) return fail(c, HCMVS_ERR_INVALID, "estimate: n_src %d not in 1..%d", n_src, HCMVS_MAX_VIEWS);
-	// d_min == 0 is what the `restore` variant ends up with (its range takes the enlarged previous-level map in, zeros included,
-	// restore/libs/MVS/SceneDensify.cpp:526-532)
-	if (!(it.d_min >= 0.f) || !(it.d_max > it.d_min)) return fail(c, HCMVS_ERR_INVALID, "estimate: bad depth range [%g,%g)", it.d_min, it.d_max);
 	View* pref = find_view(c, "estimate", it.ref_id);
 	if (!pref) return HCMVS_ERR_INVALID;
 	View& ref = *pref;
 	if (!ref.gray) return fail(c, HCMVS_ERR_INVALID, "estimate: view %u was registered without a gray image (fuse-only view)", it.ref_id);
-	int rc = ensure_slot(c, slot, (size_t)ref.w * ref.h, ref.h);
+	rc = refuse_estimate(c, est_check_image(slot, ref.w, ref.h, *p), items, n_items, p, &ref);
+	if (rc) return rc;
+	rc = ensure_slot(c, slot, (size_t)ref.w * ref.h, ref.h);
 	if (rc) return rc;
 	rc = ensure_gradient(c, ref);
 	if (rc) return rc;
-	memset(&k, 0, sizeof k);
-	k.W = ref.w; k.H = ref.h; k.V = n_src;
-	k.border = p->adapthalfwin > kHalfWindow ? p->adapthalfwin : kHalfWindow; // nSizeHalfWindow generalised (pm_common.h)
-	if (ref.w < 2 * k.border + 2 || ref.h < 2 * k.border + 2) return fail(c, HCMVS_ERR_INVALID, "estimate: view %u (%dx%d) has no pixel inside the %d px border", it.ref_id, ref.w, ref.h, k.border);
-	k.adapthalfwin = p->adapthalfwin; k.nRandomIters = p->n_random_iters; k.itExternal = p->it_external;
-	k.propHalfwin = p->propagate_halfwin; k.propStep = p->propagate_step;
-	k.ref = ref.gray; k.gra = ref.gra.get<uint8_t>(); k.views = c->dViews.get<DevView>() + (size_t)slot * kMaxViews;
-	double Hr[9];
-	mat3_inv(ref.K, Hr);
-	for (int i = 0; i < 9; ++i) k.Hr[i] = (float)Hr[i];
-	k.ifx = 1.0 / ref.K[0]; k.ify = 1.0 / ref.K[4]; k.cx = ref.K[2]; k.cy = ref.K[5];
-	DevView* hv = c->hViews.data() + (size_t)slot * kMaxViews;
-	memset(hv, 0, sizeof(DevView) * kMaxViews);
-	uintptr_t lo = ~(uintptr_t)0, hi = 0;
-	View* src[HCMVS_MAX_VIEWS]; // the source views, looked up once
+	const View* src[kMaxViews]; // the source views, looked up once
+	EstCamera cam[kMaxViews];
+	uint64_t imgAt[kMaxViews];
+	size_t imgBytes[kMaxViews];
 	for (int v = 0; v < n_src; ++v) {
-		src[v] = find_view(c, "estimate", it.src_ids[v]);
-		if (!src[v]) return HCMVS_ERR_INVALID;
-		View& s = *src[v];
-		if (!s.gray) return fail(c, HCMVS_ERR_INVALID, "estimate: source view %u was registered without a gray image (fuse-only view)", it.src_ids[v]);
-		rc = ensure_quads(c, s);
+		View* s = find_view(c, "estimate", it.src_ids[v]);
+		if (!s) return HCMVS_ERR_INVALID;
+		if (!s->gray) return fail(c, HCMVS_ERR_INVALID, "estimate: source view %u was registered without a gray image (fuse-only view)", it.src_ids[v]);
+		rc = ensure_quads(c, *s);
 		if (rc) return rc;
-		double KR[9], Hl[9], A[9];
-		mat3_mul(s.K, s.R, KR);
-		mat3_mul_bt(KR, ref.R, Hl);
-		const double dC[3] = {ref.C[0] - s.C[0], ref.C[1] - s.C[1], ref.C[2] - s.C[2]};
-		for (int i = 0; i < 3; ++i) hv[v].Hm[i] = (float)(KR[i * 3] * dC[0] + KR[i * 3 + 1] * dC[1] + KR[i * 3 + 2] * dC[2]);
-		mat3_mul(Hl, Hr, A);
-		for (int i = 0; i < 9; ++i) hv[v].A[i] = (float)A[i];
-		hv[v].w = s.w; hv[v].h = s.h;
-		const uintptr_t b = (uintptr_t)s.quads.get(), e = b + (size_t)s.w * s.h * sizeof(float4);
-		if (b < lo) lo = b;
-		if (e > hi) hi = e;
+		src[v] = s; cam[v] = camera_of(*s);
+		imgAt[v] = (uintptr_t)s->quads.get(); imgBytes[v] = (size_t)s->w * s->h * sizeof(float4);
 	}
-	// 32-bit texel offsets from one scalar base: the source views of one item must lie within a 4 GiB window.
-	// When the caller's images are further apart they are first copied (device to device, a few tens of MB) into a
-	// compact slab owned by the context.
-	if (hi - lo < 0xFFFF0000ull) {
-		k.imgBase = (const char*)lo;
-		for (int v = 0; v < n_src; ++v) hv[v].byteOff = (uint32_t)((uintptr_t)src[v]->quads.get() - lo);
-	} else {
-		Carve slab;
-		for (int v = 0; v < n_src; ++v) { const View& s = *src[v]; hv[v].byteOff = (uint32_t)slab((size_t)s.w * s.h * sizeof(float4)); }
-		if (slab.size >= 0xFFFF0000ull) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
+	EstConst& k = c->hItems[slot];
+	DevView* hv = c->hViews.data() + (size_t)slot * kMaxViews;
+	const bool hint = it.d_hint_depth && it.d_hint_normal;
+	est_item_consts(camera_of(ref), cam, n_src, *p, it.d_min, it.d_max, it.seed_offset, hint, k, hv);
+	k.ref = ref.gray; k.gra = ref.gra.get<uint8_t>(); k.views = c->dViews.get<DevView>() + (size_t)slot * kMaxViews;
+	uint32_t imgOff[kMaxViews];
+	const EstWindow win = est_image_window(imgAt, imgBytes, n_src, imgOff);
+	if (win.kind == kEstWindowRefused) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
+	for (int v = 0; v < n_src; ++v) hv[v].byteOff = imgOff[v];
+	if (win.kind == kEstWindowDirect) k.imgBase = (const char*)(uintptr_t)win.base;
+	else { // the caller's images lie further apart: copied (device to device, a few tens of MB) into a compact slab owned by the context
 		DevBuf& srcSlab = c->slots[slot].srcSlab;
-		HIPCHK(c, srcSlab.reserve(slab.size, c->stream));
-		for (int v = 0; v < n_src; ++v) {
-			const View& s = *src[v];
-			HIPCHK(c, hipMemcpyAsync(srcSlab.get() + hv[v].byteOff, s.quads.get(), (size_t)s.w * s.h * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-		}
+		HIPCHK(c, srcSlab.reserve(win.slabBytes, c->stream));
+		for (int v = 0; v < n_src; ++v)
+			HIPCHK(c, hipMemcpyAsync(srcSlab.get() + imgOff[v], src[v]->quads.get(), imgBytes[v], hipMemcpyDeviceToDevice, c->stream));
 		k.imgBase = srcSlab.get();
 	}
-	k.dMin = it.d_min; k.dMax = it.d_max; k.dMinSqr = sqrtf(it.d_min); k.dMaxSqr = sqrtf(it.d_max);
-	k.smoothBonusDepth = 1.f - p->random_smooth_bonus;
-	k.smoothBonusNormal = (1.f - p->random_smooth_bonus) * 0.96f;
-	k.smoothSigmaDepth = -1.f / (2.f * (p->random_smooth_depth * p->random_smooth_depth));
-	{ const float r = fd2r(p->random_smooth_normal_deg); k.smoothSigmaNormal = -1.f / (2.f * (r * r)); }
-	k.angle1Range = fd2r(p->random_angle1_deg);
-	k.angle2Range = fd2r(p->random_angle2_deg);
-	k.thConfSmall = p->ncc_threshold_keep * 0.2f;
-	k.thConfBig = p->ncc_threshold_keep * 0.4f;
-	k.thConfRand = p->ncc_threshold_keep * 0.9f;
-	k.thRobust = p->ncc_threshold_keep * 1.2f;
-	k.thKeep = p->ncc_threshold_keep;
-	k.depthRatio = p->random_depth_ratio;
-	k.pfScale = 1.f - p->photometric_flow;
-	k.seed = p->seed + it.seed_offset;
 	k.dn = c->slots[slot].dn.get<float4>(); k.conf = c->slots[slot].conf.get<float>(); k.progress = c->slots[slot].progress.get<int32_t>();
-	k.hintDepth = nullptr; k.hintNormal = nullptr; k.hintIter = -1;
-	if (it.d_hint_depth && it.d_hint_normal && p->it_external == p->n_external_iters - 1) { // restore/libs/MVS/DepthMap.cpp:1527
-		k.hintDepth = it.d_hint_depth; k.hintNormal = it.d_hint_normal; k.hintIter = p->n_estimation_iters - 1;
-	}
+	if (est_uses_hint(*p, hint)) { k.hintDepth = it.d_hint_depth; k.hintNormal = it.d_hint_normal; }
 	k.keep = ref.keep.capacity() ? ref.keep.get<uint8_t>() : nullptr; // the reference view's mask only (source views ignore theirs)
-	// --n-viewspread (DepthMap.cpp:1504-1608): from outer iteration 1 on, the source views that offer maps of their own
-	k.spread = nullptr;
 	SpreadView* hs = c->hSpread.data() + (size_t)slot * kMaxViews;
 	memset(hs, 0, sizeof(SpreadView) * kMaxViews);
-	if (c->viewspread && p->it_external >= 1) {
-		bool any = false;
-		for (int v = 0; v < n_src; ++v) {
-			const View& s = *src[v];
-			if (!s.sDepth || s.rescaled) continue;
-			any = true;
-			hs[v].depth = s.sDepth; hs[v].normal = s.sNormal; hs[v].conf = s.sConf;
-			hs[v].w = s.w; hs[v].h = s.h;
-			hs[v].cx = s.K[2]; hs[v].cy = s.K[5]; hs[v].ifx = 1.0 / s.K[0]; hs[v].ify = 1.0 / s.K[4];
-			// depth in the reference camera of a point Xc of view j's camera: (R_ref R_j^T Xc + R_ref (C_j - C_ref)).z
-			double T[9];
-			mat3_mul_bt(ref.R, s.R, T);
-			const double dC[3] = {s.C[0] - ref.C[0], s.C[1] - ref.C[1], s.C[2] - ref.C[2]};
-			hs[v].Tz[0] = T[6]; hs[v].Tz[1] = T[7]; hs[v].Tz[2] = T[8];
-			hs[v].tz = ref.R[6] * dC[0] + ref.R[7] * dC[1] + ref.R[8] * dC[2];
-		}
-		if (any) k.spread = c->dSpread.get<SpreadView>() + (size_t)slot * kMaxViews;
-	}
-	return HCMVS_OK;
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-static inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-	const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-	return a0 < b0 + nb && b0 < a0 + na;
-}
-
-// view spread: a launch must not read what it writes -- the in/out maps of no item may overlap the spread maps of a source view of any item
-static int check_spread_overlap(hcmvs_ctx* c, const hcmvs_batch_item* items, int n_items) {
-	for (int i = 0; i < n_items; ++i) {
-		const size_t n = (size_t)c->hItems[i].W * c->hItems[i].H;
-		for (int k = 0; k < n_items; ++k)
-			for (int v = 0; v < items[k].n_src; ++v) {
-				const SpreadView& sv = c->hSpread[(size_t)k * kMaxViews + v];
-				if (!c->hItems[k].spread || !sv.depth) continue;
-				const size_t m = (size_t)sv.w * sv.h;
-				const void* io[3] = {items[i].d_depth, items[i].d_normal, items[i].d_conf};
-				const size_t ion[3] = {n * 4, n * 12, n * 4};
-				const void* sp[3] = {sv.depth, sv.normal, sv.conf};
-				const size_t spn[3] = {m * 4, m * 12, m * 4};
-				for (int a = 0; a < 3; ++a)
-					for (int b = 0; b < 3; ++b)
-						if (overlaps(io[a], ion[a], sp[b], spn[b]))
-							return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the spread maps of source view %u of item %d: "
-							            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", i, items[i].ref_id, items[k].src_ids[v], k);
-			}
+	for (int v = 0; v < n_src; ++v) {
+		const View& s = *src[v];
+		if (!est_view_spreads(c->viewspread, *p, s.sDepth, s.rescaled)) continue;
+		hs[v].depth = s.sDepth; hs[v].normal = s.sNormal; hs[v].conf = s.sConf;
+		est_spread_consts(camera_of(ref), cam[v], hs[v]);
+		k.spread = c->dSpread.get<SpreadView>() + (size_t)slot * kMaxViews;
 	}
 	return HCMVS_OK;
 }
@@ -684,28 +567,30 @@ static int check_spread_overlap(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!items || !p) return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
-	if (n_items < 1 || n_items > kMaxBatch) return fail(c, HCMVS_ERR_INVALID, "estimate: batch size %d not in 1..%d", n_items, kMaxBatch);
-	if (p->adapthalfwin < 1 || p->adapthalfwin > kMaxHalfWindow) return fail(c, HCMVS_ERR_INVALID, "estimate: adapthalfwin %d not in 1..%d", p->adapthalfwin, kMaxHalfWindow);
-	if (p->n_estimation_iters < 0 || p->n_random_iters < 0 || p->n_random_iters > 20)
-		return fail(c, HCMVS_ERR_INVALID, "estimate: bad iteration counts");
+	int rc = refuse_estimate(c, est_check_call(n_items, *p), items, n_items, p);
+	if (rc) return rc;
 	HIPCHK(c, hipSetDevice(c->device));
 	int maxRows = 0;
 	bool spread = false;
 	hcmvs::SweepBatch batch;
 	batch.big = p->adapthalfwin > kHalfWindow; batch.nSweeps = p->n_estimation_iters; batch.nCU = c->nCU;
-	batch.sweepPerLaunch = c->sweepPerLaunch; batch.sweepSegment = c->sweepSegment; batch.wavesPerRow = c->wavesPerRow;
+	batch.sweepPerLaunch = c->knobs.perLaunch; batch.sweepSegment = c->knobs.segment; batch.wavesPerRow = c->knobs.wavesPerRow;
+	batch.items.reserve(n_items);
 	for (int i = 0; i < n_items; ++i) {
-		if (items[i].n_src < 1 || items[i].n_src > kMaxViews || hcmvs::segments_for(items[i].n_src) != hcmvs::segments_for(items[0].n_src))
-			return fail(c, HCMVS_ERR_INVALID, "estimate: the items of a batch must use source-view counts of one class (1-8 or 9-16)");
-		int rc = build_item(c, i, items[i], p, c->hItems[i]);
+		rc = build_item(c, i, items, n_items, p);
 		if (rc) return rc;
 		const EstConst& k = c->hItems[i];
-		const int rows = k.H - 2 * k.border;
-		if (rows > maxRows) maxRows = rows;
+		batch.items.push_back(est_sweep_item(k, batch.nSweeps));
+		maxRows = std::max(maxRows, batch.items.back().rows);
 		spread = spread || k.spread;
-		batch.items.push_back({rows, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == batch.nSweeps - 1, k.keep != nullptr, k.spread != nullptr});
 	}
-	if (spread) { int rc = check_spread_overlap(c, items, n_items); if (rc) return rc; }
+	if (spread) { // a launch must not read what it writes
+		const EstOverlap o = est_spread_overlap(c->hItems.data(), c->hSpread.data(), items, n_items);
+		if (o.item >= 0)
+			return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the spread maps of source view %u of item %d: "
+			            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", o.item, items[o.item].ref_id,
+			            items[o.other].src_ids[o.view], o.other);
+	}
 	hipStream_t s = c->stream;
 	// same stream => the previous call's kernels are done with these tables before the copies land
 	if (spread) HIPCHK(c, hipMemcpyAsync(c->dSpread.get(), c->hSpread.data(), sizeof(SpreadView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
@@ -715,7 +600,7 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 64, s));
 	HIPCHK(c, hipMemsetAsync(c->sync.get(), 0, 64 + sizeof(int32_t) * 2 * kMaxBatch, s));
 
-	HIPCHK(c, hipEventRecord(c->ev[0], s));
+	HIPCHK(c, hipEventRecord(c->ev[0].get(), s));
 	for (int i = 0; i < n_items; ++i) {
 		const EstConst& k = c->hItems[i];
 		const float* depthIn = items[i].d_depth;
@@ -728,9 +613,9 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		}
 		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s);
 	}
-	HIPCHK(c, hipEventRecord(c->ev[1], s));
+	HIPCHK(c, hipEventRecord(c->ev[1].get(), s));
 	int32_t* sync = c->sync.get<int32_t>();
-	const SweepArgs sa{c->dItems.get<EstConst>(), n_items, maxRows, {sync + 16, sync + 16 + kMaxBatch, sync + 1, c->evals.get<unsigned long long>()}, c->sweepLag, c->xcdAffinity};
+	const SweepArgs sa{c->dItems.get<EstConst>(), n_items, maxRows, {sync + 16, sync + 16 + kMaxBatch, sync + 1, c->evals.get<unsigned long long>()}, c->knobs.lag, c->knobs.affinity};
 	const std::vector<hcmvs::SweepLaunch> plan = hcmvs::plan_sweeps(batch); // HCMVS_SWEEP_LAUNCHES, HCMVS_SWEEP_SEGMENT, HCMVS_WAVES_PER_ROW
 	for (const hcmvs::SweepLaunch& l : plan) {
 		HIPCHK(c, hipMemsetAsync(sync + 16, 0, sizeof(int32_t) * 2 * kMaxBatch, s)); // tickets + rowsDone; the error word stays sticky
@@ -741,10 +626,10 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread);
 	}
 	c->lastSweepLaunches = (int)plan.size();
-	HIPCHK(c, hipEventRecord(c->ev[2], s));
+	HIPCHK(c, hipEventRecord(c->ev[2].get(), s));
 	for (int i = 0; i < n_items; ++i)
 		launch_end_pass(c->hItems[i], p->it_external == p->n_external_iters - 1 ? 1 : 0, items[i].d_depth, items[i].d_normal, items[i].d_conf, s);
-	HIPCHK(c, hipEventRecord(c->ev[3], s));
+	HIPCHK(c, hipEventRecord(c->ev[3].get(), s));
 	HIPCHK(c, hipGetLastError());
 	c->lastSweeps = p->n_estimation_iters;
 	c->haveStats = true;
@@ -772,10 +657,10 @@ int hcmvs_get_stats(hcmvs_ctx* c, hcmvs_stats* out) {
 	out->evals = ev[0];
 	out->evals_issued = ev[1];
 	out->tap_evals = ev[2];
-	HIPCHK(c, hipEventElapsedTime(&out->ms_score, c->ev[0], c->ev[1]));
-	HIPCHK(c, hipEventElapsedTime(&out->ms_sweeps, c->ev[1], c->ev[2]));
-	HIPCHK(c, hipEventElapsedTime(&out->ms_end, c->ev[2], c->ev[3]));
-	HIPCHK(c, hipEventElapsedTime(&out->ms_total, c->ev[0], c->ev[3]));
+	HIPCHK(c, hipEventElapsedTime(&out->ms_score, c->ev[0].get(), c->ev[1].get()));
+	HIPCHK(c, hipEventElapsedTime(&out->ms_sweeps, c->ev[1].get(), c->ev[2].get()));
+	HIPCHK(c, hipEventElapsedTime(&out->ms_end, c->ev[2].get(), c->ev[3].get()));
+	HIPCHK(c, hipEventElapsedTime(&out->ms_total, c->ev[0].get(), c->ev[3].get()));
 	out->n_sweeps = c->lastSweeps;
 	out->n_sweep_launches = c->lastSweepLaunches;
 	out->ms_sweep_avg = c->lastSweeps > 0 ? out->ms_sweeps / (float)c->lastSweeps : 0.f;
@@ -911,29 +796,22 @@ static int init_enqueue(hcmvs_ctx* c, const char* who, bool triangles, const Vie
 	hipStream_t s = c->stream;
 	const size_t nTiles = (size_t)t.tilesX * t.tilesY;
 	const InitLayout l = init_layout(tableBytes, nTiles, t.items.size());
-	if (!c->initCopied) HIPCHK(c, hipEventCreateWithFlags(&c->initCopied, hipEventDisableTiming));
-	for (auto& e : c->initEv) if (!e) HIPCHK(c, hipEventCreate(&e));
-	if (c->initInFlight) { HIPCHK(c, hipEventSynchronize(c->initCopied)); c->initInFlight = false; } // the previous call's tables have left the staging
-	if (c->capInitPinned < l.bytes) {
-		if (c->initPinned) (void)hipHostFree(c->initPinned);
-		c->initPinned = nullptr; c->capInitPinned = 0;
+	HIPCHK(c, c->initCopied.ensure());
+	for (Event& e : c->initEv) HIPCHK(c, e.ensure());
+	if (c->initInFlight) { HIPCHK(c, hipEventSynchronize(c->initCopied.get())); c->initInFlight = false; } // the previous call's tables have left the staging
+	if (c->initPinned.capacity() < l.bytes) {
 		const size_t cap = std::max(l.bytes + l.bytes / 2, (size_t)1 << 20);
-		if (hipHostMalloc((void**)&c->initPinned, cap, hipHostMallocDefault) != hipSuccess) {
-			(void)hipGetLastError();
-			c->initPinned = nullptr;
-			return fail(c, HCMVS_ERR_HIP, "%s: no page-locked staging of %zu bytes", who, cap);
-		}
-		c->capInitPinned = cap;
+		if (c->initPinned.reserve(cap) != hipSuccess) return fail(c, HCMVS_ERR_HIP, "%s: no page-locked staging of %zu bytes", who, cap);
 	}
 	HIPCHK(c, c->initBuf.reserve(l.bytes, s));
-	char* h = c->initPinned;
+	char* h = c->initPinned.get();
 	memset(h + l.counters, 0, 2 * sizeof(uint64_t));
 	if (tableBytes) memcpy(h + l.table, table, tableBytes);
 	memcpy(h + l.first, t.first.data(), (nTiles + 1) * sizeof(uint32_t));
 	if (!t.items.empty()) memcpy(h + l.items, t.items.data(), t.items.size() * sizeof(uint32_t));
 	char* d = c->initBuf.get();
 	HIPCHK(c, hipMemcpyAsync(d, h, l.bytes, hipMemcpyHostToDevice, s)); // same stream: the previous call's kernel is done with the buffer
-	HIPCHK(c, hipEventRecord(c->initCopied, s));
+	HIPCHK(c, hipEventRecord(c->initCopied.get(), s));
 	c->initInFlight = true;
 	InitRaster r;
 	r.W = v.w; r.H = v.h; r.tilesX = t.tilesX; r.tilesY = t.tilesY;
@@ -941,11 +819,11 @@ static int init_enqueue(hcmvs_ctx* c, const char* who, bool triangles, const Vie
 	r.first = (const uint32_t*)(d + l.first); r.items = (const uint32_t*)(d + l.items);
 	r.depth = d_depth; r.normal = d_normal;
 	r.counters = (unsigned long long*)(d + l.counters);
-	HIPCHK(c, hipEventRecord(c->initEv[0], s));
+	HIPCHK(c, hipEventRecord(c->initEv[0].get(), s));
 	if (triangles) launch_init_triangles(r, (const InitFace*)(d + l.table), s);
 	else launch_init_splats(r, (const InitSplatBox*)(d + l.table), s);
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(c->initEv[1], s));
+	HIPCHK(c, hipEventRecord(c->initEv[1].get(), s));
 	c->initStats.n_tile_entries = t.items.size();
 	c->initStats.device_bytes = l.bytes;
 	c->haveInitStats = true;
@@ -1016,7 +894,7 @@ int hcmvs_get_init_stats(hcmvs_ctx* c, hcmvs_init_stats* out) {
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	unsigned long long counters[2] = {0, 0};
 	HIPCHK(c, hipMemcpy(counters, c->initBuf.get(), sizeof counters, hipMemcpyDeviceToHost)); // InitLayout: the counters open the buffer
-	HIPCHK(c, hipEventElapsedTime(&c->initStats.ms_device, c->initEv[0], c->initEv[1]));
+	HIPCHK(c, hipEventElapsedTime(&c->initStats.ms_device, c->initEv[0].get(), c->initEv[1].get()));
 	c->initStats.covered_pixels = counters[0]; c->initStats.cover_hits = counters[1];
 	*out = c->initStats;
 	return HCMVS_OK;
@@ -1368,14 +1246,14 @@ int hcmvs_filter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, int3
 		launches.push_back(L);
 	}
 	std::vector<unsigned long long> cnt(items.size() * 2); // (declared before the guard below: it must outlive the copy into it)
-	hipEvent_t ev[2] = {nullptr, nullptr};
-	HIPCHK(c, hipEventCreate(&ev[0]));
-	if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return fail(c, HCMVS_ERR_HIP, "filter_sequence: hipEventCreate failed"); }
+	Event ev[2]; // timing; (declared before the guard too: they go after the stream is idle)
+	for (Event& e : ev)
+		if (e.ensure() != hipSuccess) return fail(c, HCMVS_ERR_HIP, "filter_sequence: hipEventCreate failed");
 	// whichever way the call ends: the stream is idle before the host tables (tab, cnt: source and target of asynchronous copies) go
-	struct EndGuard { hipEvent_t* e; hipStream_t s; ~EndGuard() { (void)hipStreamSynchronize(s); (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } endGuard{ev, s};
+	struct EndGuard { hipStream_t s; ~EndGuard() { (void)hipStreamSynchronize(s); } } endGuard{s};
 	HIPCHK(c, hipMemcpyAsync(dTab, tab.data(), cv.size, hipMemcpyHostToDevice, s));
 	HIPCHK(c, hipMemsetAsync(c->filterCnt.get(), 0, items.size() * 16, s));
-	HIPCHK(c, hipEventRecord(ev[0], s));
+	HIPCHK(c, hipEventRecord(ev[0].get(), s));
 	const FilterRef* dRefs = (const FilterRef*)(dTab + offRefs);
 	for (const Launch& L : launches) {
 		launch_fill_u64(c->fuseScratch.get<unsigned long long>(), ~0ull, L.keyWords, s);
@@ -1386,7 +1264,7 @@ int hcmvs_filter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, int3
 	}
 	launch_filter_commit(dRefs, (int)items.size(), s); // every image was voted from the maps as the call found them; now they change
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(ev[1], s));
+	HIPCHK(c, hipEventRecord(ev[1].get(), s));
 	HIPCHK(c, hipMemcpyAsync(cnt.data(), c->filterCnt.get(), items.size() * 16, hipMemcpyDeviceToHost, s));
 	HIPCHK(c, hipStreamSynchronize(s)); // the only wait after the first launch: nothing synchronises between the batches
 	if (stats) {
@@ -1397,7 +1275,7 @@ int hcmvs_filter_sequence(hcmvs_ctx* c, const uint32_t* ids, int32_t n_ids, int3
 		}
 		for (const Launch& L : launches) stats->batch = std::max(stats->batch, (uint32_t)L.nRefs);
 		stats->device_bytes = keyBytes + stagePx * 8 + cv.size + items.size() * 16;
-		HIPCHK(c, hipEventElapsedTime(&stats->ms_device, ev[0], ev[1]));
+		HIPCHK(c, hipEventElapsedTime(&stats->ms_device, ev[0].get(), ev[1].get()));
 	}
 	return HCMVS_OK;
 }

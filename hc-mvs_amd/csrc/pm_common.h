@@ -1,5 +1,6 @@
 /*
- * hc-mvs_amd/csrc/pm_common.h -- structures shared by the host API and the gfx950 kernels.
+ * hc-mvs_amd/csrc/pm_common.h -- what the host API and the gfx950 kernels share: the structures of an estimate (pm_types.h), those of a
+ * sweep launch and the launch wrappers.
  */
 #ifndef HCMVS_PM_COMMON_H
 #define HCMVS_PM_COMMON_H
@@ -7,73 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility> // std::integer_sequence: the kernel tables of pm_kernels.hip
+#include "pm_types.h" // after the runtime header: EstConst::dn is a float4*
 #include "sweep_plan.h"
 
 namespace hcmvs {
-
-constexpr int kHalfWindow = 7;      // nSizeHalfWindow, DepthMap.h:354 (fixed border, DepthMap.cpp:442-447)
-// The reference fixes nSizeHalfWindow = 7 / nTexels = 64 at compile time (DepthMap.h:354-358).  Patches beyond that
-// (BASELINE.json configs[4]: 11 x 11 taps, adapthalfwin 10) generalise the two constants: the border every pass keeps
-// clear follows the half window, EstConst::border = max(7, adapthalfwin).
-constexpr int kMaxHalfWindow = 10;
-constexpr int kBigTaps = (kMaxHalfWindow + 1) * (kMaxHalfWindow + 1); // 121
-constexpr int kBigSlots = 128;      // tap slots of the big-patch tables (taps dealt round-robin to the lanes of a view group)
-constexpr int kMaxViews = 16;
-constexpr int kMaxSlots = 32;       // neighbour slots of one pixel (cross pattern: 4 * ceil(halfwin/step))
-constexpr int kProgressStride = 16; // ints between the progress words of consecutive rows (64 B)
-
-// per source view constants, one lane group reads its own view's entry (DepthMap.h:412-444 ViewData)
-struct DevView {
-	uint32_t byteOff; // start of the view's footprint image (launch_quads) relative to EstConst::imgBase
-	int32_t w, h;
-	float A[9];  // Hl * Hr = Kj Rj Ri^T Ki^-1 (computed in double on the host, held as float)
-	float Hm[3]; // Kj Rj (Ci - Cj)
-};
-
-// --n-viewspread (DepthMap.cpp:1504-1608): what a sweep worker needs of one source view j whose own maps are offered as hypotheses.
-// depth == null: the view offers none.  The maps have the view's image size.
-struct SpreadView {
-	const float* depth;     // w * h
-	const float* normal;    // w * h * 3, view j's camera frame
-	const float* conf;      // w * h
-	int32_t w, h;
-	double cx, cy, ifx, ify; // view j's principal point and 1 / focal
-	double Tz[3], tz;        // third row of R_ref R_j^T and of R_ref (C_j - C_ref): depth in the reference camera of a point of view j's
-};
-
-// uniform constants of one EstimateDepthMap call (DepthMap.cpp:386-439 DepthEstimator ctor)
-struct EstConst {
-	int32_t W, H, V;
-	int32_t border;         // max(kHalfWindow, adapthalfwin): pixels closer than this to an edge are not estimated
-	int32_t adapthalfwin, nRandomIters, itExternal, propHalfwin, propStep;
-	const float* ref;
-	const uint8_t* gra;
-	const DevView* views;
-	const char* imgBase;    // lowest source footprint-image address of this call (32-bit offsets from here)
-	float Hr[9];            // Ki^-1 (double on the host, held as float)
-	double cx, cy, ifx, ify; // reference principal point and 1/focal (Camera.h:299-312)
-	float dMin, dMax, dMinSqr, dMaxSqr;
-	float smoothBonusDepth, smoothBonusNormal, smoothSigmaDepth, smoothSigmaNormal;
-	float angle1Range, angle2Range;
-	float thConfSmall, thConfBig, thConfRand, thRobust, thKeep;
-	float depthRatio, pfScale;
-	uint32_t seed;
-	// working state: (depth, nx, ny, nz) per pixel + score per pixel
-	float4* dn;
-	float* conf;
-	int32_t* progress; // [rows * kProgressStride] pixels finished per logical row of this image (sweeps)
-	// restore-variant extra hypothesis (restore/libs/MVS/DepthMap.cpp:1527-1549): in sweep number hintIter every pixel also tries
-	// the estimate of the up-sampled coarser level, with a 0.1 bonus; null / -1 when not in use
-	const float* hintDepth;
-	const float* hintNormal;
-	int32_t hintIter;
-	// --ignore-mask-label (DepthMap.cpp:319-381): per pixel 1 = estimated, 0 = ignored (left out of the visiting order of every pass:
-	// the pixel keeps what ApplyIgnoreMask and the median left it); null when the reference view has no mask
-	const uint8_t* keep;
-	// view spread (SPREAD instances of the sweep): [V] entries in the estimate's view order; null when the call has it off, at outer
-	// iteration 0 or when no source view of the item offers maps
-	const SpreadView* spread;
-};
 
 struct SweepSync {
 	int32_t* ticket;   // [kMaxBatch] next row of every image of the batch, counted through the sweeps of the launch (row + sweep * rows)

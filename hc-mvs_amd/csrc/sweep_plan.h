@@ -6,6 +6,8 @@
 #ifndef HCMVS_SWEEP_PLAN_H
 #define HCMVS_SWEEP_PLAN_H
 
+#include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 namespace hcmvs {
@@ -57,6 +59,25 @@ struct SweepBatch {
 	int sweepSegment = -1;  // HCMVS_SWEEP_SEGMENT: columns per ticket; -1 automatic, 0 whole rows
 	int wavesPerRow = 0;    // HCMVS_WAVES_PER_ROW: 1..4; 0 automatic
 };
+// The tuning knobs of the environment as a context holds them.  Each argument is the variable's text, null when it is unset; a text
+// that does not spell one of the accepted values leaves the default, silently.
+struct SweepKnobs {
+	int lag = 1;        // HCMVS_SWEEP_LAG: columns a row starts behind the previous one; a number >= 1
+	int affinity = 1;   // HCMVS_XCD_AFFINITY: rows of an image prefer the workgroups of one XCD; any number, 0 turns it off
+	int perLaunch = 0;  // HCMVS_SWEEP_LAUNCHES: "per-sweep" 1, "one" 2 (SweepBatch::sweepPerLaunch)
+	int segment = -1;   // HCMVS_SWEEP_SEGMENT: columns per ticket, a number >= 0 (SweepBatch::sweepSegment)
+	int wavesPerRow = 0; // HCMVS_WAVES_PER_ROW: 1, 2, 3 or 4 (SweepBatch::wavesPerRow)
+};
+inline SweepKnobs parse_sweep_knobs(const char* lag, const char* affinity, const char* launches, const char* segment, const char* waves) {
+	SweepKnobs k;
+	if (lag && atoi(lag) >= 1) k.lag = atoi(lag);
+	if (affinity) k.affinity = atoi(affinity) != 0;
+	if (launches && strcmp(launches, "per-sweep") == 0) k.perLaunch = 1;
+	if (launches && strcmp(launches, "one") == 0) k.perLaunch = 2;
+	if (segment && atoi(segment) >= 0) k.segment = atoi(segment);
+	if (waves && atoi(waves) >= 1 && atoi(waves) <= 4) k.wavesPerRow = atoi(waves);
+	return k;
+}
 // One launch for the sweeps first .. first + count - 1 of every item (tickets, rowsDone and the progress words of the items must be zero)
 struct SweepLaunch {
 	int first, count;

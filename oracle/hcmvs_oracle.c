@@ -456,6 +456,22 @@ static void ctx_init(est_ctx* c, const hcor_view* ref, const hcor_view* srcs, in
 	c->thRobust = p->ncc_threshold_keep * 1.2f;
 }
 
+void hcor_estimate_consts(const hcor_view* ref, const hcor_view* srcs, int n_src, const hcor_params* p, float d_min, float d_max,
+                          hcor_est_consts* out) {
+	est_ctx c;
+	ctx_init(&c, ref, srcs, n_src, NULL, p, d_min, d_max);
+	memset(out, 0, sizeof *out);
+	memcpy(out->Af, c.Af, sizeof c.Af); memcpy(out->Hmf, c.Hmf, sizeof c.Hmf); memcpy(out->Hrf, c.Hrf, sizeof c.Hrf);
+	out->ifx = c.ifx; out->ify = c.ify;
+	out->dMin = c.dMin; out->dMax = c.dMax; out->dMinSqr = c.dMinSqr; out->dMaxSqr = c.dMaxSqr;
+	out->smoothBonusDepth = c.smoothBonusDepth; out->smoothBonusNormal = c.smoothBonusNormal;
+	out->smoothSigmaDepth = c.smoothSigmaDepth; out->smoothSigmaNormal = c.smoothSigmaNormal;
+	out->angle1Range = c.angle1Range; out->angle2Range = c.angle2Range;
+	out->thConfSmall = c.thConfSmall; out->thConfBig = c.thConfBig; out->thConfRand = c.thConfRand; out->thRobust = c.thRobust;
+	memcpy(out->spT, c.spT, sizeof c.spT); memcpy(out->spt, c.spt, sizeof c.spt);
+	memcpy(out->jifx, c.jifx, sizeof c.jifx); memcpy(out->jify, c.jify, sizeof c.jify);
+}
+
 /* per-pixel state (DM.h:460-476) */
 typedef struct {
 	int x, y;

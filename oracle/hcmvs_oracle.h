@@ -157,6 +157,22 @@ void hcor_correct_normal(const hcor_view* ref, int x, int y, float n[3], int ari
 float hcor_interpolate_pixel(const hcor_view* ref, int x, int y, int nx, int ny, float depth,
                              const float normal[3], float d_min, float d_max);
 
+/* What the estimator derives from the cameras and the options before any pixel is visited (DM.cpp:386-439, DM.h:412-444; the
+ * device association holds A = Hl Hr, Hm and Hr rounded to float), copied out as hcor_estimate holds it -- so that a test can
+ * compare the host plan of the product (hc-mvs_amd/csrc/est_plan.h), which derives the same numbers on its own, field by field.
+ * spT, spt: R_ref R_j^T and R_ref (C_j - C_ref) of view spread; jifx, jify: 1 / focal of view j. */
+typedef struct {
+	float Af[HCOR_MAX_VIEWS][9], Hmf[HCOR_MAX_VIEWS][3], Hrf[9];
+	double ifx, ify;
+	float dMin, dMax, dMinSqr, dMaxSqr;
+	float smoothBonusDepth, smoothBonusNormal, smoothSigmaDepth, smoothSigmaNormal;
+	float angle1Range, angle2Range;
+	float thConfSmall, thConfBig, thConfRand, thRobust;
+	double spT[HCOR_MAX_VIEWS][9], spt[HCOR_MAX_VIEWS][3], jifx[HCOR_MAX_VIEWS], jify[HCOR_MAX_VIEWS];
+} hcor_est_consts;
+void hcor_estimate_consts(const hcor_view* ref, const hcor_view* srcs, int n_src, const hcor_params* p, float d_min, float d_max,
+                          hcor_est_consts* out);
+
 /* ---- the path -------------------------------------------------------------------------------- */
 
 /* SD.cpp:758-1072 EstimateDepthMap for one reference view (defined subset).

@@ -49,6 +49,17 @@ class Cloud(C.Structure):
                 ("claim_mask", C.POINTER(C.c_uint8)), ("owner", C.POINTER(C.POINTER(C.c_uint16)))]
 
 
+class EstConsts(C.Structure):
+    """hcor_est_consts: what the estimator derives from the cameras and the options (hcor_estimate_consts)"""
+    _V = 16
+    _fields_ = [("Af", C.c_float * 9 * _V), ("Hmf", C.c_float * 3 * _V), ("Hrf", C.c_float * 9), ("ifx", C.c_double), ("ify", C.c_double),
+                ("dMin", C.c_float), ("dMax", C.c_float), ("dMinSqr", C.c_float), ("dMaxSqr", C.c_float),
+                ("smoothBonusDepth", C.c_float), ("smoothBonusNormal", C.c_float), ("smoothSigmaDepth", C.c_float), ("smoothSigmaNormal", C.c_float),
+                ("angle1Range", C.c_float), ("angle2Range", C.c_float),
+                ("thConfSmall", C.c_float), ("thConfBig", C.c_float), ("thConfRand", C.c_float), ("thRobust", C.c_float),
+                ("spT", C.c_double * 9 * _V), ("spt", C.c_double * 3 * _V), ("jifx", C.c_double * _V), ("jify", C.c_double * _V)]
+
+
 _lib = None
 
 
@@ -100,6 +111,8 @@ def lib():
         L.hcor_estimate.argtypes = est_args; L.hcor_estimate.restype = C.c_int
         L.hcor_pass_score.argtypes = est_args
         L.hcor_pass_sweep.argtypes = est_args[:5] + [C.c_int] + est_args[5:]
+        L.hcor_estimate_consts.argtypes = [C.POINTER(View), C.POINTER(View), C.c_int, C.POINTER(Params), C.c_float, C.c_float, C.POINTER(EstConsts)]
+        L.hcor_estimate_consts.restype = None
         L.hcor_pass_end.argtypes = [C.POINTER(Params), C.c_int, C.c_int, fp, fp, fp]
         u64p = C.POINTER(C.c_uint64)
         L.hcor_spread_stats.argtypes = [u64p, u64p, u64p, u64p, C.c_int]
@@ -248,6 +261,14 @@ def estimate(views, params, d_min, d_max, depth, normal, gra=None, keep=None, ma
                          fptr(n), fptr(c), C.byref(ev))
     assert rc == 0
     return d, n, c, ev.value
+
+
+def estimate_consts(views, params, d_min, d_max):
+    """the constants hcor_estimate would derive for views[0] (ref) against views[1:] (only K, R, C and the sizes are read)"""
+    ref = make_view(views[0]); srcs = make_view_array(views[1:])
+    out = EstConsts()
+    lib().hcor_estimate_consts(C.byref(ref), srcs, len(views) - 1, C.byref(params), d_min, d_max, C.byref(out))
+    return out
 
 
 def stats(reset=False):
