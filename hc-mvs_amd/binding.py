@@ -75,6 +75,23 @@ class InitStats(C.Structure):
                 ("cover_hits", C.c_uint64), ("ms_host", C.c_float), ("ms_device", C.c_float), ("device_bytes", C.c_uint64)]
 
 
+class HandoffItem(C.Structure):
+    _fields_ = [("src_depth", C.c_void_p), ("src_normal", C.c_void_p), ("src_w", C.c_int32), ("src_h", C.c_int32),
+                ("dst_depth", C.c_void_p), ("dst_normal", C.c_void_p), ("dst_w", C.c_int32), ("dst_h", C.c_int32),
+                ("d_min", C.c_float), ("d_max", C.c_float), ("status", C.c_int32),
+                ("n_valid", C.c_uint64), ("n_clamped", C.c_uint64), ("n_rescaled", C.c_uint64)]
+
+
+class HandoffStats(C.Structure):
+    _fields_ = [("n_pixels", C.c_uint64), ("n_valid", C.c_uint64), ("n_clamped", C.c_uint64), ("n_rescaled", C.c_uint64),
+                ("n_items", C.c_int32), ("n_empty", C.c_int32), ("ms_device", C.c_float)]
+
+
+HANDOFF_INIT, HANDOFF_HINT = 0, 1           # hcmvs_handoff_maps*: mode
+HANDOFF_OK, HANDOFF_EMPTY = 0, 1            # ... an item's status
+_HANDOFF_MODES = {"init": HANDOFF_INIT, "hint": HANDOFF_HINT}
+
+
 class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
@@ -103,6 +120,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_set_neighbors", "hcmvs_filter", "hcmvs_filter_sequence", "hcmvs_set_fuse_order", "hcmvs_fuse", "hcmvs_fuse_cloud", "hcmvs_estimate_point_colors",
            "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_default_view_select_params", "hcmvs_select_views",
            "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
+           "hcmvs_handoff_maps", "hcmvs_handoff_maps_device", "hcmvs_get_handoff_stats",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
 
@@ -129,6 +147,60 @@ def resize_area_up(src, dst_w, dst_h):
     if rc != 0:
         raise HcmvsError(rc, "resize_area_up failed")
     return out
+
+
+def _handoff_items(items):
+    """list of dicts (src_depth, src_normal, dst_depth, dst_normal: addresses; src_w, src_h, dst_w, dst_h[, d_min, d_max]) -> HandoffItem array"""
+    arr = (HandoffItem * max(len(items), 1))()
+    for a, it in zip(arr, items):
+        a.src_depth = it["src_depth"] or None; a.src_normal = it["src_normal"] or None
+        a.dst_depth = it["dst_depth"] or None; a.dst_normal = it["dst_normal"] or None
+        a.src_w, a.src_h, a.dst_w, a.dst_h = int(it["src_w"]), int(it["src_h"]), int(it["dst_w"]), int(it["dst_h"])
+        a.d_min = it.get("d_min", 0.0); a.d_max = it.get("d_max", 0.0)
+        a.status = -1
+    return arr
+
+
+def _handoff_results(arr, n):
+    return [dict(d_min=arr[i].d_min, d_max=arr[i].d_max, status=arr[i].status, n_valid=arr[i].n_valid, n_clamped=arr[i].n_clamped,
+                 n_rescaled=arr[i].n_rescaled) for i in range(n)]
+
+
+def _handoff_mode(mode):
+    return _HANDOFF_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def handoff_maps_raw(items, mode):
+    """hcmvs_handoff_maps on addresses of HOST buffers (items as Context.handoff_maps_device takes them).  Returns (status of the call,
+    per-item results); nothing raises, so a refusal can be looked at"""
+    arr = _handoff_items(items)
+    rc = lib().hcmvs_handoff_maps(arr, len(items), _handoff_mode(mode))
+    return rc, _handoff_results(arr, len(items))
+
+
+def handoff_maps(maps, mode):
+    """hcmvs_handoff_maps: the hand-off between two pyramid levels on host arrays, no context (pure host code; what the device form is
+    pinned to).  maps: list of dicts(depth (h, w), normal (h, w, 3), dst_w, dst_h[, d_min, d_max]) -- the previous level's maps, the size
+    wanted, and in mode "hint" the range to widen.  mode "init": the maps a level starts from (copied or cv::resize INTER_CUBIC, cleaned;
+    d_min / d_max come out).  mode "hint": the `restore` variant's extra hypothesis (INTER_AREA enlarging; d_min / d_max are widened).
+    Returns one dict per entry: depth (dst_h, dst_w), normal (dst_h, dst_w, 3), d_min, d_max, status (HANDOFF_OK, or HANDOFF_EMPTY: no
+    valid depth, d_min / d_max as given), n_valid, n_clamped, n_rescaled"""
+    keep, items = [], []
+    for m in maps:
+        d = np.ascontiguousarray(m["depth"], np.float32); n = np.ascontiguousarray(m["normal"], np.float32)
+        if d.ndim != 2 or n.shape != d.shape + (3,):
+            raise ValueError("handoff_maps: depth (h, w) and normal (h, w, 3) expected")
+        dw, dh = int(m["dst_w"]), int(m["dst_h"])
+        od = np.empty((max(dh, 0), max(dw, 0)), np.float32); on = np.empty((max(dh, 0), max(dw, 0), 3), np.float32)
+        keep.append((d, n, od, on))
+        items.append(dict(src_depth=d.ctypes.data, src_normal=n.ctypes.data, src_w=d.shape[1], src_h=d.shape[0], dst_depth=od.ctypes.data,
+                          dst_normal=on.ctypes.data, dst_w=dw, dst_h=dh, d_min=m.get("d_min", 0.0), d_max=m.get("d_max", 0.0)))
+    rc, res = handoff_maps_raw(items, mode)
+    if rc != 0:
+        raise HcmvsError(rc, "handoff_maps: refused (null pointer, size, overlap, shrinking hint, NaN range or unknown mode)")
+    for r, (_, _, od, on) in zip(res, keep):
+        r["depth"] = od; r["normal"] = on
+    return res
 
 
 def lib():
@@ -205,6 +277,9 @@ def lib():
         L.hcmvs_select_views.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), dp, dp, dp, C.c_uint64, fp, u32p, u32p, C.POINTER(ViewSelectParams),
                                          C.POINTER(ViewSelection), C.POINTER(ViewSelectStats)]
         L.hcmvs_resize_area_up.argtypes = [fp, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
+        L.hcmvs_handoff_maps.argtypes = [C.POINTER(HandoffItem), C.c_int32, C.c_int32]
+        L.hcmvs_handoff_maps_device.argtypes = [vp, C.POINTER(HandoffItem), C.c_int32, C.c_int32]
+        L.hcmvs_get_handoff_stats.argtypes = [vp, C.POINTER(HandoffStats)]
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.hcmvs_get_spread_stats.argtypes = [vp, C.POINTER(SpreadStats)]
@@ -383,6 +458,22 @@ class Context:
         st = InitStats()
         self._chk(lib().hcmvs_get_init_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in InitStats._fields_}
+
+    def handoff_maps_device(self, items, mode):
+        """hcmvs_handoff_maps_device: the hand-off between two pyramid levels (binding.handoff_maps states the two modes) for a batch of
+        images of any mix of sizes in one pass on the context's stream.  items: list of dicts(src_depth, src_normal, dst_depth, dst_normal
+        [DEVICE addresses], src_w, src_h, dst_w, dst_h[, d_min, d_max]); every pixel of the destination maps is written, bit-identical to
+        handoff_maps.  The call waits for the stream once; it is ordered before a following estimate*_device.  Returns one dict per item:
+        d_min, d_max, status (HANDOFF_OK / HANDOFF_EMPTY), n_valid, n_clamped, n_rescaled"""
+        arr = _handoff_items(items)
+        self._chk(lib().hcmvs_handoff_maps_device(self._h, arr, len(items), _handoff_mode(mode)))
+        return _handoff_results(arr, len(items))
+
+    def handoff_stats(self):
+        """hcmvs_get_handoff_stats: counters of the last handoff_maps_device call, summed over its items, and its device time"""
+        st = HandoffStats()
+        self._chk(lib().hcmvs_get_handoff_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in HandoffStats._fields_}
 
     def estimate(self, ref_id, src_ids, params, d_min, d_max, depth, normal, conf=None):
         """EstimateDepthMap on host maps (copied); returns (depth, normal, conf)."""

@@ -19,6 +19,8 @@
 #include "mesh_kernels.h"
 #include "view_kernels.h"
 #include "init_kernels.h"
+#include "handoff_kernels.h"
+#include "handoff_host.h"
 #include "dev_buf.h"
 
 #include <cmath>
@@ -118,6 +120,13 @@ struct hcmvs_ctx final : Reclaimer {
 	Event initEv[2]; // timing: around the kernel
 	hcmvs_init_stats initStats = {};
 	bool haveInitStats = false;
+	// hcmvs_handoff_maps_device: the result slots, the items and the prefix table of a call (handoff_plan.h HandoffLayout) on the device and
+	// their page-locked staging, through which the slots also come back; the call synchronises, so nothing of it is in flight afterwards
+	DevBuf handoffBuf{this};
+	PinnedBuf handoffPinned;
+	Event handoffEv[2]; // timing: around the kernels
+	hcmvs_handoff_stats handoffStats = {};
+	bool haveHandoffStats = false;
 
 	bool reclaim() override {
 		if (!pfState.capacity()) return false;
@@ -937,6 +946,88 @@ int hcmvs_resize_area_up(const float* src, int32_t sw, int32_t sh, int32_t ch, f
 		float* D = dst + (size_t)y * dw * ch;
 		for (size_t k = 0; k < (size_t)dw * ch; ++k) D[k] = row0[k] * b0 + row1[k] * b1;
 	}
+	return HCMVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the hand-off between pyramid levels (handoff_device.h states the rule, handoff_plan.h the checks and the launch plan)
+
+static std::vector<HandoffArgs> handoff_args(const hcmvs_handoff_item* items, int32_t n) {
+	std::vector<HandoffArgs> a;
+	if (!items || n < 1 || n > kHandoffMaxItems) return a; // handoff_check reports it
+	a.resize((size_t)n);
+	for (int i = 0; i < n; ++i)
+		a[(size_t)i] = {(uintptr_t)items[i].src_depth, (uintptr_t)items[i].src_normal, (uintptr_t)items[i].dst_depth, (uintptr_t)items[i].dst_normal,
+		                items[i].src_w, items[i].src_h, items[i].dst_w, items[i].dst_h, items[i].d_min, items[i].d_max};
+	return a;
+}
+static void handoff_report(hcmvs_handoff_item& it, int mode, const HandoffResult& r) {
+	it.status = handoff_finish(mode, r, &it.d_min, &it.d_max) ? HCMVS_HANDOFF_OK : HCMVS_HANDOFF_EMPTY;
+	it.n_valid = r.valid; it.n_clamped = r.clamped; it.n_rescaled = r.rescaled;
+}
+
+int hcmvs_handoff_maps(hcmvs_handoff_item* items, int32_t n, int32_t mode) {
+	const std::vector<HandoffArgs> args = handoff_args(items, n);
+	if (!handoff_check(args.empty() ? nullptr : args.data(), n, mode).empty()) return HCMVS_ERR_INVALID;
+	for (int i = 0; i < n; ++i) {
+		hcmvs_handoff_item& it = items[i];
+		HandoffResult r;
+		it.status = handoff_host(mode, handoff_geom(it.src_w, it.src_h, it.dst_w, it.dst_h), it.src_depth, it.src_normal, it.dst_depth, it.dst_normal, &it.d_min,
+		                         &it.d_max, r) ? HCMVS_HANDOFF_OK : HCMVS_HANDOFF_EMPTY;
+		it.n_valid = r.valid; it.n_clamped = r.clamped; it.n_rescaled = r.rescaled;
+	}
+	return HCMVS_OK;
+}
+
+int hcmvs_handoff_maps_device(hcmvs_ctx* c, hcmvs_handoff_item* items, int32_t n, int32_t mode) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const std::vector<HandoffArgs> args = handoff_args(items, n);
+	const std::string why = handoff_check(args.empty() ? nullptr : args.data(), n, mode);
+	if (!why.empty()) return fail(c, HCMVS_ERR_INVALID, "handoff_maps_device: %s", why.c_str());
+	HIPCHK(c, hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	const std::vector<int32_t> first = handoff_first(args.data(), n);
+	const HandoffLayout l = handoff_layout(n, (size_t)first[(size_t)n]);
+	for (Event& e : c->handoffEv) HIPCHK(c, e.ensure());
+	if (c->handoffPinned.reserve(handoff_layout(kHandoffMaxItems, 0).staged) != hipSuccess) return fail(c, HCMVS_ERR_HIP, "handoff_maps_device: no page-locked staging");
+	HIPCHK(c, c->handoffBuf.reserve(l.bytes, s));
+	char* h = c->handoffPinned.get();
+	HandoffResult* hr = (HandoffResult*)(h + l.results);
+	HandoffItem* hi = (HandoffItem*)(h + l.items);
+	uint64_t pixels = 0;
+	for (int i = 0; i < n; ++i) {
+		hr[i] = HandoffResult(); // written by the device
+		hi[i] = {items[i].src_depth, items[i].src_normal, items[i].dst_depth, items[i].dst_normal, handoff_geom(items[i].src_w, items[i].src_h, items[i].dst_w, items[i].dst_h)};
+		pixels += (uint64_t)items[i].dst_w * items[i].dst_h;
+	}
+	memcpy(h + l.first, first.data(), first.size() * sizeof(int32_t));
+	char* d = c->handoffBuf.get();
+	HIPCHK(c, hipMemcpyAsync(d, h, l.staged, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipEventRecord(c->handoffEv[0].get(), s));
+	launch_handoff(mode, (const HandoffItem*)(d + l.items), (const int32_t*)(d + l.first), n, first[(size_t)n], (HandoffResult*)(d + l.partials),
+	               (HandoffResult*)(d + l.results), s);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(c->handoffEv[1].get(), s));
+	HIPCHK(c, hipMemcpyAsync(hr, d + l.results, (size_t)n * sizeof(HandoffResult), hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipStreamSynchronize(s)); // the one synchronisation of the call: the ranges are final on return
+	hcmvs_handoff_stats st = hcmvs_handoff_stats();
+	st.n_pixels = pixels; st.n_items = n;
+	for (int i = 0; i < n; ++i) {
+		handoff_report(items[i], mode, hr[i]);
+		st.n_valid += items[i].n_valid; st.n_clamped += items[i].n_clamped; st.n_rescaled += items[i].n_rescaled;
+		st.n_empty += items[i].status == HCMVS_HANDOFF_EMPTY;
+	}
+	c->handoffStats = st;
+	c->haveHandoffStats = true;
+	return HCMVS_OK;
+}
+
+int hcmvs_get_handoff_stats(hcmvs_ctx* c, hcmvs_handoff_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	if (!c->haveHandoffStats) return fail(c, HCMVS_ERR_INVALID, "get_handoff_stats: no device hand-off has run on this context");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipEventElapsedTime(&c->handoffStats.ms_device, c->handoffEv[0].get(), c->handoffEv[1].get())); // the call synchronised: both events have passed
+	*out = c->handoffStats;
 	return HCMVS_OK;
 }
 

@@ -104,9 +104,35 @@ def _device_sync(dev):
         torch.cuda.synchronize(dev)
 
 
+HANDOFF_BATCH = 64      # HCMVS_MAX_BATCH: images one hand-off call serves
+
+
+def _device_map(m, dev):
+    """a map of the previous level as a contiguous float32 device tensor: a torch tensor is taken as it is (moved when it lives elsewhere),
+    a numpy array is copied in"""
+    if not torch.is_tensor(m):
+        import numpy as np
+        m = torch.from_numpy(np.ascontiguousarray(m, np.float32))
+    return m.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _handoff(ctx, dev, mode, jobs, w, h):
+    """binding.Context.handoff_maps_device over jobs = (image, depth (sh, sw), normal (sh, sw, 3) device tensors, destination depth and normal
+    addresses of w x h maps, d_min, d_max), in calls of at most HANDOFF_BATCH items.  Returns the per-item results"""
+    for img, d, n, _, _, _, _ in jobs:
+        if d.dim() != 2 or tuple(n.shape) != tuple(d.shape) + (3,):
+            raise ValueError("densify_scene: the previous maps of image %d are not depth (h, w) and normal (h, w, 3)" % img)
+    _device_sync(dev)       # torch filled the sources (and zeroed the slabs) on its own stream
+    out = []
+    for b0 in range(0, len(jobs), HANDOFF_BATCH):
+        out += ctx.handoff_maps_device([dict(src_depth=d.data_ptr(), src_normal=n.data_ptr(), src_w=d.shape[1], src_h=d.shape[0], dst_depth=dd, dst_normal=dn,
+                                             dst_w=w, dst_h=h, d_min=lo, d_max=hi) for _, d, n, dd, dn, lo, hi in jobs[b0:b0 + HANDOFF_BATCH]], mode)
+    return out
+
+
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
                   fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
-                  geometric_filter=None, gf_kw=None):
+                  geometric_filter=None, gf_kw=None, hints=None, fuse=True):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -142,7 +168,17 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                made on the host, copied in -- or a dict: dict(points=xyz (n,3) [, avg_depth=, add_corners=]) for the triangulation,
                dict(splat=xyz (n,3)) for the splat; the rank's context then rasterises the maps straight into its slab
                (binding.Context.triangulate_init_device / splat_init_device: only the face / point tables travel) and d_min, d_max come
-               from that call.  Same bits either way; the two kinds may be mixed
+               from that call.  Same bits either way; the two kinds may be mixed.  dict(previous=(depth (sh, sw), normal (sh, sw, 3))): the maps
+               of the previous level of the coarse-to-fine schedule (--n-initTriangulate 0), torch device tensors or numpy arrays of ANY size:
+               the rank's context hands them over on the device straight into its slab rows (binding.Context.handoff_maps_device, mode
+               "init": copied or cv::resize INTER_CUBIC, cleaned), all of the rank's images in calls of at most 64, and d_min, d_max come from
+               the call; an image whose previous map holds no valid depth raises ValueError naming it
+    hints:     optional {image id: (depth, normal)} of a coarser or equally sized level, tensors or arrays as above: the `restore` variant's
+               extra hypothesis.  The rank's context enlarges them on the device (mode "hint": INTER_AREA) into a hint buffer of 16 B per
+               pixel of the rank's images, the image's range -- after its init -- is widened by every enlarged depth, and the estimate offers
+               the hint on the last sweep of the last outer iteration (hcmvs_batch_item d_hint_depth / d_hint_normal)
+    fuse:      False: no final fusion -- the result holds only `maps` (and `ranges`: {id: (d_min, d_max)}), what an intermediate level of
+               the schedule needs.  The geometric filter, when asked for, still runs
     params:    binding.Params of the estimate; it_external / n_external_iters are set here
     masks:     optional {image id: (labels (h, w) u16 of any size, [ignored labels])}: --ignore-mask-label for those reference images
                (binding.Context.set_ignore_mask on the rank that estimates them)
@@ -185,7 +221,11 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     slabs = torch.zeros(n_local, FLOATS_PER_PIXEL * hw, dtype=torch.float32, device=dev)
     rng = torch.zeros(n_local, 2, dtype=torch.float32, device=dev)      # (d_min, d_max) travel with the maps
     zeroed = False      # the context writes a dict entry's row on its own stream: torch's zero fill of the slabs must have landed first
+    previous = []       # (row, image, depth, normal): the entries handed over from a previous level, after the loop, in batches
     for j, img in enumerate(mine):
+        if isinstance(init[img], dict) and "previous" in init[img]:
+            previous.append((j, img) + tuple(_device_map(m, dev) for m in init[img]["previous"]))
+            continue
         if isinstance(init[img], dict):
             e = init[img]
             if not zeroed:
@@ -202,13 +242,35 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             slabs[j, :hw] = torch.from_numpy(np.ascontiguousarray(d0, np.float32)).reshape(-1).to(dev)
             slabs[j, hw:4 * hw] = torch.from_numpy(np.ascontiguousarray(n0, np.float32)).reshape(-1).to(dev)
         rng[j, 0], rng[j, 1] = float(dmin), float(dmax)
+    if previous:        # the previous level's maps, of any size, straight into the slab rows: one pass per batch, the ranges come from it
+        done = _handoff(ctx, dev, "init", [(img, d, n, slabs[j].data_ptr(), slabs[j].data_ptr() + 4 * hw, 0.0, 0.0) for j, img, d, n in previous], w, h)
+        for (j, img, _, _), r in zip(previous, done):
+            if r["status"] != 0:
+                raise ValueError("densify_scene: the previous level's depth map of image %d holds no valid depth" % img)
+            rng[j, 0], rng[j, 1] = r["d_min"], r["d_max"]
+    hint_at = {}        # image -> (hint depth, hint normal) addresses: the `restore` variant's extra hypothesis of the last sweep
+    hintbuf = None
+    if hints:
+        rows = [(j, img) for j, img in enumerate(mine) if img in hints]
+        hintbuf = torch.empty(max(len(rows), 1), 4 * hw, dtype=torch.float32, device=dev)      # 16 B per pixel of the rank's hinted images
+        host_rng = rng.cpu()
+        jobs = []
+        for k, (j, img) in enumerate(rows):
+            d, n = (_device_map(m, dev) for m in hints[img])
+            hint_at[img] = (hintbuf[k].data_ptr(), hintbuf[k].data_ptr() + 4 * hw)
+            jobs.append((img, d, n) + hint_at[img] + (float(host_rng[j, 0]), float(host_rng[j, 1])))
+        for (j, img), r in zip(rows, _handoff(ctx, dev, "hint", jobs, w, h)):
+            rng[j, 0], rng[j, 1] = r["d_min"], r["d_max"]       # the range takes the enlarged map in
     allr = allgather_maps(rng, group)
     gathered = torch.empty(world * n_local, FLOATS_PER_PIXEL * hw, dtype=torch.float32, device=dev) if world > 1 else None
 
     def item_of(img, base):
         r = allr[slab_index(ids.index(img), world, n_local)]
-        return dict(ref_id=img, src_ids=list(srcs[img]), d_min=float(r[0]), d_max=float(r[1]), d_depth=base, d_normal=base + 4 * hw,
-                    d_conf=base + 16 * hw, seed_offset=img)
+        it = dict(ref_id=img, src_ids=list(srcs[img]), d_min=float(r[0]), d_max=float(r[1]), d_depth=base, d_normal=base + 4 * hw,
+                  d_conf=base + 16 * hw, seed_offset=img)
+        if img in hint_at:
+            it["d_hint_depth"], it["d_hint_normal"] = hint_at[img]
+        return it
 
     def my_items(store, row_of):
         by_class = {}
@@ -301,6 +363,20 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
         if geometric_filter not in ("adjust", "strict"):
             raise ValueError("densify_scene: geometric_filter is None, 'adjust' or 'strict', not %r" % (geometric_filter,))
         filter_stats = ctx.filter_sequence(ids, adjust=geometric_filter == "adjust", **(gf_kw or {}))   # in place, synchronised on return
+
+    def finish(cloud):
+        cloud["maps"] = maps
+        if filter_stats is not None:
+            cloud["filter"] = filter_stats
+        if viewspread:
+            ctx.set_viewspread(False)
+            for img in ids:
+                ctx.set_spread_maps_device(img, None, None, None)
+        cloud["_keep"] = (allm, allr, slabs, hintbuf)      # the registered device maps must outlive the context's use of them
+        return cloud
+
+    if not fuse:        # an intermediate level: the maps are the result
+        return finish(dict(ranges={img: (float(allr[slab_index(k, world, n_local), 0]), float(allr[slab_index(k, world, n_local), 1])) for k, img in enumerate(ids)}))
     # the cloud's buffers: as given, or counted -- a counting fusion first (no buffers), then the real one with exactly what it needs,
     # instead of half a point per pixel of the scene on every rank (66 GB of device and of host memory each at BASELINE configs[3]); a
     # fusion repeated on the maps a fusion has left makes the same decisions, so the cloud is the single pass's
@@ -315,12 +391,39 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     cloud = ctx.fuse(ids, cap, **(fuse_kw or {}))          # replicated on every rank: identical clouds
     if capacity is None and hasattr(ctx, "fuse_count"):
         cloud["n_depths"] = counted[1]                     # the depths the fusion visited before it invalidated any (SceneDensify.cpp:3461 logs that number)
-    cloud["maps"] = maps
-    if filter_stats is not None:
-        cloud["filter"] = filter_stats
-    if viewspread:
-        ctx.set_viewspread(False)
-        for img in ids:
-            ctx.set_spread_maps_device(img, None, None, None)
-    cloud["_keep"] = (allm, allr, slabs)                   # the registered device maps must outlive the context's use of them
-    return cloud
+    return finish(cloud)
+
+
+def densify_pyramid(ctx, stages, srcs, neighbors, order, init, **kw):
+    """The fork's coarse-to-fine schedule (run.sh: levels 3 -> 2 -> 2 -> 1 -> 1) as a chain of densify_scene calls whose maps never leave
+    the device: a level starts from the previous level's maps, or takes them as the extra hypothesis of its last sweep.
+
+    stages: one dict per level, in order: views (that level's images and cameras, as densify_scene takes them), params, mode, plus any
+            densify_scene keyword (n_external_iters, postfilter, ...; they override **kw).  mode is
+              "triangulate"  the level starts from `init` (a stage may bring its own under the key init); stage 0 always does.  An init of
+                             dict(points=...) entries is rasterised at the level's own size, so one `init` serves every level
+              "handoff"      it starts from the previous stage's maps (--n-initTriangulate 0): init = dict(previous=...) for every image
+              "restore"      it starts from `init` like "triangulate" and takes the previous stage's maps as hints (the `restore` binary)
+    Only the last stage fuses.  Every rank holds all maps of a stage after its all-gather, so the chain runs unchanged with several ranks.
+    Returns the last stage's result (densify_scene's)"""
+    if not stages:
+        raise ValueError("densify_pyramid: no stages")
+    prev = None
+    for k, stage in enumerate(stages):
+        st = dict(stage)
+        views, params, mode = st.pop("views"), st.pop("params"), st.pop("mode")
+        if mode not in ("triangulate", "handoff", "restore"):
+            raise ValueError("densify_pyramid: stage %d: mode is 'triangulate', 'handoff' or 'restore', not %r" % (k, mode))
+        if k == 0 and mode != "triangulate":
+            raise ValueError("densify_pyramid: stage 0 has no previous maps: its mode is 'triangulate'")
+        opts = dict(kw)
+        stage_init = st.pop("init", init)
+        opts.update(st)
+        opts["fuse"] = k == len(stages) - 1
+        if mode == "handoff":
+            stage_init = {i: dict(previous=prev["maps"][i][:2]) for i in order}
+        elif mode == "restore":
+            opts["hints"] = {i: prev["maps"][i][:2] for i in order}
+        res = densify_scene(ctx, views, srcs, neighbors, order, stage_init, params, **opts)
+        prev = res          # the previous stage's buffers live until the next stage has taken them over
+    return prev

@@ -246,6 +246,59 @@ int hcmvs_get_init_stats(hcmvs_ctx* ctx, hcmvs_init_stats* out);
  * and dst_h >= src_h, else HCMVS_ERR_INVALID. */
 int hcmvs_resize_area_up(const float* src, int32_t src_w, int32_t src_h, int32_t channels, float* dst, int32_t dst_w, int32_t dst_h);
 
+/* ---- the hand-off between two levels of the coarse-to-fine schedule (run.sh: levels 3, 2, 2, 1, 1) ---------------------------------
+ * The previous level's maps of an image become what the next level starts from, in one of two ways:
+ *   HCMVS_HANDOFF_INIT  (--n-initTriangulate 0, SceneDensify.cpp:527-553): they are the initial maps.  Equal sizes: copied; else
+ *       cv::resize INTER_CUBIC (Keys kernel A = -0.75, pixel centres aligned, replicated border; any ratio, per axis).  Then a depth
+ *       that is not > 0 (NaN included; the cubic kernel undershoots next to holes) becomes 0, and where a depth is left and the normal
+ *       has a length it is brought to length 1.  d_min = 0.9f * the smallest, d_max = 1.1f * the largest of ALL cleaned depths, the
+ *       zeros included.
+ *   HCMVS_HANDOFF_HINT  (the `restore` variant, restore/libs/MVS/SceneDensify.cpp:508-532): they are the extra hypothesis of the last
+ *       sweep (d_hint_depth / d_hint_normal above).  cv::resize INTER_AREA enlarging, exactly as hcmvs_resize_area_up; the range given
+ *       in d_min / d_max is widened by every enlarged depth hd BEFORE the clean-up, in raster order (lo = lo > hd ? hd : lo,
+ *       hi = hi > hd ? hi : hd -- so a NaN replaces hi and is replaced by whatever follows it); a pixel whose depth is not > 0 or
+ *       whose normal has no length gets hint depth 0 (its normal stays as enlarged), the others the normal at length 1.  On return
+ *       d_min = max(lo, 0) and d_max = hi, a zero of either sign as +0.
+ * Both forms below compute the same bits (a NaN is a NaN: its sign and payload are not part of that). */
+enum { HCMVS_HANDOFF_INIT = 0, HCMVS_HANDOFF_HINT = 1 };
+enum {
+	HCMVS_HANDOFF_OK = 0,
+	HCMVS_HANDOFF_EMPTY = 1 /* init mode: the handed-over map holds no valid depth (hi is not > 0).  The destination maps are written all the
+	                           same (depth 0 everywhere), d_min / d_max are left untouched; the call and its other items do not fail */
+};
+typedef struct {
+	const float *src_depth, *src_normal; /* src_w * src_h, src_w * src_h * 3 */
+	int32_t src_w, src_h;
+	float *dst_depth, *dst_normal;       /* dst_w * dst_h, dst_w * dst_h * 3: every pixel of both is written */
+	int32_t dst_w, dst_h;
+	float d_min, d_max;                  /* hint mode: in / out; init mode: out */
+	int32_t status;                      /* out: HCMVS_HANDOFF_* (set for every item of a call that was not refused) */
+	uint64_t n_valid;                    /* out: destination pixels left with a depth > 0 */
+	uint64_t n_clamped;                  /* out: ... whose resampled depth was <= 0 or NaN although a source sample that entered it was > 0 */
+	uint64_t n_rescaled;                 /* out: ... whose normal was divided by its length */
+} hcmvs_handoff_item;
+/* counters of the last hcmvs_handoff_maps_device call, summed over its items */
+typedef struct {
+	uint64_t n_pixels;   /* destination pixels written */
+	uint64_t n_valid;
+	uint64_t n_clamped;
+	uint64_t n_rescaled;
+	int32_t n_items;
+	int32_t n_empty;     /* items with status HCMVS_HANDOFF_EMPTY */
+	float ms_device;     /* HIP events around the kernels */
+} hcmvs_handoff_stats;
+/* HOST buffers, host code, no context (callable from any thread): the rule in a plain loop.  1 <= n_items <= HCMVS_MAX_BATCH.
+ * HCMVS_ERR_INVALID, before anything is read or written: a null pointer, a size below 1, a map of 2^29 pixels or more, hint mode with a
+ * destination smaller than the source in either direction or a range given as NaN, a destination that overlaps a source or another
+ * destination of the call (its own item's included: in place is not supported), an unknown mode. */
+int hcmvs_handoff_maps(hcmvs_handoff_item* items, int32_t n_items, int32_t mode);
+/* The same with every map in DEVICE memory (the items array itself is a host array): ONE pass for the whole batch of items of any
+ * mix of sizes (a launch over all pixels and a small one that folds the ranges), enqueued on the context's stream and therefore ordered before a following hcmvs_estimate*_device.  The ranges must be
+ * final on return, so the call synchronises with the stream -- once, however many items.  The same refusals, before anything reaches
+ * the device.  HCMVS_OK when every item ran; an item without a valid depth is reported in its status only. */
+int hcmvs_handoff_maps_device(hcmvs_ctx* ctx, hcmvs_handoff_item* items, int32_t n_items, int32_t mode);
+int hcmvs_get_handoff_stats(hcmvs_ctx* ctx, hcmvs_handoff_stats* out);
+
 /* ---- filter and fuse: work on the estimated maps registered per view ------------------------------------ */
 
 /* register the maps of view `id` (host buffers are copied).  normal may be NULL.  d_min/d_max: the depth range
