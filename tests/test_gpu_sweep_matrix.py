@@ -10,83 +10,15 @@ pass 1 of the ticket choice).
 Then the edges outside the matrix: more tickets than the chip holds workgroups, 9 and 17 items with and without XCD affinity,
 HCMVS_SWEEP_LAG, one sweep in one launch, no sweep at all, ragged and over-long stretches.
 
-Every configuration gets a fresh Context (the knobs are read in hcmvs_create).  The oracle runs once per item and module."""
-import importlib
-
-import numpy as np
+Every configuration gets a fresh Context (the knobs are read in hcmvs_create).  The oracle runs once per item (sweep_matrix_run.py, shared
+with test_gpu_sweep_matrix_flavours.py)."""
 import pytest
 
-import oracle_lib as O
 import sweep_matrix as M
 import sweep_plan_lib as P
+from sweep_matrix_run import run as _run, want as _want
 
 pytestmark = pytest.mark.gpu
-
-binding = importlib.import_module("hc-mvs_amd.binding")
-
-KNOBS = ("HCMVS_WAVES_PER_ROW", "HCMVS_SWEEP_LAUNCHES", "HCMVS_SWEEP_SEGMENT", "HCMVS_XCD_AFFINITY", "HCMVS_SWEEP_LAG")
-
-_ORACLE = {}
-
-
-def _want(key, item, kw, seed_offset):
-    """the oracle's (depth, normal, conf, evals) of one item, computed once per module (device association, row order, 8 threads)"""
-    key = (key, tuple(sorted(kw.items())), seed_offset)
-    if key not in _ORACLE:
-        po = O.default_params(arith_mode=O.ARITH_DEVICE, order=O.ORDER_ROWS, n_threads=8, **kw)
-        po.seed = kw["seed"] + seed_offset
-        if item["hint"] is not None:
-            po.hint_depth = O.fptr(item["hint"][0]); po.hint_normal = O.fptr(item["hint"][1])
-        _ORACLE[key] = O.estimate(item["views"], po, item["dmin"], item["dmax"], item["d0"], item["n0"])
-    return _ORACLE[key]
-
-
-def _compare(got, want, what):
-    for g, w, n in zip(got, want, ("depth", "normal", "conf")):
-        if not np.array_equal(g, w):
-            bad = np.argwhere(g != w)
-            raise AssertionError("%s: %s differs at %d elements, first %s: gpu %r oracle %r" %
-                                 (what, n, len(bad), bad[0], g[tuple(bad[0])], w[tuple(bad[0])]))
-
-
-def _run(monkeypatch, scenes, wants, offsets, kw, knobs, n_launches):
-    """one estimate_batch_device over the scenes' reference views in a fresh context created under `knobs`: maps, evaluation count and the
-    number of sweep launches"""
-    import torch
-    dev = torch.device("cuda:0")
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in knobs.items():
-        assert k in KNOBS
-        monkeypatch.setenv(k, str(v))
-    what = " ".join("%s=%s" % (k[6:], v) for k, v in knobs.items())
-    c = binding.Context(0)
-    try:
-        items, held = [], []
-        vid = 0
-        for sc, off in zip(scenes, offsets):
-            ids = list(range(vid, vid + len(sc["views"])))
-            vid += len(ids)
-            for i, v in zip(ids, sc["views"]):
-                c.upload_view(i, v["gray"], v["K"], v["R"], v["C"])
-            td = torch.from_numpy(sc["d0"]).to(dev); tn = torch.from_numpy(sc["n0"]).to(dev); tc = torch.zeros_like(td)
-            it = dict(ref_id=ids[0], src_ids=ids[1:], d_min=sc["dmin"], d_max=sc["dmax"], d_depth=td.data_ptr(), d_normal=tn.data_ptr(),
-                      d_conf=tc.data_ptr(), seed_offset=off)
-            if sc["hint"] is not None:
-                hd = torch.from_numpy(sc["hint"][0]).to(dev); hn = torch.from_numpy(sc["hint"][1]).to(dev)
-                it.update(d_hint_depth=hd.data_ptr(), d_hint_normal=hn.data_ptr()); held.append((hd, hn))
-            held.append((td, tn, tc)); items.append(it)
-        torch.cuda.synchronize()
-        c.estimate_batch_device(items, binding.default_params(**kw))
-        c.synchronize()
-        st = c.stats()      # (a sweep worker that gave up waiting raises here)
-        for i, (h, want) in enumerate(zip([h for h in held if len(h) == 3], wants)):
-            _compare([t.cpu().numpy() for t in h], want[:3], "%s, item %d" % (what, i))
-        assert st.evals == sum(w[3] for w in wants), what
-        assert st.n_sweep_launches == n_launches, what
-    finally:
-        c.close()
-
 
 def _knobs(launches, segment, waves, **more):
     k = {"HCMVS_SWEEP_LAUNCHES": launches, "HCMVS_SWEEP_SEGMENT": segment, "HCMVS_WAVES_PER_ROW": waves}

@@ -1,7 +1,9 @@
 """The ledger of tests/sweep_matrix.py, on the CPU: which sweep-kernel instances and launch shapes the matrix of
 test_gpu_sweep_matrix.py launches, read from the launch plan (hc-mvs_amd/csrc/sweep_plan.h through tests/sweep_plan_shim.cpp, g++ alone).
 It must be EVERY plain instance the library holds (MASK = SPREAD = false: 40 of the 152) in every shape plan_sweeps can give it, so that a
-later change to plan_sweeps or to the matrix cannot silently drop an instance from the GPU's oracle coverage."""
+later change to plan_sweeps or to the matrix cannot silently drop an instance from the GPU's oracle coverage.  The other 112 (MASK, SPREAD,
+MASK + SPREAD) have the same ledger in test_sweep_matrix_flavours_plan.py, which also asserts that the four together are all 152: every
+instance the library holds is pinned to the oracle."""
 import itertools
 
 import pytest
