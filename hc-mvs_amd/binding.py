@@ -96,6 +96,14 @@ class SpreadStats(C.Structure):
     _fields_ = [("slots_scored", C.c_uint64), ("slots_accepted", C.c_uint64), ("slots_dropped", C.c_uint64), ("candidates_outside", C.c_uint64)]
 
 
+class PriorParams(C.Structure):
+    _fields_ = [("para_prior", C.c_float), ("sigma_prior", C.c_float), ("photo2geo", C.c_int32)]
+
+
+class PriorStats(C.Structure):
+    _fields_ = [("evals_prior", C.c_uint64), ("pixels_prior", C.c_uint64)]
+
+
 class FilterStats(C.Structure):
     _fields_ = [("n_processed", C.c_uint64), ("n_discarded", C.c_uint64), ("n_filtered", C.c_uint32), ("n_skipped", C.c_uint32),
                 ("batch", C.c_uint32), ("ms_device", C.c_float), ("device_bytes", C.c_uint64), ("image_processed", C.POINTER(C.c_uint64)),
@@ -122,7 +130,9 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
            "hcmvs_handoff_maps", "hcmvs_handoff_maps_device", "hcmvs_get_handoff_stats",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
-           "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats"]
+           "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats",
+           "hcmvs_default_prior_params", "hcmvs_set_prior_params", "hcmvs_set_depth_prior", "hcmvs_set_depth_prior_device",
+           "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -283,6 +293,13 @@ def lib():
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.hcmvs_get_spread_stats.argtypes = [vp, C.POINTER(SpreadStats)]
+        L.hcmvs_default_prior_params.argtypes = [C.POINTER(PriorParams)]
+        L.hcmvs_default_prior_params.restype = None
+        L.hcmvs_set_prior_params.argtypes = [vp, C.POINTER(PriorParams)]
+        L.hcmvs_set_depth_prior.argtypes = [vp, C.c_uint32, fp]
+        L.hcmvs_set_depth_prior_device.argtypes = [vp, C.c_uint32, vp]
+        L.hcmvs_estimate_sweeps_batch_device.argtypes = [vp, C.POINTER(BatchItem), C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32]
+        L.hcmvs_get_prior_stats.argtypes = [vp, C.POINTER(PriorStats)]
         _lib = L
     return _lib
 
@@ -293,6 +310,15 @@ def default_params(**kw):
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_prior_params(**kw):
+    p = PriorParams()
+    lib().hcmvs_default_prior_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
         setattr(p, k, v)
     return p
 
@@ -493,8 +519,8 @@ class Context:
                                               C.c_void_p(d_depth_ptr), C.c_void_p(d_normal_ptr),
                                               C.c_void_p(d_conf_ptr)))
 
-    def estimate_batch_device(self, items, params):
-        """items: list of dicts (ref_id, src_ids, d_min, d_max, d_depth, d_normal, d_conf [device pointers], seed_offset)"""
+    @staticmethod
+    def _batch_items(items):
         arr = (BatchItem * len(items))()
         keep = []
         for i, it in enumerate(items):
@@ -503,7 +529,51 @@ class Context:
             arr[i].seed_offset = it.get("seed_offset", 0); arr[i].d_min = it["d_min"]; arr[i].d_max = it["d_max"]
             arr[i].d_depth = it["d_depth"]; arr[i].d_normal = it["d_normal"]; arr[i].d_conf = it["d_conf"]
             arr[i].d_hint_depth = it.get("d_hint_depth"); arr[i].d_hint_normal = it.get("d_hint_normal")
+        arr._keep = keep
+        return arr
+
+    def estimate_batch_device(self, items, params):
+        """items: list of dicts (ref_id, src_ids, d_min, d_max, d_depth, d_normal, d_conf [device pointers], seed_offset)"""
+        arr = self._batch_items(items)
         self._chk(lib().hcmvs_estimate_batch_device(self._h, arr, len(items), C.byref(params)))
+
+    def estimate_sweeps_batch_device(self, items, params, first_sweep, n_sweeps):
+        """the reference's extra sweeps: sweeps first_sweep .. first_sweep + n_sweeps - 1 on maps that are the state an estimate leaves
+        between outer iterations (d_depth, d_normal, d_conf = the score), then the end pass as in estimate_batch_device; items as there"""
+        arr = self._batch_items(items)
+        self._chk(lib().hcmvs_estimate_sweeps_batch_device(self._h, arr, len(items), C.byref(params), int(first_sweep), int(n_sweeps)))
+
+    # ---- depth priors (--n-para_prior, --sigma-prior, --n-photo2geo; DepthMap.cpp:941-954) ------------------
+
+    def set_prior_params(self, para_prior=None, sigma_prior=None, photo2geo=None):
+        """the prior term's options for the estimates that follow; None keeps the reference's default (0.5, 0.2, 2)"""
+        p = default_prior_params()
+        if para_prior is not None:
+            p.para_prior = para_prior
+        if sigma_prior is not None:
+            p.sigma_prior = sigma_prior
+        if photo2geo is not None:
+            p.photo2geo = photo2geo
+        self._chk(lib().hcmvs_set_prior_params(self._h, C.byref(p)))
+
+    def set_depth_prior(self, vid, prior):
+        """the prior depth map of view vid as a reference view: (h, w) float32 on the host, copied; None removes it"""
+        if prior is None:
+            self._chk(lib().hcmvs_set_depth_prior(self._h, vid, None))
+            return
+        a = np.ascontiguousarray(prior, np.float32)
+        assert a.shape == tuple(self.shapes[vid])
+        self._chk(lib().hcmvs_set_depth_prior(self._h, vid, _f(a)))
+
+    def set_depth_prior_device(self, vid, d_prior_ptr):
+        """the same in device memory (w * h floats at the view's size), caller-owned, not copied; None removes it"""
+        self._chk(lib().hcmvs_set_depth_prior_device(self._h, vid, C.c_void_p(d_prior_ptr) if d_prior_ptr else None))
+
+    def prior_stats(self):
+        """counters of the prior term of the last estimate: dict(evals_prior, pixels_prior)"""
+        s = PriorStats()
+        self._chk(lib().hcmvs_get_prior_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in PriorStats._fields_}
 
     def stats(self):
         s = Stats()

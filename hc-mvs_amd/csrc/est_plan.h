@@ -64,7 +64,10 @@ enum EstBad {
 	kEstSrcClass,   // item `at`: not the source-count class (1-8 or 9-16) of item 0
 	kEstNull,       // item `at`: no source ids or no in/out maps
 	kEstDepthRange, // item `at`: not 0 <= d_min < d_max
-	kEstBorder      // item `at`: its reference image has no pixel inside the border
+	kEstBorder,     // item `at`: its reference image has no pixel inside the border
+	kEstPriorHint,  // item `at` has the `restore` hint in effect while an item of the batch has an active depth prior
+	kEstPriorSpread, // item `at` has view spread doing work while an item of the batch has an active depth prior
+	kEstSweepRange  // sweeps-only call: first_sweep < 0, n_sweeps < 1 or an index beyond HCMVS_MAX_SWEEP_INDEX
 };
 struct EstCheck {
 	EstBad broken = kEstOk;
@@ -161,8 +164,8 @@ inline void est_spread_consts(const EstCamera& ref, const EstCamera& s, SpreadVi
 }
 
 // what plan_sweeps needs of an item whose constants and pointers are set
-inline SweepItem est_sweep_item(const EstConst& k, int nSweeps) {
-	return {k.H - 2 * k.border, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == nSweeps - 1, k.keep != nullptr, k.spread != nullptr};
+inline SweepItem est_sweep_item(const EstConst& k, int nSweeps, bool prior = false) {
+	return {k.H - 2 * k.border, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == nSweeps - 1, k.keep != nullptr, k.spread != nullptr, prior};
 }
 
 // ---- the image window ----
@@ -190,6 +193,45 @@ inline EstWindow est_image_window(const uint64_t* addr, const size_t* bytes, int
 	Carve slab;
 	for (int v = 0; v < n; ++v) off[v] = (uint32_t)slab(bytes[v]);
 	return {slab.size >= kEstWindowLimit ? kEstWindowRefused : kEstWindowSlab, 0, slab.size};
+}
+
+// ---- depth priors (DepthMap.cpp:941-954) ----
+// what hcmvs_set_prior_params refuses: para_prior outside [0, 1] or not finite, sigma_prior not > 0 (or not finite), photo2geo < 0
+enum PriorBad { kPriorOk = 0, kPriorPara, kPriorSigma, kPriorPhoto2geo };
+inline PriorBad est_check_prior_params(const hcmvs_prior_params& pp) {
+	if (!(pp.para_prior >= 0.f && pp.para_prior <= 1.f)) return kPriorPara; // (a NaN fails both comparisons)
+	if (!(pp.sigma_prior > 0.f) || !(pp.sigma_prior < INFINITY)) return kPriorSigma;
+	if (pp.photo2geo < 0) return kPriorPhoto2geo;
+	return kPriorOk;
+}
+// the active-prior rule: a prior is registered for the reference view, the term has weight, and the outer iteration has reached photo2geo
+inline bool est_prior_active(bool registered, const hcmvs_prior_params& pp, const hcmvs_params& p) {
+	return registered && pp.para_prior > 0.f && p.it_external >= pp.photo2geo;
+}
+// the term's constants (PriorItem::prior itself is the caller's pointer): score * keep + (2 * (1 - exp(dd^2 * sigma))) * para.
+// countIter: the sweep in which the pixels with a usable prior are counted; -1: the init-score pass counts them
+inline void est_prior_consts(const hcmvs_prior_params& pp, int countIter, PriorItem& k) {
+	k.keep = 1.f - pp.para_prior;
+	k.para = pp.para_prior;
+	k.sigma = -1.f / (2.f * (pp.sigma_prior * pp.sigma_prior));
+	k.countIter = countIter;
+}
+// Per item of a batch: has an active prior, has the hint in effect (est_uses_hint), has view spread doing work (est_view_spreads of some
+// source view).  A batch is one set of launches, so an active prior anywhere in it is refused together with a hint or with view spread
+// at work anywhere in it; `at` is the first item with the hint (or, failing that, with view spread) that stands in the way.
+inline EstCheck est_check_prior_batch(const bool* priorActive, const bool* hintInEffect, const bool* spreadWork, int nItems) {
+	bool any = false;
+	for (int i = 0; i < nItems; ++i) any = any || priorActive[i];
+	if (!any) return {};
+	for (int i = 0; i < nItems; ++i) if (hintInEffect[i]) return {kEstPriorHint, i};
+	for (int i = 0; i < nItems; ++i) if (spreadWork[i]) return {kEstPriorSpread, i};
+	return {};
+}
+// the sweeps-only call (hcmvs_estimate_sweeps_batch_device): a sweep's random stream is it_external * 64 + 1 + index, and stream
+// (it_external + 1) * 64 is the next outer iteration's init-score pass, so an index has room up to HCMVS_MAX_SWEEP_INDEX = 62
+inline EstCheck est_check_sweeps(int firstSweep, int nSweeps) {
+	if (firstSweep < 0 || nSweeps < 1 || firstSweep > HCMVS_MAX_SWEEP_INDEX || nSweeps > HCMVS_MAX_SWEEP_INDEX + 1 - firstSweep) return {kEstSweepRange, -1};
+	return {};
 }
 
 // ---- view spread: a launch must not read what it writes ----

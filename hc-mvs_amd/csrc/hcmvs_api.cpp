@@ -42,7 +42,7 @@ constexpr uint32_t kMaxViewId = 65536;      // view ids, and the ids a neighbour
 
 struct View {
 	View() = default;
-	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), keep(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r) {}
+	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), keep(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r), priorMem(r) {}
 	int w = 0, h = 0;
 	float* gray = nullptr;   // device: the caller's (hcmvs_set_view_device) or grayMem
 	uint8_t* bgr = nullptr;  // device or null: the caller's or bgrMem
@@ -60,6 +60,9 @@ struct View {
 	// --n-viewspread: the maps this view offers as a SOURCE view (hcmvs_set_spread_maps_device; the caller's, of the view's size)
 	const float *sDepth = nullptr, *sNormal = nullptr, *sConf = nullptr;
 	bool rescaled = false; // made by hcmvs_rescale_view: never spreads
+	// depth prior of the view as a REFERENCE view, w * h floats: the caller's (hcmvs_set_depth_prior_device) or priorMem; null = none
+	const float* prior = nullptr;
+	DevBuf priorMem;
 };
 
 } // namespace
@@ -85,7 +88,7 @@ struct hcmvs_ctx final : Reclaimer {
 	DevBuf maskStage{this}; // hcmvs_set_ignore_mask: the label image and the ignored labels on their way in
 	// host-path staging
 	DevBuf sDepth{this}, sNormal{this}, sConf{this};
-	DevBuf dViews{this};                  // DevView [kMaxBatch][kMaxViews]
+	DevBuf dViews{this};                  // DevView [kMaxBatch][kViewSlotEntries]: an item's views, then its PriorItem (pm_types.h)
 	std::vector<DevView> hViews;          // host copy handed to hipMemcpyAsync (must outlive the call)
 	DevBuf dItems{this};                  // EstConst [kMaxBatch]
 	std::vector<EstConst> hItems;
@@ -93,9 +96,11 @@ struct hcmvs_ctx final : Reclaimer {
 	std::vector<SpreadView> hSpread;
 	int viewspread = 0;                   // hcmvs_set_viewspread
 	bool haveSpreadStats = false;         // the last estimate ran with view spread in effect
+	hcmvs_prior_params prior = {0.5f, 0.2f, 2}; // hcmvs_set_prior_params (the reference's defaults)
+	bool havePriorStats = false;          // the last estimate had an item with an active prior
 	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
 	SweepKnobs knobs;                     // the HCMVS_* tuning knobs of the environment (sweep_plan.h)
-	DevBuf evals{this};                   // unsigned long long [4]
+	DevBuf evals{this};                   // unsigned long long [16]: SweepSync::evals
 	Event ev[4];                          // timing: before the init score, the sweeps, the end pass, and after it
 	int lastSweeps = 0, lastSweepLaunches = 0;
 	bool haveStats = false;
@@ -209,8 +214,8 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	c->stream = c->ownStream;
 	for (Event& e : c->ev)
 		if (e.ensure() != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
-	c->hViews.resize((size_t)kMaxBatch * kMaxViews); c->hItems.resize(kMaxBatch); c->hSpread.resize((size_t)kMaxBatch * kMaxViews);
-	if (c->dViews.reserve(sizeof(DevView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(64, c->stream) != hipSuccess ||
+	c->hViews.resize((size_t)kMaxBatch * kViewSlotEntries); c->hItems.resize(kMaxBatch); c->hSpread.resize((size_t)kMaxBatch * kMaxViews);
+	if (c->dViews.reserve(sizeof(DevView) * kViewSlotEntries * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(128, c->stream) != hipSuccess ||
 	    c->dSpread.reserve(sizeof(SpreadView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess ||
 	    c->dItems.reserve(sizeof(EstConst) * kMaxBatch, c->stream) != hipSuccess || c->sync.reserve(64 + sizeof(int32_t) * 2 * kMaxBatch, c->stream) != hipSuccess) {
 		hcmvs_destroy(c);
@@ -505,6 +510,15 @@ static int refuse_estimate(hcmvs_ctx* c, EstCheck bad, const hcmvs_batch_item* i
 	case kEstDepthRange: return fail(c, HCMVS_ERR_INVALID, "estimate: bad depth range [%g,%g)", items[bad.at].d_min, items[bad.at].d_max);
 	case kEstBorder:
 		return fail(c, HCMVS_ERR_INVALID, "estimate: view %u (%dx%d) has no pixel inside the %d px border", items[bad.at].ref_id, ref->w, ref->h, est_border(*p));
+	case kEstPriorHint:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: item %d (view %u) offers the `restore` hint in its last outer iteration while an item of the batch has an "
+		            "active depth prior: the prior term is not combined with the hint (remove one of the two)", bad.at, items[bad.at].ref_id);
+	case kEstPriorSpread:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: view spread has maps to try for item %d (view %u) while an item of the batch has an active depth prior: "
+		            "the prior term is not combined with view spread (hcmvs_set_viewspread(ctx, 0), as the reference's schedule runs priors)", bad.at, items[bad.at].ref_id);
+	case kEstSweepRange:
+		return fail(c, HCMVS_ERR_INVALID, "estimate_sweeps: first_sweep >= 0, n_sweeps >= 1 and a last index <= %d are needed (the random stream of a sweep "
+		            "is it_external * 64 + 1 + index)", HCMVS_MAX_SWEEP_INDEX);
 	}
 	return HCMVS_ERR_INVALID;
 }
@@ -513,7 +527,7 @@ static EstCamera camera_of(const View& v) { return {v.K, v.R, v.C, v.w, v.h}; }
 
 // Item `slot` of a batch into hItems / hViews / hSpread: the plan's constants (est_plan.h) and what only the context knows -- the views'
 // device images, made when first needed, the slot's working maps and the caller's pointers
-static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int n_items, const hcmvs_params* p) {
+static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int n_items, const hcmvs_params* p, bool sweepsOnly, int firstSweep) {
 	const hcmvs_batch_item& it = items[slot];
 	int rc = refuse_estimate(c, est_check_item(items, slot), items, n_items, p);
 	if (rc) return rc;
@@ -524,6 +538,7 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int
 	if (!ref.gray) return fail(c, HCMVS_ERR_INVALID, "estimate: view %u was registered without a gray image (fuse-only view)", it.ref_id);
 	rc = refuse_estimate(c, est_check_image(slot, ref.w, ref.h, *p), items, n_items, p, &ref);
 	if (rc) return rc;
+	const bool priorActive = est_prior_active(ref.prior != nullptr, c->prior, *p);
 	rc = ensure_slot(c, slot, (size_t)ref.w * ref.h, ref.h);
 	if (rc) return rc;
 	rc = ensure_gradient(c, ref);
@@ -542,10 +557,10 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int
 		imgAt[v] = (uintptr_t)s->quads.get(); imgBytes[v] = (size_t)s->w * s->h * sizeof(float4);
 	}
 	EstConst& k = c->hItems[slot];
-	DevView* hv = c->hViews.data() + (size_t)slot * kMaxViews;
-	const bool hint = it.d_hint_depth && it.d_hint_normal;
+	DevView* hv = c->hViews.data() + (size_t)slot * kViewSlotEntries;
+	const bool hint = !sweepsOnly && it.d_hint_depth && it.d_hint_normal; // (the sweeps-only entry never offers the hint)
 	est_item_consts(camera_of(ref), cam, n_src, *p, it.d_min, it.d_max, it.seed_offset, hint, k, hv);
-	k.ref = ref.gray; k.gra = ref.gra.get<uint8_t>(); k.views = c->dViews.get<DevView>() + (size_t)slot * kMaxViews;
+	k.ref = ref.gray; k.gra = ref.gra.get<uint8_t>(); k.views = c->dViews.get<DevView>() + (size_t)slot * kViewSlotEntries;
 	uint32_t imgOff[kMaxViews];
 	const EstWindow win = est_image_window(imgAt, imgBytes, n_src, imgOff);
 	if (win.kind == kEstWindowRefused) return fail(c, HCMVS_ERR_INVALID, "estimate: the source images of one item exceed 4 GiB");
@@ -570,28 +585,59 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int
 		est_spread_consts(camera_of(ref), cam[v], hs[v]);
 		k.spread = c->dSpread.get<SpreadView>() + (size_t)slot * kMaxViews;
 	}
+	PriorItem& pi = *prior_item(hv); // behind the item's views
+	memset(&pi, 0, sizeof pi);
+	if (priorActive) {
+		pi.prior = ref.prior;
+		est_prior_consts(c->prior, sweepsOnly ? firstSweep : -1, pi); // (no init-score pass: the call's first sweep counts the pixels with a usable prior)
+	}
 	return HCMVS_OK;
 }
 
-int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p) {
+// hcmvs_estimate_batch_device (sweepsOnly false: [mask] -> [median] -> init score -> n_estimation_iters sweeps -> end pass) and
+// hcmvs_estimate_sweeps_batch_device (sweepsOnly: import of depth, normal and conf -> sweeps firstSweep .. firstSweep + nSweeps - 1 -> end pass)
+static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p, bool sweepsOnly, int firstSweep, int nSweeps) {
 	if (!c) return HCMVS_ERR_INVALID;
 	if (!items || !p) return fail(c, HCMVS_ERR_INVALID, "estimate: null argument");
 	int rc = refuse_estimate(c, est_check_call(n_items, *p), items, n_items, p);
 	if (rc) return rc;
+	if (sweepsOnly) {
+		rc = refuse_estimate(c, est_check_sweeps(firstSweep, nSweeps), items, n_items, p);
+		if (rc) return rc;
+	}
+	{ // An active prior anywhere in the batch is refused together with a hint in effect or with view spread at work, before anything
+	  // reaches the device.  (Items that name unknown views are refused by build_item, in item order, as before.)
+		std::vector<char> flags(3 * (size_t)n_items, 0);
+		bool* priorActive = (bool*)flags.data(); bool* hintInEffect = priorActive + n_items; bool* spreadWork = hintInEffect + n_items;
+		for (int i = 0; i < n_items; ++i) {
+			const hcmvs_batch_item& it = items[i];
+			auto rv = c->views.find(it.ref_id);
+			priorActive[i] = rv != c->views.end() && est_prior_active(rv->second.prior != nullptr, c->prior, *p);
+			hintInEffect[i] = !sweepsOnly && est_uses_hint(*p, it.d_hint_depth && it.d_hint_normal);
+			for (int v = 0; it.src_ids && v < it.n_src && v < kMaxViews; ++v) {
+				auto sv = c->views.find(it.src_ids[v]);
+				if (sv != c->views.end() && est_view_spreads(c->viewspread, *p, sv->second.sDepth, sv->second.rescaled)) spreadWork[i] = true;
+			}
+		}
+		rc = refuse_estimate(c, est_check_prior_batch(priorActive, hintInEffect, spreadWork, n_items), items, n_items, p);
+		if (rc) return rc;
+	}
 	HIPCHK(c, hipSetDevice(c->device));
 	int maxRows = 0;
-	bool spread = false;
+	bool spread = false, prior = false;
 	hcmvs::SweepBatch batch;
-	batch.big = p->adapthalfwin > kHalfWindow; batch.nSweeps = p->n_estimation_iters; batch.nCU = c->nCU;
+	batch.big = p->adapthalfwin > kHalfWindow; batch.nSweeps = nSweeps; batch.firstSweep = firstSweep; batch.nCU = c->nCU;
 	batch.sweepPerLaunch = c->knobs.perLaunch; batch.sweepSegment = c->knobs.segment; batch.wavesPerRow = c->knobs.wavesPerRow;
 	batch.items.reserve(n_items);
 	for (int i = 0; i < n_items; ++i) {
-		rc = build_item(c, i, items, n_items, p);
+		rc = build_item(c, i, items, n_items, p, sweepsOnly, firstSweep);
 		if (rc) return rc;
 		const EstConst& k = c->hItems[i];
-		batch.items.push_back(est_sweep_item(k, batch.nSweeps));
+		const bool itemPrior = prior_item(c->hViews.data() + (size_t)i * kViewSlotEntries)->prior != nullptr;
+		batch.items.push_back(est_sweep_item(k, batch.nSweeps, itemPrior));
 		maxRows = std::max(maxRows, batch.items.back().rows);
 		spread = spread || k.spread;
+		prior = prior || itemPrior;
 	}
 	if (spread) { // a launch must not read what it writes
 		const EstOverlap o = est_spread_overlap(c->hItems.data(), c->hSpread.data(), items, n_items);
@@ -604,14 +650,16 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 	// same stream => the previous call's kernels are done with these tables before the copies land
 	if (spread) HIPCHK(c, hipMemcpyAsync(c->dSpread.get(), c->hSpread.data(), sizeof(SpreadView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
 	c->haveSpreadStats = spread;
-	HIPCHK(c, hipMemcpyAsync(c->dViews.get(), c->hViews.data(), sizeof(DevView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
+	c->havePriorStats = prior;
+	HIPCHK(c, hipMemcpyAsync(c->dViews.get(), c->hViews.data(), sizeof(DevView) * kViewSlotEntries * n_items, hipMemcpyHostToDevice, s));
 	HIPCHK(c, hipMemcpyAsync(c->dItems.get(), c->hItems.data(), sizeof(EstConst) * n_items, hipMemcpyHostToDevice, s));
-	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 64, s));
+	HIPCHK(c, hipMemsetAsync(c->evals.get(), 0, 128, s));
 	HIPCHK(c, hipMemsetAsync(c->sync.get(), 0, 64 + sizeof(int32_t) * 2 * kMaxBatch, s));
 
 	HIPCHK(c, hipEventRecord(c->ev[0].get(), s));
 	for (int i = 0; i < n_items; ++i) {
 		const EstConst& k = c->hItems[i];
+		if (sweepsOnly) { launch_import_state(k, items[i].d_depth, items[i].d_normal, items[i].d_conf, s); continue; }
 		const float* depthIn = items[i].d_depth;
 		// ApplyIgnoreMask on the initial maps, then the median (SceneDensify.cpp:776-860): an ignored pixel may come out of the median
 		// with a positive depth (five or more valid neighbours) -- kept, with its zero normal, as the reference does
@@ -620,7 +668,7 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 			launch_median3(items[i].d_depth, c->slots[i].tmpDepth.get<float>(), k.W, k.H, s);
 			depthIn = c->slots[i].tmpDepth.get<float>();
 		}
-		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s);
+		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s, batch.items[i].prior);
 	}
 	HIPCHK(c, hipEventRecord(c->ev[1].get(), s));
 	int32_t* sync = c->sync.get<int32_t>();
@@ -631,8 +679,8 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		for (int i = 0; i < n_items; ++i)
 			HIPCHK(c, hipMemsetAsync(c->slots[i].progress.get(), 0, (size_t)batch.items[i].rows * kProgressStride * sizeof(int32_t), s));
 		if (!launch_sweep(sa, l, s))
-			return fail(c, HCMVS_ERR_INVALID, "estimate: no sweep kernel for %d waves per row, big %d two %d pack %d hint %d mask %d spread %d",
-			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread);
+			return fail(c, HCMVS_ERR_INVALID, "estimate: no sweep kernel for %d waves per row, big %d two %d pack %d hint %d mask %d spread %d prior %d",
+			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread, l.v.prior);
 	}
 	c->lastSweepLaunches = (int)plan.size();
 	HIPCHK(c, hipEventRecord(c->ev[2].get(), s));
@@ -640,10 +688,18 @@ int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int
 		launch_end_pass(c->hItems[i], p->it_external == p->n_external_iters - 1 ? 1 : 0, items[i].d_depth, items[i].d_normal, items[i].d_conf, s);
 	HIPCHK(c, hipEventRecord(c->ev[3].get(), s));
 	HIPCHK(c, hipGetLastError());
-	c->lastSweeps = p->n_estimation_iters;
+	c->lastSweeps = nSweeps;
 	c->haveStats = true;
 	c->errPending = true;
 	return HCMVS_OK;
+}
+
+int hcmvs_estimate_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p) {
+	return estimate_batch(c, items, n_items, p, false, 0, p ? p->n_estimation_iters : 0);
+}
+int hcmvs_estimate_sweeps_batch_device(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* p, int32_t first_sweep,
+                                       int32_t n_sweeps) {
+	return estimate_batch(c, items, n_items, p, true, first_sweep, n_sweeps);
 }
 
 int hcmvs_estimate_device(hcmvs_ctx* c, uint32_t ref_id, const uint32_t* src_ids, int32_t n_src, const hcmvs_params* p,
@@ -675,6 +731,61 @@ int hcmvs_get_stats(hcmvs_ctx* c, hcmvs_stats* out) {
 	out->ms_sweep_avg = c->lastSweeps > 0 ? out->ms_sweeps / (float)c->lastSweeps : 0.f;
 	c->errPending = true;
 	return check_sweep_error(c);
+}
+
+// ---- depth priors (DepthMap.cpp:941-954) ----
+
+void hcmvs_default_prior_params(hcmvs_prior_params* p) {
+	if (!p) return;
+	p->para_prior = 0.5f; p->sigma_prior = 0.2f; p->photo2geo = 2; // DensifyPointCloud.cpp:162, :175, :183
+}
+int hcmvs_set_prior_params(hcmvs_ctx* c, const hcmvs_prior_params* p) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (!p) return fail(c, HCMVS_ERR_INVALID, "set_prior_params: null argument");
+	switch (est_check_prior_params(*p)) {
+	case kPriorOk: break;
+	case kPriorPara: return fail(c, HCMVS_ERR_INVALID, "set_prior_params: para_prior %g is not in [0, 1]", (double)p->para_prior);
+	case kPriorSigma: return fail(c, HCMVS_ERR_INVALID, "set_prior_params: sigma_prior %g is not a finite number > 0", (double)p->sigma_prior);
+	case kPriorPhoto2geo: return fail(c, HCMVS_ERR_INVALID, "set_prior_params: photo2geo %d is negative", p->photo2geo);
+	}
+	c->prior = *p;
+	return HCMVS_OK;
+}
+static int set_depth_prior(hcmvs_ctx* c, uint32_t id, const float* prior, bool copy) {
+	if (!c) return HCMVS_ERR_INVALID;
+	View* pv = find_view(c, "set_depth_prior", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	View& v = *pv;
+	HIPCHK(c, hipSetDevice(c->device));
+	if (!prior) { // (an estimate in flight may still read the old prior)
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		v.prior = nullptr;
+		v.priorMem.reset();
+		return HCMVS_OK;
+	}
+	if (v.rescaled) return fail(c, HCMVS_ERR_INVALID, "set_depth_prior: view %u was made by hcmvs_rescale_view: only a reference view's prior is ever read", id);
+	if (!copy) { v.prior = prior; v.priorMem.reset(); return HCMVS_OK; }
+	const size_t bytes = (size_t)v.w * v.h * sizeof(float);
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // (an estimate in flight may still read the copy that is about to be overwritten)
+	HIPCHK(c, v.priorMem.reserve(bytes, c->stream));
+	const int rc = upload_staged(c, v.priorMem.get(), prior, bytes);
+	if (rc) return rc;
+	v.prior = v.priorMem.get<float>();
+	return HCMVS_OK;
+}
+int hcmvs_set_depth_prior_device(hcmvs_ctx* c, uint32_t id, const float* d_prior) { return set_depth_prior(c, id, d_prior, false); }
+int hcmvs_set_depth_prior(hcmvs_ctx* c, uint32_t id, const float* prior) { return set_depth_prior(c, id, prior, true); }
+int hcmvs_get_prior_stats(hcmvs_ctx* c, hcmvs_prior_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	memset(out, 0, sizeof *out);
+	if (!c->haveStats) return fail(c, HCMVS_ERR_INVALID, "get_prior_stats: no estimate has run");
+	if (!c->havePriorStats) return HCMVS_OK; // the last estimate had no active prior: all zero
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	unsigned long long ev[2];
+	HIPCHK(c, hipMemcpy(ev, c->evals.get<unsigned long long>() + 8, sizeof ev, hipMemcpyDeviceToHost));
+	out->evals_prior = ev[0]; out->pixels_prior = ev[1];
+	return HCMVS_OK;
 }
 
 // ---- view spread (DensifyPointCloud --n-viewspread, DepthMap.cpp:1504-1608) ----

@@ -112,6 +112,11 @@ __device__ __forceinline__ uint8_t uniform_byte(const uint8_t* base, int idx) {
 	const uint32_t w = *(cu32p)(a & ~(uintptr_t)3);
 	return (uint8_t)(w >> (8u * (unsigned)(a & 3u)));
 }
+// One float of a map that no kernel of this launch writes (the depth prior), at a wave-uniform index: a scalar load, like uniform_byte
+__device__ __forceinline__ float uniform_float(const float* base, int idx) {
+	typedef __attribute__((address_space(4))) const uint32_t* cu32p;
+	return __uint_as_float(*(cu32p)((uintptr_t)base + 4u * (uintptr_t)(unsigned)idx));
+}
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -671,15 +676,43 @@ __device__ __forceinline__ void score_taps_big(const EstConst& c, const LaneCtx<
 	else { sum = bad ? __builtin_nanf("") : a; sumSq = b2; num = cnum; }
 }
 
+// DepthMap.cpp:941-950, the part of the prior term that depends on the pixel's prior and the hypothesis' depth only: 2 (1 - wP) para_prior
+// with wP = exp(-dd^2 / (2 sigma^2)), dd = |prior - depth| / prior (Util.inl:658-664 DepthSimilarity).  Association: a
+// true IEEE division by the prior, not a reciprocal; dd * dd times the precomputed -1 / (2 sigma^2), unfused; pm_expf as for the
+// smoothness factors; (2 (1 - wP)) para_prior.  Computed once per hypothesis; view_score adds it to every view that did not fail.
+__device__ __forceinline__ float prior_addend(float sigma, float para, float prior, float depth) {
+	const float dd = fabsf(prior - depth) / prior;
+	const float wP = pm_expf(HC_SQ(dd) * sigma);
+	return (2.f * (1.f - wP)) * para;
+}
+// what a PRIOR instance holds of its item's PriorItem while it works on the item (wave-uniform: scalar registers)
+struct PriorConst {
+	const float* map; // null: the item has no active prior
+	float keep, para, sigma;
+	int countIter;
+};
+__device__ __forceinline__ PriorConst prior_const(const EstConst& c) {
+	const HC_GLOBAL PriorItem* pi = (const HC_GLOBAL PriorItem*)(const HC_GLOBAL void*)(as_global(c.views) + kMaxViews);
+	return {pi->prior, pi->keep, pi->para, pi->sigma, pi->countIter};
+}
+// the validity rule of a prior value: finite and > 0; everything else -- 0, negative, NaN, infinite -- is "no prior here"
+__device__ __forceinline__ bool prior_usable(float prior) { return prior > 0.f && prior < __builtin_huge_valf(); }
+
 // DepthMap.cpp:597-615, 890-893: score of one view from its ZNCC sums, times the smoothness factor of the hypothesis
+// PRIOR: where the pixel carries a usable prior (pkeep >= 0: it is 1 - para_prior then, uniform over the wave, and -1 otherwise), the
+// view's score is blended with the hypothesis' addend (prior_addend) as s * (1 - para_prior) + addend, a multiplication and an addition,
+// unfused -- after the photometric scale and before the thRobust override, so that a failed view stays thRobust unblended
+// (DepthMap.cpp:558, 591)
+template <bool PRIOR = false>
 __device__ __forceinline__ float view_score(const EstConst& c, float sum, float sumSq, float num, bool viewBad, float invSumW,
-                                            float normSq0, float smoothF) {
+                                            float normSq0, float smoothF, float padd = 0.f, float pkeep = -1.f) {
 	const float normSq1 = sumSq - HC_SQ(sum) * invSumW;
 	const float nrmSq = normSq0 * normSq1;
 	float ncc = num / sqrtf(nrmSq);
 	ncc = ncc < -1.f ? -1.f : (ncc > 1.f ? 1.f : ncc);
 	float s = (1.f - ncc) * smoothF;
 	s = c.pfScale * s;
+	if constexpr (PRIOR) { if (pkeep >= 0.f) s = s * pkeep + padd; }
 	if (viewBad || !(nrmSq > 0.f)) s = c.thRobust;
 	return s;
 }
@@ -697,9 +730,10 @@ __device__ __forceinline__ void min2_merge(float& a1, float& a2, float b1, float
 
 // one hypothesis, everything in one go (init-score pass): the two best view scores of the views of L's set are merged into
 // (r1, r2); two_best() of those is the pixel's score (an estimate with 9..16 source views runs a second set of eight)
-template <int S, bool BIG, class ST>
+template <int S, bool BIG, class ST, bool PRIOR = false>
 __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>& L, const Patch<S>& P, const ST& st, float v0, float v1,
-                                            float smoothF, float depth, float n0, float n1, float n2, float& r1, float& r2) {
+                                            float smoothF, float depth, float n0, float n1, float n2, float& r1, float& r2,
+                                            float padd = 0.f, float pkeep = -1.f) {
 	float vA[9], vHm[3], H[9];
 	st.get_view(vA, vHm);
 	make_homography(c, vA, vHm, v0, v1, depth, n0, n1, n2, H);
@@ -712,7 +746,7 @@ __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>&
 		else if (P.a == 5) score_taps<S, 6>(c, L, P, st, H, sum, sumSq, num, viewBad);
 		else score_taps<S, 8>(c, L, P, st, H, sum, sumSq, num, viewBad);
 	}
-	const float s = view_score(c, sum, sumSq, num, viewBad, P.invSumW, P.normSq0, smoothF);
+	const float s = view_score<PRIOR>(c, sum, sumSq, num, viewBad, P.invSumW, P.normSq0, smoothF, padd, pkeep);
 	float m1 = L.vact ? s : __builtin_huge_valf(), m2 = __builtin_huge_valf();
 	min2_across<S>(m1, m2);
 	min2_merge(r1, r2, m1, m2);
@@ -726,10 +760,11 @@ __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>&
 // (1) and (3) cost one instruction stream per chunk instead of one per hypothesis.  Lane t gets the two best view scores of
 // hypothesis t merged into (r1, r2); two_best() of those is the hypothesis' score.  L selects the view set (views
 // L.view - L.vloc ... + 7): an estimate with 9..16 source views calls this twice per chunk.
-template <int S, bool BIG, bool PACK = false>
+// PRIOR: PA holds the prior addend of hypothesis t in lane t (prior_addend), pkeep is 1 - para_prior where the pixel's prior is usable, else -1
+template <int S, bool BIG, bool PACK = false, bool PRIOR = false>
 __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>& L, const Patch<S>& P, const LdsStore<S>& st, float v0, float v1,
                                             float F, float hd, float h0, float h1, float h2, unsigned long long todoIn, int baseIn,
-                                            int fallbackIn, float& r1, float& r2, unsigned& issued) {
+                                            int fallbackIn, float& r1, float& r2, unsigned& issued, float PA = 0.f, float pkeep = -1.f) {
 	// the list of hypotheses is the same in every lane: keep it (and the loop over it) on the scalar unit
 	const unsigned long long todo = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(todoIn >> 32)) << 32) |
 	                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)todoIn);
@@ -841,7 +876,9 @@ __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>&
 #endif
 		}
 		const float Fg = __shfl(F, g * 8, 64);
-		const float s = view_score(c, rs[0], rs[1], rs[2], false, P.invSumW, P.normSq0, Fg);
+		float pag = 0.f;
+		if constexpr (PRIOR) pag = __shfl(PA, ((todo >> (base + g)) & 1ull) ? base + g : fallback, 64); // the pair's hypothesis, as in (1)
+		const float s = view_score<PRIOR>(c, rs[0], rs[1], rs[2], false, P.invSumW, P.normSq0, Fg, pag, pkeep);
 		float m1 = vbase + pv < c.V ? s : __builtin_huge_valf(), m2 = __builtin_huge_valf();
 		min2_group<NV>(m1, m2);
 		// hypothesis base + p0 + k sits in lanes k * NV ... of (m1, m2)
@@ -1122,10 +1159,14 @@ struct SpreadCount { unsigned scored, accepted, dropped, outside; };
 // SPREAD: view spread is on in this launch (--n-viewspread, DepthMap.cpp:1504-1608; EstConst::spread): after its refinement trials a
 // pixel also tries what its source views' own maps hold around the place it projects to; every other launch runs the instance
 // without that code
-template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT, bool SPREAD>
+// PRIOR: some item of the launch has an active depth prior (PriorItem, pc); `prior` is this pixel's usable prior value, 0 where it
+// has none -- every evaluation of the pixel then blends the prior term (view_score); every other launch runs the instance without
+// that code.  A PRIOR instance has neither the hint nor view spread (sweep_variant_exists).
+template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT, bool SPREAD, bool PRIOR = false>
 __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S>& L, const LaneCtx<S>& L1, RowShared<NW>& sh, int& par, int wv,
                                               int x, int y, int q, int iter, const PixIn<S>& in, const Patch<S>& P,
-                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued, SpreadCount& spc STAMP_ARGS) {
+                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued, SpreadCount& spc, const PriorConst& pc, float prior STAMP_ARGS) {
+	static_assert(!PRIOR || !(HINT || SPREAD), "the prior term comes without the hint and without view spread");
 	const int W = c.W, lane = L.lane;
 	PixelGeom G;
 	pixel_geom(c, x, y, G);
@@ -1256,6 +1297,9 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 			}
 		}
 		const unsigned long long vmask = __ballot(hv);
+		const float pkeep = PRIOR && prior > 0.f ? pc.keep : -1.f; // (uniform over the wave)
+		float PA = 0.f; // the prior term's addend of hypothesis t in lane t
+		if constexpr (PRIOR) { if (prior > 0.f) PA = prior_addend(pc.sigma, pc.para, prior, hd); }
 		STAMP(3)
 		// ---- my share of the round: one smoothness pass per eight hypotheses, then the scorer ----
 		const int cnt = r1 - r0, per = (cnt + NW - 1) / NW, lo = r0 + wv * per, hi = (lo + per < r1 ? lo + per : r1);
@@ -1279,10 +1323,10 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 			STAMP(4)
 			if (todo) {
 				BLOCK(blk_score_chunk, 5)
-				score_chunk<S, BIG, PACK>(c, L, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, issued);
+				score_chunk<S, BIG, PACK, PRIOR>(c, L, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, issued, PA, pkeep);
 				if constexpr (TWO) {
 					unsigned again = 0;
-					score_chunk<S, BIG, PACK>(c, L1, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, again);
+					score_chunk<S, BIG, PACK, PRIOR>(c, L1, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, again, PA, pkeep);
 				}
 			}
 		}
@@ -1489,7 +1533,8 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 #endif
 // MASK: some item of the batch has a keep-mask (--ignore-mask-label); every other launch runs the instance without that code
 // SPREAD: the call has view spread on and some source view of the batch offers maps (EstConst::spread of some item is set)
-template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false, bool SPREAD = false>
+// PRIOR: some item of the batch has an active depth prior (PriorItem::prior of some item is set)
+template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false, bool SPREAD = false, bool PRIOR = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? HCMVS_OCC : 1, !BIG ? HCMVS_OCC : 2))) void sweep_kernel(const EstConst* __restrict__ items, int nItems, int maxRows, SweepSync sy,
                                                         int iter0, int nSweeps, int lag, int affinity, int segLen) {
 	__shared__ RowShared<NW> sh;
@@ -1499,6 +1544,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 	unsigned evals = 0, issued = 0;
 	unsigned long long taps = 0; // patch taps of the sequential algorithm's evaluations (per source view)
 	SpreadCount spc = {0u, 0u, 0u, 0u};
+	unsigned evalsPrior = 0, pixelsPrior = 0; // PRIOR: evaluations that blended the term; pixels with a usable prior (counted in one sweep)
 	int par = 0, rot = (int)blockIdx.x;
 	STAMP_DECL
 	RowPipe<S> pp;
@@ -1601,6 +1647,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			s1.view = L1.view;
 			s1.put_view(as_global(c.views) + (L1.vact ? L1.view : 0), L1.seg);
 		}
+		PriorConst pc = {nullptr, 0.f, 0.f, 0.f, -1};
+		if constexpr (PRIOR) pc = prior_const(c);
 		const int y = rev ? c.H - 1 - bd - r : bd + r;
 		pp.r = r; pp.y = y;
 		pp.upWord = as_global(c.progress) + (size_t)(r > 0 ? r - 1 : 0) * kProgressStride;
@@ -1664,6 +1712,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			if (q + 2 < q1) pp.tx2 = uniform_byte(c.gra, y * c.W + x + 2 * dx);
 			uint8_t km = 1; // keep-mask byte of this column, loaded with the pixel's own batch (MASK: some item of the batch has a mask)
 			if constexpr (MASK) km = uniform_byte(c.keep ? c.keep : c.gra, y * c.W + x); // (an item without one reads a byte it ignores)
+			// the pixel's prior, uniform over the wave like the keep byte and loaded with the pixel's own batch (PRIOR: some item of the batch
+			// has an active prior; an item without one reads a texel of its reference image and ignores it)
+			float prior = 0.f;
+			if constexpr (PRIOR) prior = uniform_float(pc.map ? pc.map : c.ref, y * c.W + x);
 			STAMP(12)
 			// ... and the patch weights are computed while they (and the previous row) arrive
 			Patch<S> P;
@@ -1697,8 +1749,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 				continue;
 			}
 			const unsigned e0 = evals;
-			process_pixel<S, NW, BIG, TWO, PACK, HINT, SPREAD>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued, spc STAMP_PASS);
+			if constexpr (PRIOR) prior = pc.map && prior_usable(prior) ? prior : 0.f;
+			process_pixel<S, NW, BIG, TWO, PACK, HINT, SPREAD, PRIOR>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued, spc, pc, prior STAMP_PASS);
 			taps += (unsigned long long)(evals - e0) * (unsigned)((P.a + 1) * (P.a + 1));
+			if constexpr (PRIOR) if (prior > 0.f) { evalsPrior += evals - e0; pixelsPrior += iter == pc.countIter ? 1u : 0u; }
 			STAMP(5) // (the pixel loop's back-edge is stamp 13's alone)
 		}
 		if (pp.fail) break;
@@ -1722,6 +1776,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			if (spc.accepted) atomicAdd(sy.evals + 5, (unsigned long long)spc.accepted);
 			if (spc.dropped) atomicAdd(sy.evals + 6, (unsigned long long)spc.dropped);
 			if (spc.outside) atomicAdd(sy.evals + 7, (unsigned long long)spc.outside);
+		}
+		if constexpr (PRIOR) if (wv == 0) { // the prior counters (hcmvs_get_prior_stats) follow the view-spread counters
+			if (evalsPrior) atomicAdd(sy.evals + 8, (unsigned long long)evalsPrior);
+			if (pixelsPrior) atomicAdd(sy.evals + 9, (unsigned long long)pixelsPrior);
 		}
 	}
 }
@@ -1749,7 +1807,18 @@ __global__ void import_kernel(EstConst c, const float* depthIn, const float* nor
 	}
 }
 
-template <int S, bool BIG, bool TWO = false, bool MASK = false>
+// the sweeps-only entry (hcmvs_estimate_sweeps_batch_device): the maps are the state an estimate leaves between outer iterations --
+// depth, normal and conf = the score of every pixel, taken as they are; nothing is scored
+__global__ void import_state_kernel(EstConst c, const float* depthIn, const float* normalIn, const float* confIn) {
+	const int n = c.W * c.H;
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+		c.dn[i] = make_float4(depthIn[i], normalIn[3 * i], normalIn[3 * i + 1], normalIn[3 * i + 2]);
+		c.conf[i] = confIn[i];
+	}
+}
+
+// PRIOR: the item has an active depth prior (its PriorItem): the pixel's one evaluation blends the prior term where its prior is usable
+template <int S, bool BIG, bool TWO = false, bool MASK = false, bool PRIOR = false>
 __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long long* evalsOut) {
 	LaneCtx<S> L;
 	lane_init<S>(c, L);
@@ -1769,8 +1838,10 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 	const int total = nrows * ncols;
 	const int wavesPerBlock = blockDim.x >> 6;
 	const int gw = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6), nw = gridDim.x * wavesPerBlock;
-	unsigned evals = 0;
+	unsigned evals = 0, evalsPrior = 0;
 	unsigned long long taps = 0;
+	PriorConst pc = {nullptr, 0.f, 0.f, 0.f, -1};
+	if constexpr (PRIOR) pc = prior_const(c);
 	const uint32_t stream0 = (uint32_t)c.itExternal * 64u;
 	for (int p = gw; p < total; p += nw) {
 		const int x = c.border + p % ncols, y = c.border + p / ncols;
@@ -1793,10 +1864,15 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 			random_normal(G, rand_unit(rk, 1u), rand_unit(rk, 2u), n0, n1, n2);
 		}
 		float m1 = __builtin_huge_valf(), m2 = __builtin_huge_valf();
-		score_pixel<S, BIG>(c, L, P, st, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2);
+		float padd = 0.f, pkeep = -1.f;
+		if constexpr (PRIOR) {
+			const float prior = uniform_float(pc.map, idx); // (one wave per pixel: uniform)
+			if (prior_usable(prior)) { padd = prior_addend(pc.sigma, pc.para, prior, d); pkeep = pc.keep; ++evalsPrior; }
+		}
+		score_pixel<S, BIG, RegStore<S>, PRIOR>(c, L, P, st, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep);
 		if constexpr (TWO) {
 			st1.copy_patch(st); // the pixel's patch tables (registers) with the second set's view constants
-			score_pixel<S, BIG>(c, L1, P, st1, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2);
+			score_pixel<S, BIG, RegStore<S>, PRIOR>(c, L1, P, st1, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep);
 		}
 		const float s = two_best(c, m1, m2);
 		++evals;
@@ -1810,6 +1886,10 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 		atomicAdd(evalsOut, (unsigned long long)evals);
 		atomicAdd(evalsOut + 1, (unsigned long long)evals);
 		atomicAdd(evalsOut + 2, taps);
+		if constexpr (PRIOR) if (evalsPrior) { // one evaluation per pixel: the pixels with a usable prior are the evaluations that blended
+			atomicAdd(evalsOut + 8, (unsigned long long)evalsPrior);
+			if (pc.countIter < 0) atomicAdd(evalsOut + 9, (unsigned long long)evalsPrior);
+		}
 	}
 }
 
@@ -1965,39 +2045,42 @@ void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, 
 	hipLaunchKernelGGL(apply_mask_kernel, dim3(2048), dim3(256), 0, s, keep, depth, normal, n);
 }
 
-// score_kernel<8, BIG, TWO, MASK> by (BIG, TWO, MASK): all eight exist
+// score_kernel<8, BIG, TWO, MASK, PRIOR> by (PRIOR, BIG, TWO, MASK): all sixteen exist
 template <class K, int N>
 struct KernelTable { K at[N]; };
 using ScoreKernel = void (*)(EstConst, unsigned long long*);
 template <int... I>
 static constexpr KernelTable<ScoreKernel, sizeof...(I)> score_table(std::integer_sequence<int, I...>) {
-	return {{score_kernel<8, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0>...}};
+	return {{score_kernel<8, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0>...}};
 }
-static constexpr auto kScoreKernels = score_table(std::make_integer_sequence<int, 8>{});
+static constexpr auto kScoreKernels = score_table(std::make_integer_sequence<int, 16>{});
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
-                       hipStream_t s) {
+                       hipStream_t s, bool prior) {
 	hipLaunchKernelGGL(import_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn);
 	// 9..16 views: two sets of eight
-	hipLaunchKernelGGL(kScoreKernels.at[(c.adapthalfwin > kHalfWindow ? 4 : 0) | (c.V > 8 ? 2 : 0) | (c.keep ? 1 : 0)], dim3(4096), dim3(256), 0, s, c, evals);
+	hipLaunchKernelGGL(kScoreKernels.at[(prior ? 8 : 0) | (c.adapthalfwin > kHalfWindow ? 4 : 0) | (c.V > 8 ? 2 : 0) | (c.keep ? 1 : 0)], dim3(4096), dim3(256), 0, s, c, evals);
+}
+void launch_import_state(const EstConst& c, const float* depthIn, const float* normalIn, const float* confIn, hipStream_t s) {
+	hipLaunchKernelGGL(import_state_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn, confIn);
 }
 
-// sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD> by SweepVariant: exactly the instances sweep_variant_exists admits, null elsewhere
+// sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD, PRIOR> by SweepVariant: exactly the instances sweep_variant_exists admits, null elsewhere
 using SweepKernel = void (*)(const EstConst*, int, int, SweepSync, int, int, int, int, int);
 constexpr int sweep_variant_index(SweepVariant v) {
-	return (v.nw - 1) << 6 | v.big << 5 | v.two << 4 | v.pack << 3 | v.hint << 2 | v.mask << 1 | (int)v.spread;
+	return v.prior << 8 | (v.nw - 1) << 6 | v.big << 5 | v.two << 4 | v.pack << 3 | v.hint << 2 | v.mask << 1 | (int)v.spread;
 }
 constexpr SweepVariant sweep_variant_at(int i) {
-	return {(i >> 6) + 1, (i & 32) != 0, (i & 16) != 0, (i & 8) != 0, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0};
+	return {((i >> 6) & 3) + 1, (i & 32) != 0, (i & 16) != 0, (i & 8) != 0, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0, (i & 256) != 0};
 }
 template <int I>
 static constexpr SweepKernel sweep_instance() {
 	constexpr SweepVariant v = sweep_variant_at(I);
-	if constexpr (sweep_variant_exists(v)) return sweep_kernel<8, v.nw, v.big, v.two, v.pack, v.hint, v.mask, v.spread>;
+	if constexpr (sweep_variant_exists(v)) return sweep_kernel<8, v.nw, v.big, v.two, v.pack, v.hint, v.mask, v.spread, v.prior>;
 	else return nullptr;
 }
 template <int... I>
 static constexpr KernelTable<SweepKernel, sizeof...(I)> sweep_table(std::integer_sequence<int, I...>) { return {{sweep_instance<I>()...}}; }
-static constexpr auto kSweepKernels = sweep_table(std::make_integer_sequence<int, 4 * 64>{});
+static constexpr auto kSweepKernels = sweep_table(std::make_integer_sequence<int, 2 * 4 * 64>{});
 
 bool launch_sweep(const SweepArgs& a, const SweepLaunch& l, hipStream_t s) {
 	const SweepKernel k = sweep_variant_exists(l.v) ? kSweepKernels.at[sweep_variant_index(l.v)] : nullptr;

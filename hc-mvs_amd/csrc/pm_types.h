@@ -82,5 +82,20 @@ struct EstConst {
 	const SpreadView* spread;
 };
 
+// Depth prior of one item (PRIOR instances of the kernels; DepthMap.cpp:941-954).  EstConst keeps its layout: the entry lives behind the
+// item's DevView table -- EstConst::views points at kViewSlotEntries entries, kMaxViews views and then this (prior_item()); only the
+// PRIOR instances ever look there.
+struct PriorItem {
+	const float* prior;   // the reference view's prior depth map, W * H, read and never written; null: the item has no active prior
+	float keep, para, sigma; // 1 - para_prior, para_prior, -1 / (2 sigma_prior^2)
+	int32_t countIter;    // the sweep index in which the pixels with a usable prior are counted; -1: the init-score pass counts them
+};
+constexpr int kViewSlotEntries = kMaxViews + 2; // DevView entries per item of the table EstConst::views points into
+static_assert(sizeof(PriorItem) <= 2 * sizeof(DevView) && (kMaxViews * sizeof(DevView)) % 8 == 0 && (kViewSlotEntries * sizeof(DevView)) % 8 == 0,
+              "the PriorItem behind an item's views must be 8-byte aligned in every slot");
+inline const PriorItem* prior_item(const DevView* views) { return (const PriorItem*)(const void*)(views + kMaxViews); }
+inline PriorItem* prior_item(DevView* views) { return (PriorItem*)(void*)(views + kMaxViews); }
+
+
 } // namespace hcmvs
 #endif

@@ -132,7 +132,7 @@ def _handoff(ctx, dev, mode, jobs, w, h):
 
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
                   fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
-                  geometric_filter=None, gf_kw=None, hints=None, fuse=True):
+                  geometric_filter=None, gf_kw=None, hints=None, fuse=True, priors=None, prior_params=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -189,6 +189,16 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                included (a Jacobi order).  interleave=True: the reference's own order -- the images are then estimated one after the other in
                EVERY outer iteration >= 1 (not only the filtered ones) and read the live maps: images < k as this iteration left them (in the
                last one: after the end pass), images > k from the previous one
+    priors:    optional {image id: prior depth map (h, w)}, numpy arrays (copied) or torch device tensors (float32, contiguous, read in place):
+               depth priors of those REFERENCE images (DepthMap.cpp:941-954), with prior_params =
+               dict(para_prior=, sigma_prior=, photo2geo=) (missing keys: the reference's 0.5, 0.2, 2).  The reference's schedule
+               (SceneDensify.cpp:983-1031): on outer iteration n_external_iters - 2, after the ordinary estimate of a batch, the priors of its
+               images are registered and two extra sweeps run on them, with the sweep indices n_estimation_iters and n_estimation_iters + 1
+               (binding.Context.estimate_sweeps_batch_device); on the last outer iteration the priors stay registered.  Whether an estimate
+               blends the term is the library's active-prior rule (para_prior > 0 and it_external >= photo2geo).  With fewer than two outer
+               iterations the priors are never registered -- the result then carries priors_used = False; nothing is raised.  Priors belong
+               to reference images, so ranks exchange nothing new: a rank registers those of its own images.  Not together with viewspread
+               or hints (ValueError: the library refuses the combination)
     geometric_filter: None (default: off), "adjust" or "strict": the depth-map filter stage (Scene::DenseReconstructionFilter,
                SceneDensify.cpp:4100-4185; binding.Context.filter_sequence) over ALL images between the final all-gather and the fusion.
                Replicated on every rank like the fusion -- every rank filters identical gathered maps with a deterministic kernel, and a
@@ -283,6 +293,27 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             base = allm[slab_index(k, world, n_local)].data_ptr()
             ctx.set_spread_maps_device(img, base, base + 4 * hw, base + 16 * hw)
 
+    priors = dict(priors) if priors else {}
+    if priors and (viewspread or hints):
+        raise ValueError("densify_scene: depth priors are not combined with viewspread or hints (the library refuses an active prior together with either)")
+    prior_it = int(n_external_iters) - 2 if priors else -1      # the outer iteration that registers the priors and runs the two extra sweeps
+    if priors:
+        ctx.set_prior_params(**(prior_params or {}))
+    prior_keep = []
+
+    def extra_sweeps(items):        # after the ordinary estimate of `items` on outer iteration prior_it: their priors, then sweeps N and N + 1
+        extra = [x for x in items if x["ref_id"] in priors]
+        for x in extra:
+            m = priors[x["ref_id"]]
+            if torch.is_tensor(m):
+                assert m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and tuple(m.shape) == (h, w)
+                prior_keep.append(m)
+                ctx.set_depth_prior_device(x["ref_id"], m.data_ptr())
+            else:
+                ctx.set_depth_prior(x["ref_id"], m)
+        if extra:
+            ctx.estimate_sweeps_batch_device(extra, p, p.n_estimation_iters, 2)
+
     if viewspread:
         ctx.set_viewspread(True)
     snapshot = torch.empty_like(slabs) if viewspread and world == 1 and not interleave and n_external_iters > 1 else None
@@ -315,6 +346,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                 owner = k % world
                 if owner == rank:
                     ctx.estimate_batch_device([item_of(img, allm[row].data_ptr())], p)
+                    if it == prior_it:
+                        extra_sweeps([item_of(img, allm[row].data_ptr())])
                     ctx.synchronize()
                 if world > 1:
                     if allm.is_cuda and dist.get_backend(group) == "gloo":      # one-GPU rehearsal: gloo moves host tensors
@@ -343,6 +376,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
         for cls, items in sorted(my_items(slabs, lambda img: mine.index(img)).items()):     # NO collective on the estimation path (view spread: the one above)
             for b0 in range(0, len(items), batch):
                 ctx.estimate_batch_device(items[b0:b0 + batch], p)
+                if it == prior_it:
+                    extra_sweeps(items[b0:b0 + batch])
         ctx.synchronize()
         if filt:
             allm = allgather_maps(slabs, group, out=gathered)  # every rank: every image's current maps
@@ -372,7 +407,12 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             ctx.set_viewspread(False)
             for img in ids:
                 ctx.set_spread_maps_device(img, None, None, None)
-        cloud["_keep"] = (allm, allr, slabs, hintbuf)      # the registered device maps must outlive the context's use of them
+        if priors:
+            cloud["priors_used"] = prior_it >= 0
+            for img in mine:
+                if img in priors and prior_it >= 0:
+                    ctx.set_depth_prior(img, None)
+        cloud["_keep"] = (allm, allr, slabs, hintbuf, prior_keep)      # the registered device maps must outlive the context's use of them
         return cloud
 
     if not fuse:        # an intermediate level: the maps are the result

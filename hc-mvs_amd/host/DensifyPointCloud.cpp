@@ -272,6 +272,7 @@ struct ImageData : PlanImage {
 	float *dDepth = nullptr, *dNormal = nullptr, *dConf = nullptr; // device maps, on the owner's device
 	float *gDepth = nullptr, *gNormal = nullptr, *gConf = nullptr; // the copy on the first device, where the post-filters and the fusion run (== d* when dev == 0)
 	float *dHintDepth = nullptr, *dHintNormal = nullptr;            // previous level's maps, resized (restore variant)
+	std::vector<float> prior;                                       // --depth-priors: the image's prior depth map (w * h), empty: none
 	// what a depth-map file says about its image: scene image ids, not the ids of resampled copies
 	DmapImage file_header() const { return DmapImage{name, id, w, h, cam.K, cam.R, cam.C, srcImages.empty() ? srcs : srcImages, dMin, dMax}; }
 };
@@ -591,6 +592,21 @@ bool estimate_images(Run& r, int d, const std::vector<uint32_t>& ids, const hcmv
 	if (hcmvs_estimate_batch_device(dctx, items.data(), (int32_t)items.size(), &pr) != HCMVS_OK || hcmvs_get_stats(dctx, &st) != HCMVS_OK) {
 		err = std::string("depth-map estimation failed (") + hcmvs_last_error(dctx) + ")";
 		return false;
+	}
+	// --depth-priors: after the ordinary estimate of outer iteration n - 2 the priors of these images are registered (they stay for the last
+	// iteration) and the reference's two extra sweeps run, with the sweep indices n_estimation_iters and + 1 (SceneDensify.cpp:983-1031)
+	if (prior_sweeps_after(r.o, pr.it_external)) {
+		std::vector<hcmvs_batch_item> extra;
+		for (const auto& itx : items) {
+			const ImageData& im = r.images[itx.ref_id];
+			if (im.prior.empty()) continue;
+			if (hcmvs_set_depth_prior(dctx, im.id, im.prior.data()) != HCMVS_OK) { err = std::string("registering the depth prior failed (") + hcmvs_last_error(dctx) + ")"; return false; }
+			extra.push_back(itx);
+		}
+		if (!extra.empty() && hcmvs_estimate_sweeps_batch_device(dctx, extra.data(), (int32_t)extra.size(), &pr, pr.n_estimation_iters, 2) != HCMVS_OK) {
+			err = std::string("the extra sweeps with the depth priors failed (") + hcmvs_last_error(dctx) + ")";
+			return false;
+		}
 	}
 	if (r.o.verbosity > 2)
 		for (const auto& itx : items)
@@ -1010,6 +1026,36 @@ bool set_ignore_masks(Run& r) {
 		       pxAll ? 100.0 * (double)pxIgnored / (double)pxAll : 0.0);
 	return true;
 }
+// --depth-priors <folder>: <folder>/depth%04u.prior.dmap per image that is estimated, a raw 'DR' depth map of the image's size at the run's
+// resolution level; only the depth is read.  A file of another size is an error naming it; an image without a file has no prior.
+bool load_depth_priors(Run& r) {
+	const Options& o = r.o;
+	if (o.depthPriors.empty()) return true;
+	if (priors_never_used(o) && o.verbosity > 1)
+		fprintf(stderr, "note: --depth-priors needs two outer iterations or more (--n-EstimationIters-external %d): the priors are never used\n", o.estimationItersExternal);
+	hcmvs_prior_params pp;
+	pp.para_prior = o.paraPrior; pp.sigma_prior = o.sigmaPrior; pp.photo2geo = o.photo2geo;
+	for (DeviceCtx& d : r.devs)
+		if (hcmvs_set_prior_params(d.ctx, &pp) != HCMVS_OK) { fprintf(stderr, "error: %s\n", hcmvs_last_error(d.ctx)); return false; }
+	size_t nPriors = 0;
+	for (uint32_t id : r.work) {
+		ImageData& im = r.images[id];
+		const std::string path = prior_path(o, id);
+		sceneio::DmapFile m;
+		if (!sceneio::load_dmap(path, m, 1, true)) continue; // no file (or not a depth map): no prior
+		if (m.w != im.w || m.h != im.h) {
+			fprintf(stderr, "error: the depth prior '%s' is %dx%d, image %u is %dx%d at this resolution level\n", path.c_str(), m.w, m.h, id, im.w, im.h);
+			return false;
+		}
+		if (!sceneio::load_dmap(path, m, 1)) { fprintf(stderr, "error: invalid depth prior '%s'\n", path.c_str()); return false; }
+		im.prior.swap(m.d);
+		++nPriors;
+	}
+	if (o.verbosity > 1)
+		printf("Depth priors (%s): %zu of %zu images to estimate have one; para_prior %g, sigma_prior %g, photo2geo %d\n", o.depthPriors.c_str(), nPriors, r.work.size(),
+		       (double)o.paraPrior, (double)o.sigmaPrior, o.photo2geo);
+	return true;
+}
 bool start_saver_and_workers(Run& r) {
 	hcmvs_ctx* ctx = r.ctx;
 	(void)mkdir((r.o.workdir + "/depthmap").c_str(), 0777);
@@ -1230,7 +1276,7 @@ int main(int argc, char** argv) {
 	list_todo(r);
 	if (!deal_and_budget(r) || !resume_finished(r)) return EXIT_FAILURE;
 	plan_image_batches(r);
-	if (!load_images(r) || !rescale_neighbours(r) || !set_ignore_masks(r)) return EXIT_FAILURE;
+	if (!load_images(r) || !rescale_neighbours(r) || !set_ignore_masks(r) || !load_depth_priors(r)) return EXIT_FAILURE;
 	if (!start_saver_and_workers(r) || !run_outer_iterations(r) || !finish_estimates(r)) return EXIT_FAILURE;
 	if (!filter_stage(r) || !final_maps_on_host(r)) return EXIT_FAILURE;
 	if (o.fusionMode == 1 || r.todo.empty()) return finish_without_fusion(r) ? EXIT_SUCCESS : EXIT_FAILURE;

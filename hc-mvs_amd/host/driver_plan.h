@@ -54,6 +54,11 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	int resume = 1;               // skip-if-exists (SceneDensify.cpp:3865-3880): an image whose final depth map is already in the working folder is not estimated again
 	int restoreHypothesis = 0;    // 1: the `restore` binary's extra last-sweep hypothesis from the previous level's maps
 	                              // (restore/libs/MVS/DepthMap.cpp:1527-1549); needs the previous level's maps in the working folder
+	std::string depthPriors;      // --depth-priors <folder>: per image a raw 'DR' depth map depth%04u.prior.dmap (the name the commented-out export at
+	                              // SceneDensify.cpp:3990-3991 would give) of the image's size at the run's resolution level; only the depth is read;
+	                              // an image without a file has no prior (DepthMap.cpp:941-954)
+	float paraPrior = 0.5f, sigmaPrior = 0.2f; // --n-para_prior, --sigma-prior (DensifyPointCloud.cpp:183, :162)
+	int photo2geo = 2;            // --n-photo2geo (DensifyPointCloud.cpp:175): first outer iteration that blends the prior term
 	int device = 0, batch = 32;   // reference images per launch: 32 is the measured optimum (profiles/r02_knobs.txt); lowered when HBM is short
 	std::vector<int> devices;     // --devices 0,1,...: one context + host thread per entry; reference images sharded over them by their position in
 	                              // the fusion order (k mod N); post-filters and fusion on the first (an ordinal may repeat: two contexts on one GPU)
@@ -80,11 +85,18 @@ static const char* const kKnownOptions[] = {
 	// this driver's own
 	"--min-views-trust-point", "--fuse-order", "--fuse-count", "--device", "--devices", "--batch", "--seed", "--restore-hypothesis", "--n-postfilter", "--n-postfilter-interleave", "--resume", "--n-filter"};
 
+// ... and the option that feeds the depth priors (a table of its own: kKnownOptions is the reference's table plus the driver's first set)
+static const char* const kPriorOptions[] = {"--depth-priors"};
+
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
 	"[--n-EstimationIters n] [--n-EstimationIters-external n] [--n-adapthalfwin n] [--fusion-mode 0|1] ...\n"
 	"       --n-viewspread 0|1   from outer iteration 1 on every pixel also tries what its source views' depth maps hold where it projects to\n"
 	"                            (default 0; the reference's default is 1 -- 0 keeps the results of command lines written before it existed)\n"
+	"       --depth-priors <dir> prior depth maps, <dir>/depth%04u.prior.dmap per image (raw 'DR' depth map of the image's size at the run's resolution\n"
+	"                            level; an image without a file has none), blended into every score with --n-para_prior, --sigma-prior and\n"
+	"                            --n-photo2geo; registered on outer iteration n - 2 with two extra sweeps, kept through the last.  Not together with\n"
+	"                            --n-viewspread 1 or --restore-hypothesis 1\n"
 	"       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
 	"                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 	"                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
@@ -109,6 +121,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		if (eq != std::string::npos) { val = a.substr(eq + 1); a = a.substr(0, eq); haveVal = true; }
 		bool known = false;
 		for (const char* k : kKnownOptions) known = known || a == k;
+		for (const char* k : kPriorOptions) known = known || a == k;
 		if (!known) { err = "unrecognised option '" + a + "'"; return PARSE_ERROR; }
 		if (!haveVal) { // the value is the next argument, whatever it starts with (negative numbers are values)
 			if (i + 1 >= argc) { err = "the required argument for option '" + a + "' is missing"; return PARSE_ERROR; }
@@ -132,6 +145,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	geti("--fuse-order", o.fuseOrder); geti("--fuse-count", o.fuseCount); geti("--restore-hypothesis", o.restoreHypothesis); geti("--n-postfilter", o.postFilter);
 	geti("--n-postfilter-interleave", o.postFilterInterleave); geti("--n-nOptimize", o.nOptimize); geti("--resume", o.resume); geti("--n-viewspread", o.viewspread);
 	geti("--n-filter", o.nFilter);
+	getf("--n-para_prior", o.paraPrior); getf("--sigma-prior", o.sigmaPrior); geti("--n-photo2geo", o.photo2geo);
+	if (kv.count("--depth-priors")) o.depthPriors = kv["--depth-priors"];
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -150,7 +165,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (o.postFilter < 0) o.postFilter = (o.nOptimize & 3) != 0 ? 1 : 0; // OPTDENSE::OPTIMIZE = REMOVE_SPECKLES | FILL_GAPS (DepthMap.h:113-118)
 	for (const char* k : {"--n-opticalflow", "--use-semantic", "--n-usegeoconsistency", "--n-usepartconsistency"})
 		if (kv.count(k) && atoi(kv[k].c_str()) != 0 && o.verbosity > 1)
-			o.notes.push_back(std::string(k) + " is not available in this build (defined subset); treated as 0");
+			o.notes.push_back(std::string(k) + " is not available in this build (defined subset); treated as 0" +
+			                  (std::string(k) == "--use-semantic" ? " (prior depth maps made elsewhere can be supplied with --depth-priors <folder>)" : ""));
 	geti("--filter-point-cloud", o.thFilterPointCloud);
 	getf("--sample-mesh", o.sampleMesh);
 	if (o.input.empty() || kv.count("--help")) return PARSE_USAGE;
@@ -159,6 +175,13 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (o.sampleMesh != 0 || o.thFilterPointCloud < 0) return PARSE_OK; // (no densify run)
 	if (o.fusionMode < 0) { err = "SGM fusion modes are not available"; return PARSE_ERROR; }
 	if (o.nFilter < 0 || o.nFilter > 2) { err = "--n-filter expects 0 (off), 1 (adjust) or 2 (strict)"; return PARSE_ERROR; }
+	if (!o.depthPriors.empty()) { // (without the folder the three prior options are read and have nothing to act on)
+		if (o.restoreHypothesis) { err = "--depth-priors is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
+		if (o.viewspread) { err = "--depth-priors is not combined with --n-viewspread 1 (the authors run priors with --n-viewspread 0)"; return PARSE_ERROR; }
+		if (!(o.paraPrior >= 0.f && o.paraPrior <= 1.f)) { err = "--n-para_prior expects a value in [0, 1]"; return PARSE_ERROR; }
+		if (!(o.sigmaPrior > 0.f) || !(o.sigmaPrior < INFINITY)) { err = "--sigma-prior expects a finite value > 0"; return PARSE_ERROR; }
+		if (o.photo2geo < 0) { err = "--n-photo2geo expects a value >= 0"; return PARSE_ERROR; }
+	}
 	if (o.batch < 1) o.batch = 1;
 	if (o.batch > HCMVS_MAX_BATCH) o.batch = HCMVS_MAX_BATCH;
 	if (o.estimationItersExternal < 1) o.estimationItersExternal = 1;
@@ -447,6 +470,12 @@ inline IterPlan plan_iteration(const Options& o, int it, bool anyWork) {
 	p.mainSubmitsFinal = last && p.meet && !o.nFilter;
 	return p;
 }
+// --depth-priors, the reference's schedule (SceneDensify.cpp:983-1031): on outer iteration n - 2, after the ordinary estimate of a batch, the
+// priors of its images are registered and two extra sweeps run (indices --n-EstimationIters and + 1); they stay registered through the last
+// iteration.  With fewer than two outer iterations the priors are never used.
+inline bool prior_sweeps_after(const Options& o, int it) { return !o.depthPriors.empty() && it == o.estimationItersExternal - 2; }
+inline bool priors_never_used(const Options& o) { return !o.depthPriors.empty() && o.estimationItersExternal < 2; }
+inline std::string prior_path(const Options& o, uint32_t id) { return sceneio::map_path(o.depthPriors, "/depth%04u.prior.dmap", id); }
 // --n-filter: the filter stage hands the maps of every image that has them to the saver
 inline bool stage_submits_final(const Options& o) { return o.nFilter != 0; }
 

@@ -193,6 +193,48 @@ typedef struct {
 } hcmvs_spread_stats;
 int hcmvs_get_spread_stats(hcmvs_ctx* ctx, hcmvs_spread_stats* out);
 
+/* ---- depth priors (DensifyPointCloud --n-para_prior / --sigma-prior / --n-photo2geo; ScorePixelImage, DepthMap.cpp:941-954) -----
+ * A reference view may carry a prior depth map.  While it is active, every ScorePixel evaluation of an estimate of that view blends,
+ * per source view and before the two best views are taken,
+ *     dd = |prior - depth| / prior,  wP = exp(-dd^2 / (2 sigma_prior^2)),  score = score * (1 - para_prior) + 2 * (1 - wP) * para_prior
+ * at the pixels whose prior is finite and > 0; a view that failed (thRobust) is not blended.  The prior of view `id` is ACTIVE in an
+ * estimate of `id` when one is registered, para_prior > 0 and params->it_external >= photo2geo; without an active prior every call
+ * computes exactly what it computes without this section.  The library consumes the map; making one (planes, a coarser level, a
+ * rendering) is the caller's.  DESIGN.md section 5, D11 pins the association and the validity rule. */
+typedef struct {
+	float para_prior;   /* --n-para_prior: weight of the term, 0 .. 1 */
+	float sigma_prior;  /* --sigma-prior: width of the relative depth difference, > 0 */
+	int32_t photo2geo;  /* --n-photo2geo: first outer iteration that blends the term, >= 0 */
+} hcmvs_prior_params;
+/* the reference's defaults: 0.5, 0.2, 2 (DensifyPointCloud.cpp:162, :175, :183) */
+void hcmvs_default_prior_params(hcmvs_prior_params* p);
+/* for the estimates that follow.  Refused, with nothing changed: para_prior outside [0, 1] or not finite, sigma_prior not > 0 (or not
+ * finite), photo2geo < 0. */
+int hcmvs_set_prior_params(hcmvs_ctx* ctx, const hcmvs_prior_params* p);
+/* the prior of view `id` as a REFERENCE view: w*h floats in DEVICE memory at the view's size, caller-owned, not copied, read (never
+ * written) by the estimates that follow.  NULL removes it; registering the view again or hcmvs_release_view drops it.  A view made by
+ * hcmvs_rescale_view is refused: only a reference view's prior is ever read. */
+int hcmvs_set_depth_prior_device(hcmvs_ctx* ctx, uint32_t id, const float* d_prior);
+/* the same from a HOST buffer, into a copy the context owns.  Blocking. */
+int hcmvs_set_depth_prior(hcmvs_ctx* ctx, uint32_t id, const float* prior);
+/* An item with an active prior is refused (HCMVS_ERR_INVALID, nothing enqueued) together with the `restore` hint in effect or with
+ * view spread doing work for it: the authors run priors with --n-viewspread 0, and the hint belongs to the other binary. */
+
+/* The reference's extra sweeps (SceneDensify.cpp:983-1031): sweeps first_sweep .. first_sweep + n_sweeps - 1 on maps that are the
+ * state an estimate leaves between outer iterations (depth, normal, conf = the score) -- no mask application, no median, no init-score
+ * pass; the sweep index decides direction and random stream as in an estimate; then the end pass as in hcmvs_estimate_batch_device.
+ * params->n_estimation_iters is not used; the hint of an item is never offered.  Refused: first_sweep < 0, n_sweeps < 1, and
+ * first_sweep + n_sweeps > HCMVS_MAX_SWEEP_INDEX + 1 (a sweep's random stream is it_external * 64 + 1 + index). */
+#define HCMVS_MAX_SWEEP_INDEX 62
+int hcmvs_estimate_sweeps_batch_device(hcmvs_ctx* ctx, const hcmvs_batch_item* items, int32_t n_items, const hcmvs_params* params,
+                                       int32_t first_sweep, int32_t n_sweeps);
+/* counters of the prior term of the last estimate (summed over the items of a batch); synchronises */
+typedef struct {
+	uint64_t evals_prior;  /* evaluations that blended the term (they are part of hcmvs_stats::evals) */
+	uint64_t pixels_prior; /* estimated pixels of the items with an active prior whose prior is usable (finite and > 0) */
+} hcmvs_prior_stats;
+int hcmvs_get_prior_stats(hcmvs_ctx* ctx, hcmvs_prior_stats* out);
+
 /* SceneDensify.cpp:783-808: splat n_points sparse world points (xyz f32) seen by view `id` as 5x5 blocks
  * into host maps depth (w*h) / normal (w*h*3); returns the depth range (min*0.9, max*1.1). Host-side helper. */
 int hcmvs_splat_init(hcmvs_ctx* ctx, uint32_t id, const float* points_xyz, int32_t n_points, float* depth,

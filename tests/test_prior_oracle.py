@@ -1,0 +1,179 @@
+"""The oracle variant with a depth prior (tests/oracle_prior.c; DepthMap.cpp:941-954): known answers of the term, the aggregation over
+blended view scores, the estimate without a prior against the plain oracle, the sweeps-only entry and the two arithmetic modes."""
+import importlib
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import oracle_prior_lib as OP
+import prior_cases as PC
+
+synth = importlib.import_module("hc-mvs_amd.synth")
+MODES = [O.ARITH_REFERENCE, O.ARITH_DEVICE]
+f32 = np.float32
+
+
+def term64(score, prior, depth, para, sigma):
+    """the term in float64 numpy"""
+    dd = abs(prior - depth) / prior
+    wP = np.exp(-dd * dd / (2 * sigma * sigma))
+    return score * (1 - para) + 2 * (1 - wP) * para
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_known_answers_of_the_term(mode):
+    rng = np.random.default_rng(3)
+    for _ in range(200):
+        score = float(f32(rng.uniform(0, 2))); prior = float(f32(rng.uniform(1, 20))); depth = float(f32(prior * rng.uniform(0.6, 1.4)))
+        para = float(f32(rng.uniform(0.05, 1))); sigma = float(f32(rng.uniform(0.05, 0.5)))
+        got = OP.blend(score, prior, depth, para, sigma, mode)
+        assert got == pytest.approx(term64(score, prior, depth, para, sigma), rel=2e-6, abs=2e-6)
+    # a prior equal to the depth: dd = 0, wP = 1, the addend is 0 -- score * (1 - para_prior) exactly
+    for score, para in ((0.37, 0.4), (1.2, 0.5), (0.0, 1.0), (0.66, 0.125)):
+        assert OP.blend(score, 7.25, 7.25, para, 0.2, mode) == float(f32(score) * (f32(1) - f32(para)))
+        assert OP.addend(7.25, 7.25, para, 0.2, mode) == 0.0
+    # far from the prior the addend saturates at 2 * para_prior
+    assert OP.addend(5.0, 50.0, 0.4, 0.2, mode) == float(f32(2) * f32(0.4))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_validity_rule(mode):
+    """finite and > 0; everything else leaves the score as it is, bit for bit"""
+    for bad in (0.0, -0.0, -3.5, float("nan"), float("inf"), float("-inf")):
+        assert not OP.usable(bad)
+        assert OP.blend(0.4375, bad, 6.0, 0.5, 0.2, mode) == 0.4375
+    assert OP.usable(1e-30) and OP.usable(3.0e38)
+
+
+def pixel_case(V=3, seed=21):
+    views = synth.make_views(96, 80, 90.0, V, seed=seed)
+    x, y = 48, 40
+    depth = float(views[0]["depth"][y, x]); normal = views[0]["normal"][y, x].astype(np.float32)
+    return views, x, y, depth, normal
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_pixel_score_sees_the_blended_views(mode):
+    views, x, y, depth, normal = pixel_case()
+    p = O.default_params(adapthalfwin=6, it_external=2, n_external_iters=3, arith_mode=mode)
+    plain = float(O.lib().hcor_score_pixel(O.C.byref(O.make_view(views[0])), O.make_view_array(views[1:]), 3, O.u8ptr(O.gradient_map(views[0]["gray"])),
+                                           O.C.byref(p), x, y, O.C.c_float(depth), O.fptr(normal)))
+    # no prior at the pixel, and a prior before photo2geo: the plain score bit for bit
+    s0, v0 = OP.score_pixel(views, p, x, y, depth, normal, 0.0)
+    assert s0 == plain
+    p1 = O.default_params(adapthalfwin=6, it_external=1, n_external_iters=3, arith_mode=mode)
+    plain1 = float(O.lib().hcor_score_pixel(O.C.byref(O.make_view(views[0])), O.make_view_array(views[1:]), 3, O.u8ptr(O.gradient_map(views[0]["gray"])),
+                                            O.C.byref(p1), x, y, O.C.c_float(depth), O.fptr(normal)))
+    assert OP.score_pixel(views, p1, x, y, depth, normal, depth * 1.2)[0] == plain1
+    # with a prior: every view that was scored is blended, the aggregation runs over the blended values
+    prior = depth * 1.02
+    s, v = OP.score_pixel(views, p, x, y, depth, normal, prior)
+    want = [OP.blend(float(a), prior, depth, 0.5, 0.2, mode) for a in v0]
+    assert list(v) == [f32(w) for w in want]
+    two = sorted(want)[:2]
+    assert s == float((f32(two[0]) + f32(two[1])) / f32(2))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_a_failed_view_stays_thRobust_and_the_blend_can_lift_a_view_over_it(mode):
+    """view 2 is pushed out of the image (a failed view: thRobust, unblended); a valid view that a far prior lifts over thRobust leaves
+    the aggregation with the best view alone"""
+    views, x, y, depth, normal = pixel_case()
+    views = [dict(v) for v in views]
+    C2 = np.array(views[2]["C"], np.float64) + np.array([400.0, 0, 0])       # the patch projects outside view 2
+    views[2]["C"] = C2
+    p = O.default_params(adapthalfwin=6, it_external=2, n_external_iters=3, arith_mode=mode)
+    th = float(f32(p.ncc_threshold_keep) * f32(1.2))
+    s0, v0 = OP.score_pixel(views, p, x, y, depth, normal, 0.0)
+    assert v0[1] == f32(th) and v0[0] < th and v0[2] < th
+    far = depth * 3.0                                                          # addend = 2 * para_prior * (1 - wP) ~ 1: every valid view ends above thRobust
+    s, v = OP.score_pixel(views, p, x, y, depth, normal, far)
+    assert v[1] == f32(th)                                                     # the failed view: not blended
+    assert v[0] > th and v[2] > th
+    lo = sorted(float(a) for a in v)
+    assert lo[0] == th and s == th                                             # second best >= thRobust: the best view alone (DepthMap.cpp:1040)
+    # a mild prior keeps the two valid views below thRobust: their mean
+    s, v = OP.score_pixel(views, p, x, y, depth, normal, depth)
+    assert s == float((f32(min(v[0], v[2])) + f32(max(v[0], v[2]))) / f32(2))
+
+
+def small_case(V=3, seed=7):
+    views = synth.make_views(96, 80, 90.0, V, seed=seed)
+    d, n, c, dmin, dmax = PC.start_maps(views, seed)
+    return views, d, n, c, dmin, dmax
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("it_external", [0, 2])
+def test_without_a_prior_the_variant_is_the_plain_oracle(mode, it_external):
+    views, d, n, c, dmin, dmax = small_case()
+    keep = np.ones((80, 96), np.uint8); keep[20:30, 40:60] = 0
+    for kp in (None, keep):
+        p = O.default_params(adapthalfwin=6, n_estimation_iters=2, it_external=it_external, n_external_iters=3, arith_mode=mode, order=O.ORDER_ROWS,
+                             n_threads=4, seed=5, **PC.KW)
+        want = O.estimate(views, p, dmin, dmax, d, n, keep=kp)
+        got = OP.estimate(views, p, dmin, dmax, d, n, keep=kp)
+        assert all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3])) and got[3]["evals"] == want[3]
+        assert got[3]["evals_prior"] == 0 and got[3]["pixels_prior"] == 0
+        # a registered prior that is not active: para_prior = 0, or photo2geo above the iteration
+        prior = PC.make_prior(views[0], seed=1)
+        for kw in (dict(para_prior=0.0), dict(photo2geo=it_external + 1)):
+            got = OP.estimate(views, p, dmin, dmax, d, n, keep=kp, prior=prior, **kw)
+            assert all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3])) and got[3]["evals_prior"] == 0
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_the_prior_changes_the_estimate_and_is_counted(mode):
+    views, d, n, c, dmin, dmax = small_case()
+    prior = PC.make_prior(views[0], seed=2)
+    p = O.default_params(adapthalfwin=6, n_estimation_iters=2, it_external=2, n_external_iters=3, arith_mode=mode, seed=5, **PC.KW)
+    plain = OP.estimate(views, p, dmin, dmax, d, n)
+    got = OP.estimate(views, p, dmin, dmax, d, n, prior=prior)
+    est = PC.estimated_pixels(d.shape, 7)
+    assert got[3]["pixels_prior"] == int((PC.usable(prior) & est).sum())
+    assert 0.5 < got[3]["pixels_prior"] / est.sum() < 0.9
+    assert 0 < got[3]["evals_prior"] < got[3]["evals"]
+    assert not np.array_equal(got[0], plain[0])
+    # pixels without a usable prior whose neighbourhood has none either are rare; the maps differ where priors are
+    assert np.mean(got[2][est & PC.usable(prior)] != plain[2][est & PC.usable(prior)]) > 0.5
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_sweeps_only_entry_continues_an_estimate(mode):
+    """sweeps N and N + 1 after an estimate of N sweeps = one run of N + 2 sweeps of the pixel loop without a score pass in between"""
+    views, d, n, c, dmin, dmax = small_case()
+    prior = PC.make_prior(views[0], seed=3)
+    N = 2
+    kw = dict(adapthalfwin=6, it_external=1, n_external_iters=3, arith_mode=mode, seed=9, **PC.KW)
+    pr = dict(prior=prior, para_prior=0.4, photo2geo=1)
+    a = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, d, n, **pr)
+    b = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N, 2), **pr)
+    whole = OP.estimate(views, O.default_params(n_estimation_iters=N + 2, **kw), dmin, dmax, d, n, **pr)
+    assert all(np.array_equal(x, y) for x, y in zip(b[:3], whole[:3]))
+    assert a[3]["evals"] + b[3]["evals"] == whole[3]["evals"]
+    assert a[3]["evals_prior"] + b[3]["evals_prior"] == whole[3]["evals_prior"]
+    assert b[3]["pixels_prior"] == whole[3]["pixels_prior"] == a[3]["pixels_prior"]
+    # and the sweep index decides direction and random stream: other indices give other maps
+    other = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N + 1, 2), **pr)
+    assert not np.array_equal(other[0], b[0])
+
+
+def test_the_two_arithmetic_modes_agree_statistically():
+    """the bound of tests/test_oracle_estimate.py for the plain estimate, on its scene, with a prior at work"""
+    import test_oracle_estimate as T
+    views, d0, n0, dmin, dmax = T.scene(128, 96, 110.0, 4, seed=4, n_pts=120)
+    prior = PC.make_prior(views[0], seed=4)
+    kw = dict(adapthalfwin=6, n_estimation_iters=4, n_threads=8, order=O.ORDER_ROWS)
+    pr = dict(prior=prior, photo2geo=0)
+    r = OP.estimate(views, O.default_params(arith_mode=O.ARITH_REFERENCE, **kw), dmin, dmax, d0, n0, **pr)
+    v = OP.estimate(views, O.default_params(arith_mode=O.ARITH_DEVICE, **kw), dmin, dmax, d0, n0, **pr)
+    assert r[3]["evals_prior"] > 0
+    both = (r[0] > 0) & (v[0] > 0)
+    assert ((r[0] > 0) == (v[0] > 0)).mean() > 0.985
+    rel = np.abs(r[0] - v[0])[both] / r[0][both]
+    assert (rel < 0.01).mean() > 0.92 and np.mean(np.abs(r[0] - v[0])[both]) < 0.04
+    assert abs(int((r[0] > 0).sum()) - int((v[0] > 0).sum())) <= 0.01 * (r[0] > 0).sum()
+    gt = views[0]["depth"]
+    acc = [float((np.abs(m[0] - gt)[m[0] > 0] / gt[m[0] > 0] < 0.01).mean()) for m in (r, v)]
+    assert abs(acc[0] - acc[1]) < 0.02
