@@ -3,7 +3,7 @@
  *
  * CPU restatement of the PatchMatch depth-map estimation path of HC-MVS:
  *   DM.cpp:354-381 (visiting order), 386-439 (constants), 442-519 (patch + bilateral weights),
- *   522-616 + 890-893 (ScorePixelImage), 987-1046 (ScorePixel), 1050-1501 (ProcessPixel), 1504-1608 (view spread, hcmvs_spread.inc),
+ *   522-616 + 890-893 (ScorePixelImage), 941-954 (its depth-prior term), 987-1046 (ScorePixel), 1050-1501 (ProcessPixel), 1504-1608 (view spread, hcmvs_spread.inc),
  *   1671-1738 (InterpolatePixel, InitPlane); DM.h:537-548, 565-574, 618-634;
  *   SD.cpp:581-595 (gradient map), 649-744 (passes), 758-1056 (driver), 783-808 (splat init).
  *
@@ -62,6 +62,9 @@ void hcor_default_params(hcor_params* p) {
 	p->order = HCOR_ORDER_ZIGZAG;
 	p->n_threads = 1;
 	p->median_blur = 1;
+	p->para_prior = 0.5f;         /* the reference's defaults; prior_map NULL: no prior */
+	p->sigma_prior = 0.2f;
+	p->photo2geo = 2;
 }
 
 static inline uint32_t fmix32(uint32_t h) {
@@ -409,13 +412,61 @@ typedef struct {
 	/* view spread (hcmvs_spread.inc): on for this call; R_ref R_j^T, R_ref (C_j - C_ref), 1 / f of view j */
 	int spread;
 	double spT[HCOR_MAX_VIEWS][9], spt[HCOR_MAX_VIEWS][3], jifx[HCOR_MAX_VIEWS], jify[HCOR_MAX_VIEWS];
-	uint64_t evals;
+	/* depth prior (score_pixel): active for this call; device association: 1 - para_prior and -1 / (2 sigma^2), rounded once */
+	int prior;
+	float priorKeep, priorSigmaK;
+	uint64_t evals, evals_prior;
 } est_ctx;
 
 static int device_segments(int V) {
 	(void)V;
 	return 8; /* the kernels run one lane layout for every view count: 8 tap segments per view (9..16 views: two sets of eight
 	           * view groups; the per-view arithmetic does not depend on which lane group evaluates it) */
+}
+
+/* The depth prior's term (DensifyPointCloud --n-para_prior, --sigma-prior, --n-photo2geo; ScorePixelImage, DM.cpp:941-954), from the
+ * reference's lines (not from the kernels), per source view, after the (1 - photometric_flow) scale and before the two-best-views
+ * aggregation (DM.cpp:987-1046); a view that left early with thRobust (DM.cpp:558, 591) is not blended:
+ *     if (it_external >= photo2geo && prior(x0) != 0) {
+ *         dd = |prior - depth| / prior                      (Util.inl:658-664 DepthSimilarity)
+ *         wP = EXP(-SQUARE(dd) / (2 * SQUARE(sigma_prior)))
+ *         score = score * (1 - para_prior) + 2 * (1 - wP) * para_prior
+ *     }
+ * What the reference leaves undefined is defined as DESIGN.md section 5, D11 states it: the term applies where the prior is finite and
+ * > 0 (the reference tests != 0 and asserts > 0); a negative, NaN or infinite prior is "no prior here".  The prior is active when a map
+ * is given, para_prior > 0 and it_external >= photo2geo.
+ *
+ * Arithmetic.  HCOR_ARITH_REFERENCE follows the lines above operation by operation in float, with libm's expf.  HCOR_ARITH_DEVICE states
+ * the association of the gfx950 kernels: dd = |prior - depth| / prior with an IEEE division, wP = pm_expf((dd * dd) * k) with
+ * k = -1 / (2 * (sigma * sigma)) rounded once on the host, addend = (2 * (1 - wP)) * para_prior computed once per hypothesis,
+ * score = score * (1 - para_prior) + addend with (1 - para_prior) rounded once on the host; nothing is fused. */
+static inline int prior_usable(float prior) { return prior > 0.f && prior < INFINITY; } /* D11: finite and > 0 */
+static inline float prior_keep(float para) { return 1.f - para; }
+static inline float prior_sigmaK(float sigma) { return -1.f / (2.f * (sigma * sigma)); }
+/* 2 (1 - wP) para_prior of one hypothesis */
+static float prior_addend(int mode, float prior, float depth, float para, float sigma, float sigmaK) {
+	if (mode == HCOR_ARITH_DEVICE) {
+		const float dd = fabsf(prior - depth) / prior;
+		const float wP = pm_expf((dd * dd) * sigmaK);
+		return (2.f * (1.f - wP)) * para;
+	}
+	const float dd = fabsf(prior - depth) / prior;                 /* DepthSimilarity */
+	const float wP = expf(-SQ(dd) / (2 * SQ(sigma)));              /* DM.cpp:948 */
+	return 2 * (1.f - wP) * para;                                  /* DM.cpp:950, the right-hand summand */
+}
+/* DM.cpp:950 on a view's score */
+static inline float prior_blend(int mode, float s, float para, float keep, float addend) {
+	return mode == HCOR_ARITH_DEVICE ? s * keep + addend : s * (1.f - para) + addend;
+}
+
+int hcor_prior_usable(float prior) { return prior_usable(prior); }
+void hcor_prior_consts(float para, float sigma, float* out) { out[0] = prior_keep(para); out[1] = prior_sigmaK(sigma); }
+float hcor_prior_addend(float prior, float depth, float para, float sigma, int mode) {
+	return prior_addend(mode, prior, depth, para, sigma, prior_sigmaK(sigma));
+}
+float hcor_prior_blend(float score, float prior, float depth, float para, float sigma, int mode) {
+	if (!prior_usable(prior)) return score;
+	return prior_blend(mode, score, para, prior_keep(para), hcor_prior_addend(prior, depth, para, sigma, mode));
 }
 
 static void ctx_init(est_ctx* c, const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra,
@@ -439,6 +490,9 @@ static void ctx_init(est_ctx* c, const hcor_view* ref, const hcor_view* srcs, in
 		c->jifx[v] = 1.0 / srcs[v].K[0]; c->jify[v] = 1.0 / srcs[v].K[4];
 	}
 	c->spread = p->spread_on && p->spread_maps && p->it_external >= 1;
+	c->prior = p->prior_map && p->para_prior > 0.f && p->it_external >= p->photo2geo;
+	c->priorKeep = prior_keep(p->para_prior);
+	c->priorSigmaK = prior_sigmaK(p->sigma_prior);
 	for (int i = 0; i < 9; ++i) c->Hrf[i] = (float)c->Hr[i];
 	c->ifx = 1.0 / ref->K[0]; c->ify = 1.0 / ref->K[4];
 	c->S = device_segments(V);
@@ -486,6 +540,7 @@ typedef struct {
 	float cX[HCOR_MAX_NEIGHBORS][3];
 	int cSlot[HCOR_MAX_NEIGHBORS]; /* position in the candidate list (= lane of the slot on the device) */
 	float planeN[3], planeD;
+	float prior; /* the pixel's depth prior while the prior is active and the value usable (prior_at), else 0: fill_patch leaves 0 */
 } pix_state;
 
 /* nSizeHalfWindow generalised (hcmvs_oracle.h): 7 for every patch the reference supports, adapthalfwin beyond that */
@@ -530,6 +585,7 @@ static void fill_patch(const est_ctx* c, pix_state* ps, int x, int y) {
 	const hcor_view* ref = c->ref;
 	const int W = ref->width;
 	ps->x = x; ps->y = y;
+	ps->prior = 0.f;
 	const float tx = (float)c->gra[y * W + x];
 	ps->a = tx > 100 ? 5 : c->p.adapthalfwin;
 	const int a = ps->a;
@@ -668,9 +724,14 @@ static int smooth_factors(const est_ctx* c, const pix_state* ps, float depth, co
 	return ps->nClose;
 }
 
-/* DM.cpp:522-616, 890-893: reference association */
+/* where a scored view returns: the prior's term on the scaled score, for a pixel that has a prior (priorAdd: score_pixel's addend) */
+static inline float scored_view(const est_ctx* c, const pix_state* ps, float s, float priorAdd) {
+	return ps->prior > 0.f ? prior_blend(c->p.arith_mode, s, c->p.para_prior, c->priorKeep, priorAdd) : s;
+}
+
+/* DM.cpp:522-616, 890-893, 941-954: reference association */
 static float score_view_ref(const est_ctx* c, const pix_state* ps, int v, float depth, const float* normal,
-                            const float* sf, int nsf) {
+                            const float* sf, int nsf, float priorAdd) {
 	const hcor_view* im = &c->srcs[v];
 	/* DM.h:565-574 */
 	const double n[3] = {normal[0], normal[1], normal[2]};
@@ -710,7 +771,7 @@ static float score_view_ref(const est_ctx* c, const pix_state* ps, int v, float 
 	ncc = ncc < -1.f ? -1.f : (ncc > 1.f ? 1.f : ncc);
 	float s = 1.f - ncc;
 	for (int q = 0; q < nsf; ++q) s *= sf[q];
-	return (1.f - c->p.photometric_flow) * s + c->p.photometric_flow * 0.f;
+	return scored_view(c, ps, (1.f - c->p.photometric_flow) * s + c->p.photometric_flow * 0.f, priorAdd);
 }
 
 /* statistics of the device association's inside test (see score_view_dev) */
@@ -732,7 +793,7 @@ static void device_H(const est_ctx* c, const pix_state* ps, int v, float depth, 
 		for (int j = 0; j < 3; ++j) H[i * 3 + j] = fmaf(c->Hmf[v][i], q[j], c->Af[v][i * 3 + j]);
 }
 static float score_view_dev(const est_ctx* c, const pix_state* ps, int v, float depth, const float* normal,
-                            const float* sf, int nsf) {
+                            const float* sf, int nsf, float priorAdd) {
 	const hcor_view* im = &c->srcs[v];
 	float H[9];
 	device_H(c, ps, v, depth, normal, H);
@@ -802,11 +863,11 @@ static float score_view_dev(const est_ctx* c, const pix_state* ps, int v, float 
 	ncc = ncc < -1.f ? -1.f : (ncc > 1.f ? 1.f : ncc);
 	float s = 1.f - ncc;
 	for (int q = 0; q < nsf; ++q) s *= sf[q];
-	return (1.f - c->p.photometric_flow) * s;
+	return scored_view(c, ps, (1.f - c->p.photometric_flow) * s, priorAdd);
 }
 
-/* DM.cpp:987-1046 (DENSE_AGGNCC_MINMEAN) */
-static float score_pixel(est_ctx* c, const pix_state* ps, float depth, const float* normal) {
+/* DM.cpp:987-1046 (DENSE_AGGNCC_MINMEAN); view_out (optional): the V view scores the aggregation runs over */
+static float score_pixel_views(est_ctx* c, const pix_state* ps, float depth, const float* normal, float* view_out) {
 	float sf[HCOR_MAX_NEIGHBORS];
 	int nsf = smooth_factors(c, ps, depth, normal, sf);
 	if (c->p.arith_mode == HCOR_ARITH_DEVICE) {
@@ -825,17 +886,29 @@ static float score_pixel(est_ctx* c, const pix_state* ps, float depth, const flo
 		sf[0] = F;
 		nsf = 1;
 	}
+	/* the prior's addend, once per hypothesis; the views blend it where they return a score (scored_view) */
+	const float priorAdd = ps->prior > 0.f ? prior_addend(c->p.arith_mode, ps->prior, depth, c->p.para_prior, c->p.sigma_prior, c->priorSigmaK) : 0.f;
 	float s0 = FLT_MAX, s1 = FLT_MAX; /* two smallest */
 	for (int v = 0; v < c->V; ++v) {
-		const float s = c->p.arith_mode == HCOR_ARITH_DEVICE ? score_view_dev(c, ps, v, depth, normal, sf, nsf)
-		                                                      : score_view_ref(c, ps, v, depth, normal, sf, nsf);
+		const float s = c->p.arith_mode == HCOR_ARITH_DEVICE ? score_view_dev(c, ps, v, depth, normal, sf, nsf, priorAdd)
+		                                                      : score_view_ref(c, ps, v, depth, normal, sf, nsf, priorAdd);
+		if (view_out) view_out[v] = s;
 		if (s < s0) { s1 = s0; s0 = s; }
 		else if (s < s1) s1 = s;
 	}
 	c->evals++;
+	if (ps->prior > 0.f) c->evals_prior++;
 	if (c->V <= 1) return s0;
 	if (s1 >= c->thRobust) return s0;
 	return (s0 + s1) / 2;
+}
+static float score_pixel(est_ctx* c, const pix_state* ps, float depth, const float* normal) {
+	return score_pixel_views(c, ps, depth, normal, NULL);
+}
+
+/* the pixel's prior for pix_state: its value while the prior is active and the value usable, else 0 */
+static inline float prior_at(const est_ctx* c, long idx) {
+	return c->prior && prior_usable(c->p.prior_map[idx]) ? c->p.prior_map[idx] : 0.f;
 }
 
 /* Util.inl:614-626 */
@@ -925,8 +998,8 @@ float hcor_score_view(const hcor_view* ref, const hcor_view* src, const uint8_t*
 	est_ctx c; pix_state ps;
 	ctx_init(&c, ref, src, 1, gra, p, 1.f, 2.f);
 	fill_patch(&c, &ps, x, y);
-	return p->arith_mode == HCOR_ARITH_DEVICE ? score_view_dev(&c, &ps, 0, depth, normal, NULL, 0)
-	                                          : score_view_ref(&c, &ps, 0, depth, normal, NULL, 0);
+	return p->arith_mode == HCOR_ARITH_DEVICE ? score_view_dev(&c, &ps, 0, depth, normal, NULL, 0, 0.f)
+	                                          : score_view_ref(&c, &ps, 0, depth, normal, NULL, 0, 0.f);
 }
 float hcor_score_pixel(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
                        const hcor_params* p, int x, int y, float depth, const float normal[3]) {
@@ -934,6 +1007,16 @@ float hcor_score_pixel(const hcor_view* ref, const hcor_view* srcs, int n_src, c
 	ctx_init(&c, ref, srcs, n_src, gra, p, 1.f, 2.f);
 	fill_patch(&c, &ps, x, y);
 	return score_pixel(&c, &ps, depth, normal);
+}
+float hcor_prior_score_pixel(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra, const hcor_params* p, int x, int y,
+                             float depth, const float normal[3], float prior, float* view_scores) {
+	est_ctx c; pix_state ps;
+	hcor_params q = *p;
+	q.prior_map = &prior; /* a map of the one pixel: prior_at(0) applies the active and the validity rule */
+	ctx_init(&c, ref, srcs, n_src, gra, &q, 0.f, 1.f);
+	fill_patch(&c, &ps, x, y);
+	ps.prior = prior_at(&c, 0);
+	return score_pixel_views(&c, &ps, depth, normal, view_scores);
 }
 void hcor_correct_normal(const hcor_view* ref, int x, int y, float n[3], int mode) {
 	const float vd[3] = {(float)(((double)x - ref->K[2]) / ref->K[0]), (float)(((double)y - ref->K[5]) / ref->K[4]), 1.f};
@@ -966,6 +1049,7 @@ static void score_one(est_ctx* c, int x, int y, float* depth, float* normal, flo
 	}
 	pix_state ps;
 	fill_patch(c, &ps, x, y);
+	ps.prior = prior_at(c, idx);
 	float d = depth[idx];
 	float n[3] = {normal[3 * idx], normal[3 * idx + 1], normal[3 * idx + 2]};
 	const uint32_t st = STREAM_SCORE(c->p.it_external);
@@ -1009,6 +1093,7 @@ static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, f
 	if (!border_ok(c, x, y)) return;
 	pix_state ps;
 	fill_patch(c, &ps, x, y);
+	ps.prior = prior_at(c, (long)y * W + x);
 	const int rev = (iter % 2) != 0; /* dir = RB2LT for odd iterations, DM.cpp:418 */
 	int nbx[HCOR_MAX_NEIGHBORS], nby[HCOR_MAX_NEIGHBORS], nbc[HCOR_MAX_NEIGHBORS];
 	int nNb = 0;
@@ -1147,12 +1232,12 @@ static void process_pixel(est_ctx* c, int x, int y, int iter, float* depthMap, f
 static inline int kept(const hcor_params* p, long i) { return !p->keep || p->keep[i]; } /* the keep-mask, hcmvs_oracle.h */
 
 void hcor_pass_score(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p,
-                     float dMin, float dMax, float* depth, float* normal, float* conf, uint64_t* evals) {
+                     float dMin, float dMax, float* depth, float* normal, float* conf, hcor_counts* counts) {
 	const int W = ref->width, H = ref->height;
-	uint64_t total = 0;
+	uint64_t total = 0, total_prior = 0;
 	const int nt = p->n_threads > 0 ? p->n_threads : 1;
 	(void)nt;
-#pragma omp parallel num_threads(nt) reduction(+ : total)
+#pragma omp parallel num_threads(nt) reduction(+ : total, total_prior)
 	{
 		est_ctx c;
 		ctx_init(&c, ref, srcs, V, gra, p, dMin, dMax);
@@ -1160,13 +1245,13 @@ void hcor_pass_score(const hcor_view* ref, const hcor_view* srcs, int V, const u
 		for (int y = 0; y < H; ++y)
 			for (int x = 0; x < W; ++x)
 				if (kept(p, (long)y * W + x)) score_one(&c, x, y, depth, normal, conf);
-		total += c.evals;
+		total += c.evals; total_prior += c.evals_prior;
 	}
-	if (evals) *evals += total;
+	if (counts) { counts->evals += total; counts->evals_prior += total_prior; }
 }
 
 void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p,
-                     int iter, float dMin, float dMax, float* depth, float* normal, float* conf, uint64_t* evals) {
+                     int iter, float dMin, float dMax, float* depth, float* normal, float* conf, hcor_counts* counts) {
 	const int W = ref->width, H = ref->height;
 	const int rev = (iter % 2) != 0;
 	if (p->order == HCOR_ORDER_ZIGZAG) {
@@ -1182,7 +1267,7 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 			if (kept(p, (long)y * W + x)) process_pixel(&c, x, y, iter, depth, normal, conf);
 		}
 		free(coords);
-		if (evals) *evals += c.evals;
+		if (counts) { counts->evals += c.evals; counts->evals_prior += c.evals_prior; }
 		return;
 	}
 	/* HCOR_ORDER_ROWS: row-pipelined wavefront.  A pixel needs its left/up neighbours (right/down when
@@ -1191,8 +1276,8 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 	 * RNG is keyed by pixel, not by visiting sequence. */
 	const int nt = p->n_threads > 0 ? p->n_threads : 1;
 	atomic_int* progress = (atomic_int*)calloc((size_t)H, sizeof(atomic_int)); /* pixels finished per logical row */
-	uint64_t total = 0;
-#pragma omp parallel num_threads(nt) reduction(+ : total)
+	uint64_t total = 0, total_prior = 0;
+#pragma omp parallel num_threads(nt) reduction(+ : total, total_prior)
 	{
 		est_ctx c;
 		ctx_init(&c, ref, srcs, V, gra, p, dMin, dMax);
@@ -1212,10 +1297,10 @@ void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int V, const u
 				atomic_store_explicit(&progress[r], q + 1, memory_order_release); /* an ignored pixel's column still counts as done */
 			}
 		}
-		total += c.evals;
+		total += c.evals; total_prior += c.evals_prior;
 	}
 	free(progress);
-	if (evals) *evals += total;
+	if (counts) { counts->evals += total; counts->evals_prior += total_prior; }
 }
 
 void hcor_pass_end(const hcor_params* p, int W, int H, float* depth, float* normal, float* conf) {
@@ -1230,12 +1315,37 @@ void hcor_pass_end(const hcor_params* p, int W, int H, float* depth, float* norm
 	}
 }
 
-int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p,
-                  float dMin, float dMax, float* depth, float* normal, float* conf, uint64_t* evals) {
+/* what both entries check before they touch a map, and the counter that is a function of the inputs alone */
+static int estimate_begin(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p, float dMin, float dMax,
+                          hcor_counts* counts) {
 	if (V < 1 || V > HCOR_MAX_VIEWS) return 1;
 	if (p->adapthalfwin < 1 || p->adapthalfwin > HCOR_MAX_HALF_WINDOW) return 1;
+	est_ctx c;
+	ctx_init(&c, ref, srcs, V, gra, p, dMin, dMax);
+	if (c.prior && (c.spread || (p->hint_depth && p->hint_normal && p->it_external == p->n_external_iters - 1))) return 2;
+	if (!counts) return 0;
+	memset(counts, 0, sizeof *counts);
+	for (int y = 0; y < ref->height; ++y)
+		for (int x = 0; x < ref->width; ++x) {
+			const long i = (long)y * ref->width + x;
+			if (kept(p, i) && border_ok(&c, x, y) && prior_at(&c, i) > 0.f) counts->pixels_prior++;
+		}
+	return 0;
+}
+
+/* sweeps first .. first + n - 1, then pass C on the last outer iteration */
+static void sweeps_and_end(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p, int first, int n,
+                           float dMin, float dMax, float* depth, float* normal, float* conf, hcor_counts* counts) {
+	for (int iter = first; iter < first + n; ++iter)
+		hcor_pass_sweep(ref, srcs, V, gra, p, iter, dMin, dMax, depth, normal, conf, counts);
+	if (p->it_external == p->n_external_iters - 1) hcor_pass_end(p, ref->width, ref->height, depth, normal, conf);
+}
+
+int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p,
+                  float dMin, float dMax, float* depth, float* normal, float* conf, hcor_counts* counts) {
+	const int rc = estimate_begin(ref, srcs, V, gra, p, dMin, dMax, counts);
+	if (rc) return rc;
 	const int W = ref->width, H = ref->height;
-	if (evals) *evals = 0;
 	for (long i = 0; i < (long)W * H; ++i) /* DepthData::ApplyIgnoreMask */
 		if (!kept(p, i)) { depth[i] = 0; normal[3 * i] = normal[3 * i + 1] = normal[3 * i + 2] = 0; conf[i] = 0; }
 	if (p->median_blur) {
@@ -1244,9 +1354,20 @@ int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int V, const uint
 		memcpy(depth, tmp, sizeof(float) * (size_t)W * H);
 		free(tmp);
 	}
-	hcor_pass_score(ref, srcs, V, gra, p, dMin, dMax, depth, normal, conf, evals);
-	for (int iter = 0; iter < p->n_estimation_iters; ++iter)
-		hcor_pass_sweep(ref, srcs, V, gra, p, iter, dMin, dMax, depth, normal, conf, evals);
-	if (p->it_external == p->n_external_iters - 1) hcor_pass_end(p, W, H, depth, normal, conf);
+	hcor_pass_score(ref, srcs, V, gra, p, dMin, dMax, depth, normal, conf, counts);
+	sweeps_and_end(ref, srcs, V, gra, p, 0, p->n_estimation_iters, dMin, dMax, depth, normal, conf, counts);
+	return 0;
+}
+
+int hcor_estimate_sweeps(const hcor_view* ref, const hcor_view* srcs, int V, const uint8_t* gra, const hcor_params* p, int first_sweep,
+                         int n_sweeps, float dMin, float dMax, float* depth, float* normal, float* conf, hcor_counts* counts) {
+	if (first_sweep < 0 || n_sweeps < 1 || first_sweep + n_sweeps > 63) return 1;
+	if (!(p->ncc_threshold_keep > 0.f)) return 1;
+	hcor_params q = *p;
+	q.hint_depth = q.hint_normal = NULL; /* never offered here */
+	const int rc = estimate_begin(ref, srcs, V, gra, &q, dMin, dMax, counts);
+	if (rc) return rc;
+	if (q.spread_on && q.spread_maps && q.it_external >= 1) return 1; /* nothing pins view spread in this entry */
+	sweeps_and_end(ref, srcs, V, gra, &q, first_sweep, n_sweeps, dMin, dMax, depth, normal, conf, counts);
 	return 0;
 }

@@ -89,6 +89,14 @@ typedef struct {
 	 * given and it_external >= 1.  The maps must not alias depth / normal / conf (a sweep must not read what it writes). */
 	const hcor_spread_map* spread_maps;
 	int spread_on;
+	/* depth prior (--n-para_prior, --sigma-prior, --n-photo2geo; ScorePixelImage, DM.cpp:941-954; the term is stated at score_pixel in
+	 * hcmvs_oracle.c): W*H floats, NULL = none.  Active when a map is given, para_prior > 0 and it_external >= photo2geo; it applies
+	 * at the pixels whose prior is finite and > 0.  An active prior is refused together with view spread
+	 * and with a hint on the last outer iteration (return 2), as the library refuses them. */
+	const float* prior_map;
+	float para_prior;           /* --n-para_prior = 0.5 */
+	float sigma_prior;          /* --sigma-prior = 0.2 */
+	int photo2geo;              /* --n-photo2geo = 2: first outer iteration that blends the term */
 } hcor_params;
 
 void hcor_default_params(hcor_params* p);
@@ -148,6 +156,18 @@ float hcor_score_view(const hcor_view* ref, const hcor_view* src, const uint8_t*
 float hcor_score_pixel(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
                        const hcor_params* p, int x, int y, float depth, const float normal[3]);
 
+/* the depth prior's term piece by piece, over the helpers the scorer uses: the validity rule (D11: finite and > 0); out[0] =
+ * 1 - para_prior, out[1] = -1 / (2 sigma^2) as the device association holds them; 2 (1 - wP) para_prior of one hypothesis; DM.cpp:950
+ * on one view's score (a prior that is not usable leaves the score as it is) */
+int hcor_prior_usable(float prior);
+void hcor_prior_consts(float para, float sigma, float* out);
+float hcor_prior_addend(float prior, float depth, float para, float sigma, int mode);
+float hcor_prior_blend(float score, float prior, float depth, float para, float sigma, int mode);
+/* hcor_score_pixel with the prior value `prior` at the pixel (p's prior_map is not read; para_prior, sigma_prior, photo2geo are);
+ * view_scores (optional): the n_src view scores the aggregation ran over */
+float hcor_prior_score_pixel(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra, const hcor_params* p, int x, int y,
+                             float depth, const float normal[3], float prior, float* view_scores);
+
 /* Util.inl:614-626 */
 void hcor_normal2dir(const float n[3], float p[2], int arith_mode);
 void hcor_dir2normal(const float p[2], float n[3], int arith_mode);
@@ -179,18 +199,34 @@ void hcor_estimate_consts(const hcor_view* ref, const hcor_view* srcs, int n_src
  * depth/normal/conf: H*W, H*W*3, H*W in/out.  gra: H*W gradient map (SD.cpp:581-595).
  * Runs: [keep-mask applied] -> [median blur] -> pass A (SD.cpp:649-675) -> n_estimation_iters sweeps (SD.cpp:677-686,
  * DM.cpp:1050-1501) -> pass C when it_external == n_external_iters-1 (SD.cpp:688-744).
- * eval_count (optional): receives the number of ScorePixel evaluations performed. */
+ * This one path covers every variant the GPU is pinned to: the keep-mask, view spread, the `restore` hint and the depth prior are
+ * optional inputs of hcor_params, honoured by the passes in both sweep orders and with any thread count.
+ * counts (optional): receives the counters of the call.  Returns 0; 1 for arguments out of range; 2 for an active prior together
+ * with view spread or with a hint on the last outer iteration. */
+typedef struct {
+	uint64_t evals;        /* ScorePixel evaluations */
+	uint64_t evals_prior;  /* those that blended the prior's term: the evaluations of pixels with a usable prior while the prior is active */
+	uint64_t pixels_prior; /* estimated pixels (kept, inside the border) with a usable prior while the prior is active */
+} hcor_counts;
 int hcor_estimate(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
                   const hcor_params* p, float d_min, float d_max, float* depth, float* normal,
-                  float* conf, uint64_t* eval_count);
+                  float* conf, hcor_counts* counts);
+/* The reference's extra sweeps (SD.cpp:983-1031).  depth / normal / conf are taken as the state an estimate leaves between outer
+ * iterations (conf = the score): sweeps first_sweep .. first_sweep + n_sweeps - 1, then pass C under hcor_estimate's condition; no
+ * mask application, no median, no pass A.  The hint is never offered (p's is not read), as include/hcmvs_hip.h states for the
+ * library.  Returns 1 also for first_sweep < 0, n_sweeps < 1, first_sweep + n_sweeps > 63, ncc_threshold_keep not > 0 and for view
+ * spread (nothing pins it in this entry). */
+int hcor_estimate_sweeps(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
+                         const hcor_params* p, int first_sweep, int n_sweeps, float d_min, float d_max, float* depth,
+                         float* normal, float* conf, hcor_counts* counts);
 
-/* the three passes individually (same arguments), for per-pass parity tests */
+/* the three passes individually (same arguments), for per-pass parity tests; counts (optional): evals and evals_prior are added to */
 void hcor_pass_score(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
                      const hcor_params* p, float d_min, float d_max, float* depth, float* normal,
-                     float* conf, uint64_t* eval_count);
+                     float* conf, hcor_counts* counts);
 void hcor_pass_sweep(const hcor_view* ref, const hcor_view* srcs, int n_src, const uint8_t* gra,
                      const hcor_params* p, int iter, float d_min, float d_max, float* depth,
-                     float* normal, float* conf, uint64_t* eval_count);
+                     float* normal, float* conf, hcor_counts* counts);
 void hcor_pass_end(const hcor_params* p, int w, int h, float* depth, float* normal, float* conf);
 
 /* view spread (hcmvs_spread.inc).  Counters summed over every call since the last reset: slots scored, slots accepted, slots dropped

@@ -31,7 +31,13 @@ class Params(C.Structure):
                 ("random_smooth_bonus", C.c_float), ("photometric_flow", C.c_float), ("seed", C.c_uint32),
                 ("arith_mode", C.c_int), ("order", C.c_int), ("n_threads", C.c_int), ("median_blur", C.c_int),
                 ("hint_depth", C.POINTER(C.c_float)), ("hint_normal", C.POINTER(C.c_float)),
-                ("keep", C.POINTER(C.c_uint8)), ("spread_maps", C.POINTER(SpreadMap)), ("spread_on", C.c_int)]
+                ("keep", C.POINTER(C.c_uint8)), ("spread_maps", C.POINTER(SpreadMap)), ("spread_on", C.c_int),
+                ("prior_map", C.POINTER(C.c_float)), ("para_prior", C.c_float), ("sigma_prior", C.c_float), ("photo2geo", C.c_int)]
+
+
+class Counts(C.Structure):
+    """hcor_counts: what an estimate counted"""
+    _fields_ = [("evals", C.c_uint64), ("evals_prior", C.c_uint64), ("pixels_prior", C.c_uint64)]
 
 
 class DepthMap(C.Structure):
@@ -106,9 +112,20 @@ def lib():
         L.hcor_interpolate_pixel.argtypes = [C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, fp,
                                              C.c_float, C.c_float]
         L.hcor_interpolate_pixel.restype = C.c_float
+        L.hcor_prior_usable.argtypes = [C.c_float]
+        L.hcor_prior_usable.restype = C.c_int
+        L.hcor_prior_consts.argtypes = [C.c_float, C.c_float, fp]
+        L.hcor_prior_consts.restype = None
+        L.hcor_prior_addend.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]
+        L.hcor_prior_addend.restype = C.c_float
+        L.hcor_prior_blend.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]
+        L.hcor_prior_blend.restype = C.c_float
+        L.hcor_prior_score_pixel.argtypes = L.hcor_score_pixel.argtypes + [C.c_float, fp]
+        L.hcor_prior_score_pixel.restype = C.c_float
         est_args = [C.POINTER(View), C.POINTER(View), C.c_int, u8p, C.POINTER(Params), C.c_float, C.c_float, fp, fp,
-                    fp, C.POINTER(C.c_uint64)]
+                    fp, C.POINTER(Counts)]
         L.hcor_estimate.argtypes = est_args; L.hcor_estimate.restype = C.c_int
+        L.hcor_estimate_sweeps.argtypes = est_args[:5] + [C.c_int, C.c_int] + est_args[5:]; L.hcor_estimate_sweeps.restype = C.c_int
         L.hcor_pass_score.argtypes = est_args
         L.hcor_pass_sweep.argtypes = est_args[:5] + [C.c_int] + est_args[5:]
         L.hcor_estimate_consts.argtypes = [C.POINTER(View), C.POINTER(View), C.c_int, C.POINTER(Params), C.c_float, C.c_float, C.POINTER(EstConsts)]
@@ -234,10 +251,14 @@ def make_maps(maps):
     return arr
 
 
-def estimate(views, params, d_min, d_max, depth, normal, gra=None, keep=None, maps=None, on=False, conf=None):
+def estimate(views, params, d_min, d_max, depth, normal, gra=None, keep=None, maps=None, on=False, conf=None, prior=None, prior_params=None,
+             sweeps=None, stats=None):
     """Runs the oracle on views[0] (ref) vs views[1:].  depth (h,w), normal (h,w,3) and conf (h,w; None = zeros) are copied.
     keep: keep-mask (h, w) u8 (1 = estimated, 0 = ignored; None = no mask).  maps: the source views' spread maps as make_maps takes
-    them (None: no view has maps), on = --n-viewspread.  params itself is left as it was.
+    them (None: no view has maps), on = --n-viewspread.  prior: depth prior (h, w) float32 or None; prior_params: dict(para_prior,
+    sigma_prior, photo2geo), missing keys as params has them.  sweeps = (first_sweep, n_sweeps) runs hcor_estimate_sweeps on depth,
+    normal and conf (the state an estimate leaves between outer iterations).  stats: a dict that receives evals, evals_prior and
+    pixels_prior.  params itself is left as it was.
     Returns depth, normal, conf, evals."""
     L = lib()
     ref = make_view(views[0]); srcs = make_view_array(views[1:])
@@ -256,11 +277,55 @@ def estimate(views, params, d_min, d_max, depth, normal, gra=None, keep=None, ma
     if sm is not None:
         p.spread_maps = sm
     p.spread_on = int(bool(on))
-    ev = C.c_uint64(0)
-    rc = L.hcor_estimate(C.byref(ref), srcs, len(views) - 1, u8ptr(gra), C.byref(p), d_min, d_max, fptr(d),
-                         fptr(n), fptr(c), C.byref(ev))
-    assert rc == 0
-    return d, n, c, ev.value
+    pm = None if prior is None else np.ascontiguousarray(prior, np.float32)
+    if pm is not None:
+        assert pm.shape == (h, w)
+        p.prior_map = fptr(pm)
+    for key, v in (prior_params or {}).items():
+        assert key in ("para_prior", "sigma_prior", "photo2geo"), key
+        setattr(p, key, v)
+    ct = Counts()
+    head = (C.byref(ref), srcs, len(views) - 1, u8ptr(gra), C.byref(p))
+    tail = (d_min, d_max, fptr(d), fptr(n), fptr(c), C.byref(ct))
+    rc = L.hcor_estimate(*head, *tail) if sweeps is None else L.hcor_estimate_sweeps(*head, int(sweeps[0]), int(sweeps[1]), *tail)
+    assert rc == 0, rc
+    if stats is not None:
+        stats.update(evals=int(ct.evals), evals_prior=int(ct.evals_prior), pixels_prior=int(ct.pixels_prior))
+    return d, n, c, int(ct.evals)
+
+
+def prior_usable(x):
+    return bool(lib().hcor_prior_usable(C.c_float(x)))
+
+
+def prior_consts(para, sigma):
+    """(1 - para_prior, -1 / (2 sigma^2)) as the oracle derives them for the device association"""
+    out = (C.c_float * 2)()
+    lib().hcor_prior_consts(C.c_float(para), C.c_float(sigma), out)
+    return float(out[0]), float(out[1])
+
+
+def prior_addend(prior, depth, para, sigma, mode):
+    return float(lib().hcor_prior_addend(C.c_float(prior), C.c_float(depth), C.c_float(para), C.c_float(sigma), int(mode)))
+
+
+def prior_blend(score, prior, depth, para, sigma, mode):
+    return float(lib().hcor_prior_blend(C.c_float(score), C.c_float(prior), C.c_float(depth), C.c_float(para), C.c_float(sigma), int(mode)))
+
+
+def prior_score_pixel(views, params, x, y, depth, normal, prior, para=0.5, sigma=0.2, photo2geo=2, gra=None):
+    """ScorePixel of views[0] against views[1:] at (x, y), no smoothness neighbours, with the prior value `prior` at the pixel.
+    Returns (score, the V blended view scores)"""
+    ref = make_view(views[0]); srcs = make_view_array(views[1:])
+    if gra is None:
+        gra = gradient_map(views[0]["gray"])
+    p = Params.from_buffer_copy(params)
+    p.para_prior, p.sigma_prior, p.photo2geo = para, sigma, photo2geo
+    n = np.ascontiguousarray(normal, np.float32)
+    vs = np.zeros(len(views) - 1, np.float32)
+    s = lib().hcor_prior_score_pixel(C.byref(ref), srcs, len(views) - 1, u8ptr(gra), C.byref(p), int(x), int(y), C.c_float(depth), fptr(n),
+                                     C.c_float(prior), fptr(vs))
+    return float(s), vs
 
 
 def estimate_consts(views, params, d_min, d_max):

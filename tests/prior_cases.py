@@ -49,3 +49,12 @@ def estimated_pixels(shape, border, keep=None):
     m = np.zeros(shape, bool)
     m[border:h - border, border:w - border] = True
     return m if keep is None else m & (np.asarray(keep) != 0)
+
+
+def estimate(views, params, d_min, d_max, depth, normal, conf=None, prior=None, keep=None, gra=None, sweeps=None, **prior_params):
+    """oracle_lib.estimate with a prior (prior_params: para_prior, sigma_prior, photo2geo) and with its counters:
+    depth, normal, conf, dict(evals, evals_prior, pixels_prior)"""
+    st = {}
+    d, n, c, _ = O.estimate(views, params, d_min, d_max, depth, normal, gra=gra, keep=keep, conf=conf, prior=prior, prior_params=prior_params,
+                            sweeps=sweeps, stats=st)
+    return d, n, c, st

@@ -40,11 +40,16 @@ def gradient_map(view):
 
 
 def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=False, interleave=False, mode=O.ARITH_DEVICE, seed=1234,
-            n_threads=8, fuse=True, pf_kw=None, fuse_kw=None, hints=None, viewspread=False, **est_kw):
+            n_threads=8, fuse=True, pf_kw=None, fuse_kw=None, hints=None, viewspread=False, priors=None, prior_params=None, **est_kw):
     """views: {id: dict(gray, K, R, C[, bgr])}; srcs / neighbors: {id: [ids]}; order: fusion order; init: {id: (depth0, normal0, d_min, d_max)};
     hints: optional {id: (hint_depth, hint_normal)} (the `restore` variant's extra hypothesis, last sweep of the last outer iteration);
+    priors: optional {id: (h, w) float32}, the prior schedule of distributed.densify_scene(priors=...): on outer iteration
+    n_external_iters - 2 an image with a prior has it registered after its estimate and runs the reference's two extra sweeps (indices
+    n_estimation_iters and n_estimation_iters + 1); on the last outer iteration the prior stays registered; with fewer than two outer
+    iterations the priors are never used.  prior_params: dict(para_prior, sigma_prior, photo2geo), missing keys the reference's defaults;
     est_kw: oracle estimate parameters (adapthalfwin, n_estimation_iters, propagate_halfwin, ...).
-    Returns dict(maps={id: (depth, normal, conf)}, cloud=..., filled=[...], evals=int, spread=(scored, accepted, dropped, outside))."""
+    Returns dict(maps={id: (depth, normal, conf)}, cloud=..., filled=[...], evals=int, evals_prior=int,
+    spread=(scored, accepted, dropped, outside))."""
     ids = sorted(views)
     assert ids == list(range(len(ids)))
     gra = {i: gradient_map(views[i]) for i in ids}
@@ -54,11 +59,11 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
         cur[i] = dict(K=views[i]["K"], R=views[i]["R"], C=views[i]["C"], depth=np.ascontiguousarray(d0, np.float32).copy(),
                       normal=np.ascontiguousarray(n0, np.float32).copy(), conf=np.zeros(d0.shape, np.float32), bgr=views[i].get("bgr"),
                       d_min=float(dmin), d_max=float(dmax), neighbors=[n for n in neighbors[i] if n in views][:31])
-    filled, evals = [], 0
+    filled, evals, evals_prior, registered = [], 0, 0, set()
     O.stats(reset=True)
 
     def estimate(i, it, offered):
-        nonlocal evals
+        nonlocal evals, evals_prior
         kw = dict(est_kw)
         keep = []
         if hints is not None and i in hints and it == n_external_iters - 1:
@@ -71,9 +76,19 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
         maps = None
         if offered is not None:
             maps = [(offered[s]["depth"], offered[s]["normal"], offered[s]["conf"]) for s in srcs[i]]
-        d, n, c, ev = O.estimate(vs, p, cur[i]["d_min"], cur[i]["d_max"], cur[i]["depth"], cur[i]["normal"], gra=gra[i], maps=maps, on=viewspread)
-        cur[i]["depth"], cur[i]["normal"], cur[i]["conf"] = d, n, c
-        evals += ev
+        runs = [None]       # the estimate; then, on outer iteration n - 2, the prior's two extra sweeps (SceneDensify.cpp:983-1031)
+        if priors is not None and i in priors and it == n_external_iters - 2:
+            runs.append((p.n_estimation_iters, 2))
+        for sweeps in runs:
+            if sweeps is not None:
+                registered.add(i)
+            st = {}
+            d, n, c, ev = O.estimate(vs, p, cur[i]["d_min"], cur[i]["d_max"], cur[i]["depth"], cur[i]["normal"], gra=gra[i], maps=maps, on=viewspread,
+                                     conf=None if sweeps is None else cur[i]["conf"], prior=priors[i] if i in registered else None,
+                                     prior_params=prior_params, sweeps=sweeps, stats=st)
+            cur[i]["depth"], cur[i]["normal"], cur[i]["conf"] = d, n, c
+            evals += ev
+            evals_prior += st["evals_prior"]
 
     def post(i):
         dd, nd, cd, nf = O.postfilter([cur[k] for k in ids], i, gra[i], order, mode=mode, **(pf_kw or {}))
@@ -100,7 +115,7 @@ def densify(views, srcs, neighbors, order, init, n_external_iters=1, postfilter=
                 for i in ids:
                     post(i)
     out = dict(maps={i: (cur[i]["depth"].copy(), cur[i]["normal"].copy(), cur[i]["conf"].copy()) for i in ids}, filled=filled, evals=evals,
-               spread=O.stats())
+               evals_prior=evals_prior, spread=O.stats())
     if fuse:
         h, w = cur[ids[0]]["depth"].shape
         out["cloud"] = O.fuse_depthmaps([cur[k] for k in ids], list(order), h * w * len(ids) // 2 + 16, **(fuse_kw or {}))

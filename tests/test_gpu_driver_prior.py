@@ -1,7 +1,7 @@
 """Depth priors through the scene path: distributed.densify_scene(priors=...) and DensifyPointCloud --depth-priors (files in, files out)
-against the scene-level oracle of the prior schedule (tests/scene_oracle_prior.py), bit for bit: on outer iteration n - 2 the priors are
+against the scene-level oracle's prior schedule (tests/scene_oracle.py, priors=), bit for bit: on outer iteration n - 2 the priors are
 registered after the ordinary estimate and the reference's two extra sweeps run; on the last outer iteration they stay registered.
-The oracle's answer (single-threaded per image) is computed once for both tests."""
+The oracle's answer is computed once for both tests."""
 import importlib
 import os
 import subprocess
@@ -11,7 +11,7 @@ import pytest
 
 import oracle_lib as O
 import prior_cases as PC
-import scene_oracle_prior as SOP
+import scene_oracle as SO
 import test_gpu_driver_spread as DS
 import test_gpu_schedule as GS
 
@@ -33,7 +33,7 @@ def scene(tmp_path_factory):
     views, verts, scene_path = GS._driver_scene(tmp, n=4, w=128, h=96)
     oviews, srcs, neighbors, order, init = DS._oracle_inputs(views, verts)
     priors = {i: PC.make_prior(views[i], seed=i) for i in (0, 1, 3)}
-    want = SOP.densify(oviews, srcs, neighbors, order, init, priors, prior_params=PRIOR, n_external_iters=OUTER, seed=SEED, **KW)
+    want = SO.densify(oviews, srcs, neighbors, order, init, priors=priors, prior_params=PRIOR, n_external_iters=OUTER, seed=SEED, **KW)
     assert want["evals_prior"] > 0      # the term was at work (tests/test_prior_oracle.py: it changes the maps)
     return dict(tmp=tmp, views=views, scene_path=scene_path, oviews=oviews, srcs=srcs, neighbors=neighbors, order=order, init=init, priors=priors, want=want)
 

@@ -1,6 +1,6 @@
 """Depth priors (--n-para_prior, --sigma-prior, --n-photo2geo; DepthMap.cpp:941-954) on the GPU: estimates of reference views that carry a
-prior map (hcmvs_set_depth_prior[_device] + hcmvs_set_prior_params) and the sweeps-only entry, against the oracle variant
-(tests/oracle_prior.c) in device association, bit for bit -- depth, normal, conf, the evaluation count and the two prior counters.  Every
+prior map (hcmvs_set_depth_prior[_device] + hcmvs_set_prior_params) and the sweeps-only entry, against the oracle's prior inputs
+(oracle/hcmvs_oracle.c) in device association, bit for bit -- depth, normal, conf, the evaluation count and the two prior counters.  Every
 comparison with an active prior asserts on the oracle's side that the term was at work (evals_prior > 0, 50 .. 90 % of the estimated
 pixels carry a usable prior), so none passes without it."""
 import importlib
@@ -9,7 +9,6 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-import oracle_prior_lib as OP
 import prior_cases as PC
 
 pytestmark = pytest.mark.gpu
@@ -63,13 +62,13 @@ def oracle(key, cs, po, k, prior_kw, sweeps=None, start=None):
         p = O.Params.from_buffer_copy(po)
         p.seed = po.seed + 7 * k
         d, n, c = start if start is not None else (cs["d"], cs["n"], None)
-        _WANTS[(key, k)] = OP.estimate(cs["views"], p, cs["dmin"], cs["dmax"], d, n, conf=c, prior=cs["prior"], keep=cs["keep"], sweeps=sweeps, **prior_kw)
+        _WANTS[(key, k)] = PC.estimate(cs["views"], p, cs["dmin"], cs["dmax"], d, n, conf=c, prior=cs["prior"], keep=cs["keep"], sweeps=sweeps, **prior_kw)
     return _WANTS[(key, k)]
 
 
 def run(ctx, key, cases, pg, po, base=0, prior_kw=PRIOR, active=True, sweeps=None, starts=None):
     """one hcmvs_estimate_batch_device (or, with sweeps = (first, n), one hcmvs_estimate_sweeps_batch_device) over the cases against the
-    oracle variant.  Priors are registered from the host for even items, as device memory for odd ones.  active: the batch has an item
+    oracle.  Priors are registered from the host for even items, as device memory for odd ones.  active: the batch has an item
     whose prior is active.  Returns (stats, prior stats, the GPU's maps)."""
     import torch
     dev = torch.device("cuda:0")

@@ -1,12 +1,11 @@
-"""The oracle variant with a depth prior (tests/oracle_prior.c; DepthMap.cpp:941-954): known answers of the term, the aggregation over
-blended view scores, the estimate without a prior against the plain oracle, the sweeps-only entry and the two arithmetic modes."""
+"""The oracle's depth prior (oracle/hcmvs_oracle.c; DepthMap.cpp:941-954): known answers of the term, the aggregation over blended
+view scores, the estimate with an inactive prior against the one without, the sweeps-only entry and the two arithmetic modes."""
 import importlib
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
-import oracle_prior_lib as OP
 import prior_cases as PC
 
 synth = importlib.import_module("hc-mvs_amd.synth")
@@ -27,23 +26,23 @@ def test_known_answers_of_the_term(mode):
     for _ in range(200):
         score = float(f32(rng.uniform(0, 2))); prior = float(f32(rng.uniform(1, 20))); depth = float(f32(prior * rng.uniform(0.6, 1.4)))
         para = float(f32(rng.uniform(0.05, 1))); sigma = float(f32(rng.uniform(0.05, 0.5)))
-        got = OP.blend(score, prior, depth, para, sigma, mode)
+        got = O.prior_blend(score, prior, depth, para, sigma, mode)
         assert got == pytest.approx(term64(score, prior, depth, para, sigma), rel=2e-6, abs=2e-6)
     # a prior equal to the depth: dd = 0, wP = 1, the addend is 0 -- score * (1 - para_prior) exactly
     for score, para in ((0.37, 0.4), (1.2, 0.5), (0.0, 1.0), (0.66, 0.125)):
-        assert OP.blend(score, 7.25, 7.25, para, 0.2, mode) == float(f32(score) * (f32(1) - f32(para)))
-        assert OP.addend(7.25, 7.25, para, 0.2, mode) == 0.0
+        assert O.prior_blend(score, 7.25, 7.25, para, 0.2, mode) == float(f32(score) * (f32(1) - f32(para)))
+        assert O.prior_addend(7.25, 7.25, para, 0.2, mode) == 0.0
     # far from the prior the addend saturates at 2 * para_prior
-    assert OP.addend(5.0, 50.0, 0.4, 0.2, mode) == float(f32(2) * f32(0.4))
+    assert O.prior_addend(5.0, 50.0, 0.4, 0.2, mode) == float(f32(2) * f32(0.4))
 
 
 @pytest.mark.parametrize("mode", MODES)
 def test_validity_rule(mode):
     """finite and > 0; everything else leaves the score as it is, bit for bit"""
     for bad in (0.0, -0.0, -3.5, float("nan"), float("inf"), float("-inf")):
-        assert not OP.usable(bad)
-        assert OP.blend(0.4375, bad, 6.0, 0.5, 0.2, mode) == 0.4375
-    assert OP.usable(1e-30) and OP.usable(3.0e38)
+        assert not O.prior_usable(bad)
+        assert O.prior_blend(0.4375, bad, 6.0, 0.5, 0.2, mode) == 0.4375
+    assert O.prior_usable(1e-30) and O.prior_usable(3.0e38)
 
 
 def pixel_case(V=3, seed=21):
@@ -60,16 +59,16 @@ def test_pixel_score_sees_the_blended_views(mode):
     plain = float(O.lib().hcor_score_pixel(O.C.byref(O.make_view(views[0])), O.make_view_array(views[1:]), 3, O.u8ptr(O.gradient_map(views[0]["gray"])),
                                            O.C.byref(p), x, y, O.C.c_float(depth), O.fptr(normal)))
     # no prior at the pixel, and a prior before photo2geo: the plain score bit for bit
-    s0, v0 = OP.score_pixel(views, p, x, y, depth, normal, 0.0)
+    s0, v0 = O.prior_score_pixel(views, p, x, y, depth, normal, 0.0)
     assert s0 == plain
     p1 = O.default_params(adapthalfwin=6, it_external=1, n_external_iters=3, arith_mode=mode)
     plain1 = float(O.lib().hcor_score_pixel(O.C.byref(O.make_view(views[0])), O.make_view_array(views[1:]), 3, O.u8ptr(O.gradient_map(views[0]["gray"])),
                                             O.C.byref(p1), x, y, O.C.c_float(depth), O.fptr(normal)))
-    assert OP.score_pixel(views, p1, x, y, depth, normal, depth * 1.2)[0] == plain1
+    assert O.prior_score_pixel(views, p1, x, y, depth, normal, depth * 1.2)[0] == plain1
     # with a prior: every view that was scored is blended, the aggregation runs over the blended values
     prior = depth * 1.02
-    s, v = OP.score_pixel(views, p, x, y, depth, normal, prior)
-    want = [OP.blend(float(a), prior, depth, 0.5, 0.2, mode) for a in v0]
+    s, v = O.prior_score_pixel(views, p, x, y, depth, normal, prior)
+    want = [O.prior_blend(float(a), prior, depth, 0.5, 0.2, mode) for a in v0]
     assert list(v) == [f32(w) for w in want]
     two = sorted(want)[:2]
     assert s == float((f32(two[0]) + f32(two[1])) / f32(2))
@@ -85,16 +84,16 @@ def test_a_failed_view_stays_thRobust_and_the_blend_can_lift_a_view_over_it(mode
     views[2]["C"] = C2
     p = O.default_params(adapthalfwin=6, it_external=2, n_external_iters=3, arith_mode=mode)
     th = float(f32(p.ncc_threshold_keep) * f32(1.2))
-    s0, v0 = OP.score_pixel(views, p, x, y, depth, normal, 0.0)
+    s0, v0 = O.prior_score_pixel(views, p, x, y, depth, normal, 0.0)
     assert v0[1] == f32(th) and v0[0] < th and v0[2] < th
     far = depth * 3.0                                                          # addend = 2 * para_prior * (1 - wP) ~ 1: every valid view ends above thRobust
-    s, v = OP.score_pixel(views, p, x, y, depth, normal, far)
+    s, v = O.prior_score_pixel(views, p, x, y, depth, normal, far)
     assert v[1] == f32(th)                                                     # the failed view: not blended
     assert v[0] > th and v[2] > th
     lo = sorted(float(a) for a in v)
     assert lo[0] == th and s == th                                             # second best >= thRobust: the best view alone (DepthMap.cpp:1040)
     # a mild prior keeps the two valid views below thRobust: their mean
-    s, v = OP.score_pixel(views, p, x, y, depth, normal, depth)
+    s, v = O.prior_score_pixel(views, p, x, y, depth, normal, depth)
     assert s == float((f32(min(v[0], v[2])) + f32(max(v[0], v[2]))) / f32(2))
 
 
@@ -113,13 +112,13 @@ def test_without_a_prior_the_variant_is_the_plain_oracle(mode, it_external):
         p = O.default_params(adapthalfwin=6, n_estimation_iters=2, it_external=it_external, n_external_iters=3, arith_mode=mode, order=O.ORDER_ROWS,
                              n_threads=4, seed=5, **PC.KW)
         want = O.estimate(views, p, dmin, dmax, d, n, keep=kp)
-        got = OP.estimate(views, p, dmin, dmax, d, n, keep=kp)
+        got = PC.estimate(views, p, dmin, dmax, d, n, keep=kp)
         assert all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3])) and got[3]["evals"] == want[3]
         assert got[3]["evals_prior"] == 0 and got[3]["pixels_prior"] == 0
         # a registered prior that is not active: para_prior = 0, or photo2geo above the iteration
         prior = PC.make_prior(views[0], seed=1)
         for kw in (dict(para_prior=0.0), dict(photo2geo=it_external + 1)):
-            got = OP.estimate(views, p, dmin, dmax, d, n, keep=kp, prior=prior, **kw)
+            got = PC.estimate(views, p, dmin, dmax, d, n, keep=kp, prior=prior, **kw)
             assert all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3])) and got[3]["evals_prior"] == 0
 
 
@@ -128,8 +127,8 @@ def test_the_prior_changes_the_estimate_and_is_counted(mode):
     views, d, n, c, dmin, dmax = small_case()
     prior = PC.make_prior(views[0], seed=2)
     p = O.default_params(adapthalfwin=6, n_estimation_iters=2, it_external=2, n_external_iters=3, arith_mode=mode, seed=5, **PC.KW)
-    plain = OP.estimate(views, p, dmin, dmax, d, n)
-    got = OP.estimate(views, p, dmin, dmax, d, n, prior=prior)
+    plain = PC.estimate(views, p, dmin, dmax, d, n)
+    got = PC.estimate(views, p, dmin, dmax, d, n, prior=prior)
     est = PC.estimated_pixels(d.shape, 7)
     assert got[3]["pixels_prior"] == int((PC.usable(prior) & est).sum())
     assert 0.5 < got[3]["pixels_prior"] / est.sum() < 0.9
@@ -147,16 +146,51 @@ def test_sweeps_only_entry_continues_an_estimate(mode):
     N = 2
     kw = dict(adapthalfwin=6, it_external=1, n_external_iters=3, arith_mode=mode, seed=9, **PC.KW)
     pr = dict(prior=prior, para_prior=0.4, photo2geo=1)
-    a = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, d, n, **pr)
-    b = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N, 2), **pr)
-    whole = OP.estimate(views, O.default_params(n_estimation_iters=N + 2, **kw), dmin, dmax, d, n, **pr)
+    a = PC.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, d, n, **pr)
+    b = PC.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N, 2), **pr)
+    whole = PC.estimate(views, O.default_params(n_estimation_iters=N + 2, **kw), dmin, dmax, d, n, **pr)
     assert all(np.array_equal(x, y) for x, y in zip(b[:3], whole[:3]))
     assert a[3]["evals"] + b[3]["evals"] == whole[3]["evals"]
     assert a[3]["evals_prior"] + b[3]["evals_prior"] == whole[3]["evals_prior"]
     assert b[3]["pixels_prior"] == whole[3]["pixels_prior"] == a[3]["pixels_prior"]
     # and the sweep index decides direction and random stream: other indices give other maps
-    other = OP.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N + 1, 2), **pr)
+    other = PC.estimate(views, O.default_params(n_estimation_iters=N, **kw), dmin, dmax, a[0], a[1], conf=a[2], sweeps=(N + 1, 2), **pr)
     assert not np.array_equal(other[0], b[0])
+
+
+def test_the_refusals_and_their_codes():
+    """1: a sweep range out of bounds, ncc_threshold_keep not > 0 and view spread in the sweeps-only entry; 2: an active prior together
+    with view spread (both entries) or with a hint on the last outer iteration (hcor_estimate; the sweeps-only entry never offers the
+    hint).  A refused call leaves the maps alone; an inactive prior refuses nothing."""
+    views, d, n, c, dmin, dmax = small_case()
+    prior = PC.make_prior(views[0], seed=3)
+    ref = O.make_view(views[0]); srcs = O.make_view_array(views[1:]); gra = O.gradient_map(views[0]["gray"])
+    spread_maps = O.make_maps([(d.copy(), n.copy(), c.copy())] * 3)
+
+    def rc(sweeps=None, spread=False, hint=False, with_prior=True, **kw):
+        base = dict(PC.KW, adapthalfwin=6, n_estimation_iters=1, it_external=2, n_external_iters=3, arith_mode=O.ARITH_DEVICE, order=O.ORDER_ROWS,
+                    n_threads=4)
+        p = O.default_params(**dict(base, **kw))
+        if with_prior:
+            p.prior_map = O.fptr(prior)
+        if spread:
+            p.spread_maps = spread_maps; p.spread_on = 1
+        if hint:
+            p.hint_depth = O.fptr(d); p.hint_normal = O.fptr(n)
+        dd, nn, cc = d.copy(), n.copy(), c.copy()
+        head = (O.C.byref(ref), srcs, 3, O.u8ptr(gra), O.C.byref(p))
+        tail = (dmin, dmax, O.fptr(dd), O.fptr(nn), O.fptr(cc), None)
+        r = O.lib().hcor_estimate(*head, *tail) if sweeps is None else O.lib().hcor_estimate_sweeps(*head, sweeps[0], sweeps[1], *tail)
+        assert (r == 0) != (np.array_equal(dd, d) and np.array_equal(nn, n) and np.array_equal(cc, c))
+        return r
+
+    assert [rc(sweeps=s) for s in ((-1, 2), (2, 0), (62, 2), (61, 2))] == [1, 1, 1, 0]
+    assert rc(sweeps=(2, 2), ncc_threshold_keep=0.0) == 1
+    assert rc(sweeps=(2, 2), spread=True, with_prior=False) == 1 and rc(sweeps=(2, 2), spread=True, para_prior=0.0) == 1
+    assert rc(sweeps=(2, 2), spread=True) == 2 and rc(spread=True) == 2
+    assert rc(hint=True) == 2 and rc(sweeps=(2, 2), hint=True) == 0
+    assert rc(hint=True, it_external=1, photo2geo=1) == 0                       # an active prior, the hint not in effect
+    assert rc(hint=True, photo2geo=3) == 0 and rc(spread=True, para_prior=0.0) == 0   # in effect, the prior inactive
 
 
 def test_the_two_arithmetic_modes_agree_statistically():
@@ -166,8 +200,8 @@ def test_the_two_arithmetic_modes_agree_statistically():
     prior = PC.make_prior(views[0], seed=4)
     kw = dict(adapthalfwin=6, n_estimation_iters=4, n_threads=8, order=O.ORDER_ROWS)
     pr = dict(prior=prior, photo2geo=0)
-    r = OP.estimate(views, O.default_params(arith_mode=O.ARITH_REFERENCE, **kw), dmin, dmax, d0, n0, **pr)
-    v = OP.estimate(views, O.default_params(arith_mode=O.ARITH_DEVICE, **kw), dmin, dmax, d0, n0, **pr)
+    r = PC.estimate(views, O.default_params(arith_mode=O.ARITH_REFERENCE, **kw), dmin, dmax, d0, n0, **pr)
+    v = PC.estimate(views, O.default_params(arith_mode=O.ARITH_DEVICE, **kw), dmin, dmax, d0, n0, **pr)
     assert r[3]["evals_prior"] > 0
     both = (r[0] > 0) & (v[0] > 0)
     assert ((r[0] > 0) == (v[0] > 0)).mean() > 0.985

@@ -1,6 +1,6 @@
 """What the depth prior adds to the host plans (hc-mvs_amd/csrc/est_plan.h, sweep_plan.h), on the CPU: the refusals of the prior options,
-the active-prior rule, the batch-level refusals with the hint and with view spread, the term's constants bit for bit against the oracle
-variant's own derivation (tests/oracle_prior.c), the range of the sweeps-only call, the PRIOR kernel instances and the first-sweep offset.
+the active-prior rule, the batch-level refusals with the hint and with view spread, the term's constants bit for bit against the oracle's
+own derivation (oracle/hcmvs_oracle.c), the range of the sweeps-only call, the PRIOR kernel instances and the first-sweep offset.
 tests/prior_plan_shim.cpp is compiled with g++ alone, with -ffp-contract=off as the library is: no HIP, no library."""
 import ctypes as C
 import itertools
@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import oracle_prior_lib as OP
+import oracle_lib as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "hc-mvs_amd", "csrc")
@@ -59,7 +59,7 @@ def test_the_constants_against_the_oracle(lib):
     for para, sigma in cases:
         out = (C.c_float * 3)()
         assert lib.pp_consts(para, sigma, 4, out) == 4
-        keep, sig = OP.consts(para, sigma)
+        keep, sig = O.prior_consts(para, sigma)
         assert (float(out[0]), float(out[1]), float(out[2])) == (keep, float(f32(para)), sig)
         assert keep == float(f32(1) - f32(para)) and sig == float(f32(-1) / (f32(2) * (f32(sigma) * f32(sigma))))
     assert lib.pp_consts(0.5, 0.2, -1, (C.c_float * 3)()) == -1
