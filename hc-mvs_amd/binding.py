@@ -104,6 +104,26 @@ class PriorStats(C.Structure):
     _fields_ = [("evals_prior", C.c_uint64), ("pixels_prior", C.c_uint64)]
 
 
+class PlanePriorParams(C.Structure):
+    _fields_ = [("region_label", C.c_int32), ("conf_max", C.c_float), ("planarity_min", C.c_float), ("n_neighbors", C.c_int32), ("probability", C.c_float),
+                ("min_points_div", C.c_float), ("epsilon_mul", C.c_float), ("normal_threshold", C.c_float), ("max_rounds", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PriorPlane(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("n_inliers", C.c_uint32), ("centre", C.c_double * 3), ("quad", C.c_double * 8), ("box_fallback", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PlanePriorStats(C.Structure):
+    _fields_ = [("region_pixels", C.c_uint64), ("samples", C.c_uint64), ("planar_samples", C.c_uint64), ("fitting_samples", C.c_uint64),
+                ("avg_spacing_all", C.c_double), ("avg_spacing", C.c_double), ("eps", C.c_float), ("min_points", C.c_int32), ("rounds", C.c_int32),
+                ("planes", C.c_int32), ("candidates_valid", C.c_uint64), ("prior_pixels", C.c_uint64), ("ms_device", C.c_float), ("ms_gather", C.c_float), ("ms_search", C.c_float),
+                ("ms_rounds", C.c_float), ("ms_render", C.c_float), ("device_bytes", C.c_uint64)]
+
+
+MAX_PRIOR_PLANES = 64
+
+
 class FilterStats(C.Structure):
     _fields_ = [("n_processed", C.c_uint64), ("n_discarded", C.c_uint64), ("n_filtered", C.c_uint32), ("n_skipped", C.c_uint32),
                 ("batch", C.c_uint32), ("ms_device", C.c_float), ("device_bytes", C.c_uint64), ("image_processed", C.POINTER(C.c_uint64)),
@@ -132,7 +152,9 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats",
            "hcmvs_default_prior_params", "hcmvs_set_prior_params", "hcmvs_set_depth_prior", "hcmvs_set_depth_prior_device",
-           "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats"]
+           "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats",
+           "hcmvs_default_plane_prior_params", "hcmvs_set_prior_region", "hcmvs_get_prior_region", "hcmvs_generate_plane_prior_device",
+           "hcmvs_get_plane_prior_trace"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -300,6 +322,13 @@ def lib():
         L.hcmvs_set_depth_prior_device.argtypes = [vp, C.c_uint32, vp]
         L.hcmvs_estimate_sweeps_batch_device.argtypes = [vp, C.POINTER(BatchItem), C.c_int32, C.POINTER(Params), C.c_int32, C.c_int32]
         L.hcmvs_get_prior_stats.argtypes = [vp, C.POINTER(PriorStats)]
+        L.hcmvs_default_plane_prior_params.argtypes = [C.POINTER(PlanePriorParams)]
+        L.hcmvs_default_plane_prior_params.restype = None
+        L.hcmvs_set_prior_region.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint16), C.c_int32, C.c_int32, C.c_int32]
+        L.hcmvs_get_prior_region.argtypes = [vp, C.c_uint32, u8p]
+        L.hcmvs_generate_plane_prior_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(PlanePriorParams), vp, vp, C.POINTER(PriorPlane),
+                                                        C.POINTER(PlanePriorStats)]
+        L.hcmvs_get_plane_prior_trace.argtypes = [vp, u8p, i32p, i32p, C.c_int32, i32p]
         _lib = L
     return _lib
 
@@ -319,6 +348,17 @@ def default_prior_params(**kw):
     lib().hcmvs_default_prior_params(C.byref(p))
     for k, v in kw.items():
         assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def default_plane_prior_params(**kw):
+    """hcmvs_default_plane_prior_params: the reference's values (255, 0.18, 0.3, 10, 0.01, 80, 2, 0.25), 256 rounds, seed 1; then the overrides"""
+    p = PlanePriorParams()
+    lib().hcmvs_default_plane_prior_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
         setattr(p, k, v)
     return p
 
@@ -574,6 +614,52 @@ class Context:
         s = PriorStats()
         self._chk(lib().hcmvs_get_prior_stats(self._h, C.byref(s)))
         return {k: int(getattr(s, k)) for k, _ in PriorStats._fields_}
+
+    # ---- plane priors (GenerateDepthPrior, SceneDensify.cpp:1550-1950) --------------
+
+    def set_prior_region(self, vid, labels, region_label=255):
+        """the region of view vid in which planes are fitted: the pixels of the 16-bit label image (any size, resampled INTER_NEAREST to
+        the view's) that equal region_label; None removes the region"""
+        if labels is None:
+            self._chk(lib().hcmvs_set_prior_region(self._h, vid, None, 0, 0, 0))
+            return
+        lab = np.ascontiguousarray(labels, np.uint16)
+        assert lab.ndim == 2
+        self._chk(lib().hcmvs_set_prior_region(self._h, vid, lab.ctypes.data_as(C.POINTER(C.c_uint16)), lab.shape[1], lab.shape[0], int(region_label)))
+
+    def get_prior_region(self, vid):
+        """(h, w) u8, 1 = inside the region (all 0 without one)"""
+        h, w = self.shapes[vid]
+        out = np.empty((h, w), np.uint8)
+        self._chk(lib().hcmvs_get_prior_region(self._h, vid, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def generate_plane_prior_device(self, vid, d_depth_ptr, d_normal_ptr, d_conf_ptr, d_prior_ptr, d_prior_normal_ptr=None, params=None):
+        """hcmvs_generate_plane_prior_device: the prior of view vid from its maps in device memory (the state an estimate leaves between
+        outer iterations; read only) into d_prior_ptr (h*w f32, every pixel written) and, when given, d_prior_normal_ptr (h*w*3 f32).
+        Blocking.  Returns (planes, stats): planes a list of dicts(normal, n_inliers, centre, quad (4, 2), box_fallback), stats a dict of
+        the hcmvs_plane_prior_stats fields.  The prior feeds set_depth_prior_device unchanged"""
+        p = params if params is not None else default_plane_prior_params()
+        tab = (PriorPlane * MAX_PRIOR_PLANES)()
+        st = PlanePriorStats()
+        self._chk(lib().hcmvs_generate_plane_prior_device(self._h, vid, C.c_void_p(d_depth_ptr) if d_depth_ptr else None,
+                                                          C.c_void_p(d_normal_ptr) if d_normal_ptr else None, C.c_void_p(d_conf_ptr) if d_conf_ptr else None,
+                                                          C.byref(p), C.c_void_p(d_prior_ptr) if d_prior_ptr else None,
+                                                          C.c_void_p(d_prior_normal_ptr) if d_prior_normal_ptr else None, tab, C.byref(st)))
+        planes = [dict(normal=np.array(list(t.normal), np.float32), n_inliers=int(t.n_inliers), centre=np.array(list(t.centre), np.float64),
+                       quad=np.array(list(t.quad), np.float64).reshape(4, 2), box_fallback=int(t.box_fallback)) for t in tab[:st.planes]]
+        return planes, {k: getattr(st, k) for k, _ in PlanePriorStats._fields_}
+
+    def plane_prior_trace(self, vid):
+        """the decisions of the last generate_plane_prior_device (of view vid's size): dict(stage (h, w) u8: 0 outside the region, 1 region,
+        2 sample, 3 planar, 4 fitting set; assignment (h, w) i32: plane or -1; rounds (n, 6) i32: winner or -1, cnt_0 .. cnt_3, valid candidates)"""
+        h, w = self.shapes[vid]
+        stage = np.empty((h, w), np.uint8); asg = np.empty((h, w), np.int32); n = C.c_int32()
+        i32p = C.POINTER(C.c_int32)
+        self._chk(lib().hcmvs_get_plane_prior_trace(self._h, stage.ctypes.data_as(C.POINTER(C.c_uint8)), asg.ctypes.data_as(i32p), None, 0, C.byref(n)))
+        rounds = np.zeros((max(n.value, 1), 6), np.int32)
+        self._chk(lib().hcmvs_get_plane_prior_trace(self._h, None, None, rounds.ctypes.data_as(i32p), n.value, C.byref(n)))
+        return dict(stage=stage, assignment=asg, rounds=rounds[:n.value])
 
     def stats(self):
         s = Stats()

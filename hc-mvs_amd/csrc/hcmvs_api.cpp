@@ -21,6 +21,7 @@
 #include "init_kernels.h"
 #include "handoff_kernels.h"
 #include "handoff_host.h"
+#include "prior_kernels.h"
 #include "dev_buf.h"
 
 #include <cmath>
@@ -42,7 +43,7 @@ constexpr uint32_t kMaxViewId = 65536;      // view ids, and the ids a neighbour
 
 struct View {
 	View() = default;
-	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), keep(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r), priorMem(r) {}
+	explicit View(Reclaimer* r) : grayMem(r), bgrMem(r), gra(r), keep(r), quads(r), depthMem(r), normalMem(r), confMem(r), dNeighbors(r), priorMem(r), region(r) {}
 	int w = 0, h = 0;
 	float* gray = nullptr;   // device: the caller's (hcmvs_set_view_device) or grayMem
 	uint8_t* bgr = nullptr;  // device or null: the caller's or bgrMem
@@ -63,6 +64,7 @@ struct View {
 	// depth prior of the view as a REFERENCE view, w * h floats: the caller's (hcmvs_set_depth_prior_device) or priorMem; null = none
 	const float* prior = nullptr;
 	DevBuf priorMem;
+	DevBuf region;           // hcmvs_set_prior_region: u8 per pixel as the ignore-mask kernel writes it, 0 = INSIDE the region; empty = no region
 };
 
 } // namespace
@@ -132,11 +134,17 @@ struct hcmvs_ctx final : Reclaimer {
 	Event handoffEv[2]; // timing: around the kernels
 	hcmvs_handoff_stats handoffStats = {};
 	bool haveHandoffStats = false;
+	// hcmvs_generate_plane_prior_device: the scratch of a call, kept for hcmvs_get_plane_prior_trace
+	// (the reclaimer gives it back when memory is short: the trace is then gone, the next generate call allocates again)
+	DevBuf priorGenKept{this};
+	PriorGenTrace priorTrace;
 
 	bool reclaim() override {
-		if (!pfState.capacity()) return false;
+		if (!pfState.capacity() && !priorGenKept.capacity()) return false;
 		(void)hipStreamSynchronize(stream);
 		pfState.reset();
+		priorGenKept.reset(); // the plane-prior scratch is only kept for hcmvs_get_plane_prior_trace
+		priorTrace = PriorGenTrace();
 		return true;
 	}
 };
@@ -789,6 +797,101 @@ int hcmvs_get_prior_stats(hcmvs_ctx* c, hcmvs_prior_stats* out) {
 }
 
 // ---- view spread (DensifyPointCloud --n-viewspread, DepthMap.cpp:1504-1608) ----
+
+// ---- plane priors (DepthMapsData::GenerateDepthPrior, SceneDensify.cpp:1550-1950) ----
+
+void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p) {
+	if (!p) return;
+	memset(p, 0, sizeof *p);
+	p->region_label = 255; p->conf_max = 0.18f; p->planarity_min = 0.3f; p->n_neighbors = 10; // SceneDensify.cpp:1625, :1648-1681
+	p->probability = 0.01f; p->min_points_div = 80.f; p->epsilon_mul = 2.f;                    // DensifyPointCloud.cpp --ransac-*
+	p->normal_threshold = 0.25f; p->max_rounds = 256; p->seed = 1;
+}
+int hcmvs_set_prior_region(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, int32_t region_label) {
+	if (!c) return HCMVS_ERR_INVALID;
+	View* pv = find_view(c, "set_prior_region", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	View& v = *pv;
+	HIPCHK(c, hipSetDevice(c->device));
+	if (!labels) {
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		v.region.reset();
+		return HCMVS_OK;
+	}
+	if (v.rescaled) return fail(c, HCMVS_ERR_INVALID, "set_prior_region: view %u was made by hcmvs_rescale_view: only a reference view has a prior", id);
+	if (lw < 1 || lh < 1 || lw > 65536 || lh > 65536) return fail(c, HCMVS_ERR_INVALID, "set_prior_region: bad label image %dx%d (view %u)", lw, lh, id);
+	// the ignore mask's resize: the region is where that mask would be 0 (a label outside 0 .. 65535 matches no 16-bit value)
+	const bool matches = region_label >= 0 && region_label <= 65535;
+	const size_t imgBytes = (size_t)lw * lh * sizeof(uint16_t);
+	Carve cv;
+	const size_t oImg = cv(imgBytes), oLab = cv(2 * sizeof(int32_t));
+	HIPCHK(c, c->maskStage.reserve(cv.size, c->stream));
+	HIPCHK(c, v.region.reserve((size_t)v.w * v.h, c->stream));
+	const int rc = upload_staged(c, c->maskStage.get() + oImg, labels, imgBytes);
+	if (rc) return rc;
+	int32_t* dLabel = (int32_t*)(c->maskStage.get() + oLab);
+	if (matches) HIPCHK(c, hipMemcpyAsync(dLabel, &region_label, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+	launch_ignore_mask((const uint16_t*)(c->maskStage.get() + oImg), lw, lh, dLabel, matches ? 1 : 0, v.region.get<uint8_t>(), v.w, v.h, c->stream);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // (region_label and the staging go on being used by the next call)
+	return HCMVS_OK;
+}
+int hcmvs_get_prior_region(hcmvs_ctx* c, uint32_t id, uint8_t* region) {
+	if (!c || !region) return HCMVS_ERR_INVALID;
+	const View* pv = find_view(c, "get_prior_region", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const size_t n = (size_t)pv->w * pv->h;
+	if (!pv->region.capacity()) { memset(region, 0, n); return HCMVS_OK; }
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipMemcpyAsync(region, pv->region.get(), n, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	for (size_t i = 0; i < n; ++i) region[i] = region[i] ? 0 : 1;
+	return HCMVS_OK;
+}
+int hcmvs_generate_plane_prior_device(hcmvs_ctx* c, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf,
+                                      const hcmvs_plane_prior_params* params, float* d_prior, float* d_prior_normal, hcmvs_prior_plane* planes,
+                                      hcmvs_plane_prior_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const View* pv = find_view(c, "generate_plane_prior", id);
+	if (!pv) return HCMVS_ERR_INVALID;
+	const View& v = *pv;
+	const PriorGenArgs args = {(uintptr_t)d_depth, (uintptr_t)d_normal, (uintptr_t)d_conf, (uintptr_t)d_prior, (uintptr_t)d_prior_normal, v.w, v.h, v.K, params};
+	const std::string why = prior_gen_check(args);
+	if (!why.empty()) return fail(c, HCMVS_ERR_INVALID, "generate_plane_prior: %s (view %u)", why.c_str(), id);
+	HIPCHK(c, hipSetDevice(c->device));
+	hcmvs_plane_prior_stats st;
+	std::string err;
+	const int rc = generate_plane_prior_device(v.w, v.h, v.K, v.region.capacity() ? v.region.get<uint8_t>() : nullptr, d_depth, d_normal, d_conf, *params, d_prior,
+	                                           d_prior_normal, planes, st, c->priorGenKept, c->priorTrace, c->stream, err);
+	if (rc) { c->priorTrace = PriorGenTrace(); return fail(c, HCMVS_ERR_HIP, "%s", err.c_str()); }
+	if (stats) *stats = st;
+	return HCMVS_OK;
+}
+int hcmvs_get_plane_prior_trace(hcmvs_ctx* c, uint8_t* stage, int32_t* assignment, int32_t* rounds, int32_t rounds_capacity, int32_t* n_rounds) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const PriorGenTrace& t = c->priorTrace;
+	if (rounds && rounds_capacity < 0) return fail(c, HCMVS_ERR_INVALID, "get_plane_prior_trace: negative capacity");
+	const size_t px = (size_t)t.w * t.h, nRounds = t.rounds.size() / 6;
+	if (n_rounds) *n_rounds = (int32_t)nRounds;
+	if (rounds) memcpy(rounds, t.rounds.data(), sizeof(int32_t) * 6 * std::min(nRounds, (size_t)rounds_capacity));
+	if (!stage && !assignment) return HCMVS_OK;
+	if (!t.valid) return fail(c, HCMVS_ERR_INVALID, "get_plane_prior_trace: no hcmvs_generate_plane_prior_device has looked at a region");
+	HIPCHK(c, hipSetDevice(c->device));
+	const char* b = c->priorGenKept.get();
+	if (stage) HIPCHK(c, hipMemcpyAsync(stage, b + t.lay.stage, px, hipMemcpyDeviceToHost, c->stream));
+	std::vector<int32_t> pix, asg;
+	if (assignment && t.n0) {
+		pix.resize(t.n0); asg.resize(t.n0);
+		HIPCHK(c, hipMemcpyAsync(pix.data(), b + t.lay.pixA, t.n0 * 4, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipMemcpyAsync(asg.data(), b + t.lay.assigned, t.n0 * 4, hipMemcpyDeviceToHost, c->stream));
+	}
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	if (assignment) {
+		for (size_t i = 0; i < px; ++i) assignment[i] = -1;
+		for (size_t i = 0; i < t.n0; ++i) assignment[pix[i]] = asg[i];
+	}
+	return HCMVS_OK;
+}
 
 int hcmvs_set_viewspread(hcmvs_ctx* c, int32_t on) {
 	if (!c) return HCMVS_ERR_INVALID;

@@ -132,7 +132,8 @@ def _handoff(ctx, dev, mode, jobs, w, h):
 
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
                   fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
-                  geometric_filter=None, gf_kw=None, hints=None, fuse=True, priors=None, prior_params=None):
+                  geometric_filter=None, gf_kw=None, hints=None, fuse=True, priors=None, prior_params=None,
+                  plane_priors=None, plane_prior_params=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -199,6 +200,14 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                iterations the priors are never registered -- the result then carries priors_used = False; nothing is raised.  Priors belong
                to reference images, so ranks exchange nothing new: a rank registers those of its own images.  Not together with viewspread
                or hints (ValueError: the library refuses the combination)
+    plane_priors: optional {image id: label image (any size, 16-bit)}: the priors of those REFERENCE images are GENERATED on the device
+               (binding.Context.generate_plane_prior_device) from planes fitted inside the pixels labelled
+               plane_prior_params.region_label (binding.default_plane_prior_params(); None: the defaults, label 255): on outer iteration
+               n_external_iters - 2, after the ordinary estimate of a batch, from each listed image's live maps into a tensor this call
+               owns; from there the path is exactly that of priors= (register, sweeps N and N + 1, registered for the last iteration).  The
+               result carries plane_prior_maps {id: (h, w) device tensor} and plane_prior_planes {id: plane count} of this rank's images.
+               The call OWNS the prior regions of the listed images: it registers them (Context.set_prior_region) and removes them at the end,
+               a region the caller had registered for such an image included.  An id in both priors and plane_priors is a ValueError; the refusals of priors= apply (viewspread, hints)
     geometric_filter: None (default: off), "adjust" or "strict": the depth-map filter stage (Scene::DenseReconstructionFilter,
                SceneDensify.cpp:4100-4185; binding.Context.filter_sequence) over ALL images between the final all-gather and the fusion.
                Replicated on every rank like the fusion -- every rank filters identical gathered maps with a deterministic kernel, and a
@@ -294,17 +303,36 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             ctx.set_spread_maps_device(img, base, base + 4 * hw, base + 16 * hw)
 
     priors = dict(priors) if priors else {}
-    if priors and (viewspread or hints):
+    plane_priors = dict(plane_priors) if plane_priors else {}
+    both = sorted(set(priors) & set(plane_priors))
+    if both:
+        raise ValueError("densify_scene: image %d is listed in priors and in plane_priors" % both[0])
+    if (priors or plane_priors) and (viewspread or hints):
         raise ValueError("densify_scene: depth priors are not combined with viewspread or hints (the library refuses an active prior together with either)")
-    prior_it = int(n_external_iters) - 2 if priors else -1      # the outer iteration that registers the priors and runs the two extra sweeps
-    if priors:
+    prior_it = int(n_external_iters) - 2 if (priors or plane_priors) else -1      # the outer iteration that registers the priors and runs the two extra sweeps
+    if priors or plane_priors:
         ctx.set_prior_params(**(prior_params or {}))
     prior_keep = []
+    plane_maps, plane_counts = {}, {}
+    ppp = plane_prior_params
+    if plane_priors and ppp is None:
+        from .binding import default_plane_prior_params
+        ppp = default_plane_prior_params()
+    if prior_it >= 0:
+        for img in mine:
+            if img in plane_priors:
+                ctx.set_prior_region(img, plane_priors[img], ppp.region_label)
 
     def extra_sweeps(items):        # after the ordinary estimate of `items` on outer iteration prior_it: their priors, then sweeps N and N + 1
-        extra = [x for x in items if x["ref_id"] in priors]
+        extra = [x for x in items if x["ref_id"] in priors or x["ref_id"] in plane_priors]
         for x in extra:
-            m = priors[x["ref_id"]]
+            if x["ref_id"] in plane_priors:     # generated from the live maps of the image (ordered behind its estimate on the context's stream)
+                m = torch.empty(h, w, dtype=torch.float32, device=dev)
+                _device_sync(dev)
+                planes, _ = ctx.generate_plane_prior_device(x["ref_id"], x["d_depth"], x["d_normal"], x["d_conf"], m.data_ptr(), None, ppp)
+                plane_maps[x["ref_id"]] = m; plane_counts[x["ref_id"]] = len(planes)
+            else:
+                m = priors[x["ref_id"]]
             if torch.is_tensor(m):
                 assert m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and tuple(m.shape) == (h, w)
                 prior_keep.append(m)
@@ -407,11 +435,15 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             ctx.set_viewspread(False)
             for img in ids:
                 ctx.set_spread_maps_device(img, None, None, None)
-        if priors:
+        if priors or plane_priors:
             cloud["priors_used"] = prior_it >= 0
             for img in mine:
-                if img in priors and prior_it >= 0:
+                if (img in priors or img in plane_priors) and prior_it >= 0:
                     ctx.set_depth_prior(img, None)
+                if img in plane_priors and prior_it >= 0:
+                    ctx.set_prior_region(img, None)
+        if plane_priors:
+            cloud["plane_prior_maps"] = plane_maps; cloud["plane_prior_planes"] = plane_counts
         cloud["_keep"] = (allm, allr, slabs, hintbuf, prior_keep)      # the registered device maps must outlive the context's use of them
         return cloud
 

@@ -16,8 +16,9 @@
  * (--n-initTriangulate 0, the fork's hand-off, SceneDensify.cpp:527-553) or from a splat (--min-views-trust-point 1); --n-nOptimize
  * gates the fork's post-filters (RemoveSmallSegments + GapInterpolation) as in the reference; --n-viewspread 1 lets every pixel also try
  * the estimates of its source views' own maps from outer iteration 1 on (DepthMap.cpp:1504-1608; default 0 here, 1 in the reference, so
- * that existing command lines keep their results; one device); optical flow, semantic priors and SGM modes are not available and
- * the corresponding flags are accepted and ignored with a note.
+ * that existing command lines keep their results; one device); --plane-priors 1 generates depth priors from planes fitted inside the
+ * label 255 of seman/<stem>.quad.pgm|ppm on outer iteration n - 2 (--export-priors <dir> writes them);
+ * optical flow, --use-semantic and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
  *
  * How the run is laid out in time (the reference overlaps image k + 1's InitViews with image k's estimate, SceneDensify.cpp:3699-3703;
  * here the unit is a batch of reference images):
@@ -272,7 +273,9 @@ struct ImageData : PlanImage {
 	float *dDepth = nullptr, *dNormal = nullptr, *dConf = nullptr; // device maps, on the owner's device
 	float *gDepth = nullptr, *gNormal = nullptr, *gConf = nullptr; // the copy on the first device, where the post-filters and the fusion run (== d* when dev == 0)
 	float *dHintDepth = nullptr, *dHintNormal = nullptr;            // previous level's maps, resized (restore variant)
-	std::vector<float> prior;                                       // --depth-priors: the image's prior depth map (w * h), empty: none
+	std::vector<float> prior;                                       // --depth-priors: the image's prior depth map (w * h), empty: none; --plane-priors 1: the
+	                                                                // generated one, filled on outer iteration n - 2
+	bool hasRegion = false;                                         // --plane-priors 1: a label file was found and its region registered
 	// what a depth-map file says about its image: scene image ids, not the ids of resampled copies
 	DmapImage file_header() const { return DmapImage{name, id, w, h, cam.K, cam.R, cam.C, srcImages.empty() ? srcs : srcImages, dMin, dMax}; }
 };
@@ -575,6 +578,31 @@ private:
 	}
 };
 
+// --plane-priors 1: the prior of `im` from its live maps (ordered behind its estimate on the context's stream), into im.prior -- where
+// --depth-priors would have put the file's -- and, with --export-priors, into the file a later run can read
+bool generate_plane_prior(Run& r, hcmvs_ctx* dctx, ImageData& im, const hcmvs_batch_item& itx, std::string& err) {
+	hcmvs_plane_prior_params pp;
+	hcmvs_default_plane_prior_params(&pp);
+	pp = plane_prior_params(r.o, pp);
+	float* dPrior = nullptr;
+	if (hipMalloc(&dPrior, im.pixels() * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); err = "out of device memory for a plane prior"; return false; }
+	hcmvs_plane_prior_stats st;
+	im.prior.resize(im.pixels());
+	const bool ok = hcmvs_generate_plane_prior_device(dctx, im.id, (const float*)itx.d_depth, (const float*)itx.d_normal, (const float*)itx.d_conf, &pp, dPrior, nullptr,
+	                                                  nullptr, &st) == HCMVS_OK &&
+	                hipMemcpy(im.prior.data(), dPrior, im.pixels() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+	(void)hipFree(dPrior);
+	if (!ok) { err = std::string("generating the plane prior of image ") + std::to_string(im.id) + " failed (" + hcmvs_last_error(dctx) + ")"; return false; }
+	if (r.o.verbosity > 2)
+		printf("Plane prior of image %3u: %d planes from %llu samples (%llu in the fitting set), %llu prior pixels, %.1f ms\n", im.id, st.planes,
+		       (unsigned long long)st.samples, (unsigned long long)st.fitting_samples, (unsigned long long)st.prior_pixels, st.ms_device);
+	if (!r.o.exportPriors.empty()) {
+		DmapImage hd = im.file_header();
+		if (!save_dmap(export_prior_path(r.o, im.id), hd, im.prior.data(), nullptr, nullptr)) { err = "can not write '" + export_prior_path(r.o, im.id) + "'"; return false; }
+	}
+	return true;
+}
+
 // ---- what the workers and the main thread both do ------------------------------------------------------------------------------------
 // one launch set for the reference images `ids` (all of device context d)
 bool estimate_images(Run& r, int d, const std::vector<uint32_t>& ids, const hcmvs_params& pr, std::string& err) {
@@ -598,7 +626,8 @@ bool estimate_images(Run& r, int d, const std::vector<uint32_t>& ids, const hcmv
 	if (prior_sweeps_after(r.o, pr.it_external)) {
 		std::vector<hcmvs_batch_item> extra;
 		for (const auto& itx : items) {
-			const ImageData& im = r.images[itx.ref_id];
+			ImageData& im = r.images[itx.ref_id];
+			if (r.o.planePriors && im.hasRegion && !generate_plane_prior(r, dctx, im, itx, err)) return false;
 			if (im.prior.empty()) continue;
 			if (hcmvs_set_depth_prior(dctx, im.id, im.prior.data()) != HCMVS_OK) { err = std::string("registering the depth prior failed (") + hcmvs_last_error(dctx) + ")"; return false; }
 			extra.push_back(itx);
@@ -1026,6 +1055,45 @@ bool set_ignore_masks(Run& r) {
 		       pxAll ? 100.0 * (double)pxIgnored / (double)pxAll : 0.0);
 	return true;
 }
+// --plane-priors 1: the label image of every image to estimate, found as the ignore mask's is (seman/<stem>.quad.pgm|ppm), registers the
+// region of the label 255 on the context that estimates the image; an image without a label file has no prior
+bool set_prior_regions(Run& r) {
+	const Options& o = r.o;
+	if (!o.planePriors) return true;
+	if (priors_never_used(o) && o.verbosity > 1)
+		fprintf(stderr, "note: --plane-priors 1 needs two outer iterations or more (--n-EstimationIters-external %d): no prior is generated\n", o.estimationItersExternal);
+	if (!o.exportPriors.empty()) (void)mkdir(o.exportPriors.c_str(), 0777);
+	hcmvs_prior_params pp;
+	pp.para_prior = o.paraPrior; pp.sigma_prior = o.sigmaPrior; pp.photo2geo = o.photo2geo;
+	for (DeviceCtx& d : r.devs)
+		if (hcmvs_set_prior_params(d.ctx, &pp) != HCMVS_OK) { fprintf(stderr, "error: %s\n", hcmvs_last_error(d.ctx)); return false; }
+	size_t nRegions = 0;
+	for (uint32_t id : r.work) {
+		ImageData& im = r.images[id];
+		const size_t sl = im.name.find_last_of('/');
+		std::string stem = sl == std::string::npos ? im.name : im.name.substr(sl + 1);
+		if (stem.find_last_of('.') != std::string::npos) stem = stem.substr(0, stem.find_last_of('.'));
+		const std::string base = dirname_of(r.paths[id]) + "/seman/" + stem + ".quad";
+		std::vector<uint16_t> lab;
+		int lw = 0, lh = 0;
+		bool found = false;
+		for (const char* ext : {".pgm", ".ppm"})
+			if (load_labels(base + ext, lw, lh, lab)) { found = true; break; }
+		if (!found) {
+			if (o.verbosity > 1) fprintf(stderr, "warning: no label image '%s.pgm' or '%s.ppm': image %u gets no plane prior\n", base.c_str(), base.c_str(), id);
+			continue;
+		}
+		hcmvs_ctx* dctx = r.devs[(size_t)im.dev].ctx;
+		if (hcmvs_set_prior_region(dctx, id, lab.data(), lw, lh, 255) != HCMVS_OK) { fprintf(stderr, "error: the prior region of image %u failed (%s)\n", id, hcmvs_last_error(dctx)); return false; }
+		im.hasRegion = true;
+		++nRegions;
+	}
+	HIPOK(hipSetDevice(o.device));
+	if (o.verbosity > 1)
+		printf("Plane priors: %zu of %zu images to estimate have a label image; probability %g, epsilon %g, min-points %g, seed %llu\n", nRegions, r.work.size(),
+		       (double)o.ransacProbability, (double)o.ransacEpsilon, (double)o.ransacMinPoints, o.sampleSeed);
+	return true;
+}
 // --depth-priors <folder>: <folder>/depth%04u.prior.dmap per image that is estimated, a raw 'DR' depth map of the image's size at the run's
 // resolution level; only the depth is read.  A file of another size is an error naming it; an image without a file has no prior.
 bool load_depth_priors(Run& r) {
@@ -1276,7 +1344,7 @@ int main(int argc, char** argv) {
 	list_todo(r);
 	if (!deal_and_budget(r) || !resume_finished(r)) return EXIT_FAILURE;
 	plan_image_batches(r);
-	if (!load_images(r) || !rescale_neighbours(r) || !set_ignore_masks(r) || !load_depth_priors(r)) return EXIT_FAILURE;
+	if (!load_images(r) || !rescale_neighbours(r) || !set_ignore_masks(r) || !load_depth_priors(r) || !set_prior_regions(r)) return EXIT_FAILURE;
 	if (!start_saver_and_workers(r) || !run_outer_iterations(r) || !finish_estimates(r)) return EXIT_FAILURE;
 	if (!filter_stage(r) || !final_maps_on_host(r)) return EXIT_FAILURE;
 	if (o.fusionMode == 1 || r.todo.empty()) return finish_without_fusion(r) ? EXIT_SUCCESS : EXIT_FAILURE;

@@ -59,6 +59,11 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	                              // an image without a file has no prior (DepthMap.cpp:941-954)
 	float paraPrior = 0.5f, sigmaPrior = 0.2f; // --n-para_prior, --sigma-prior (DensifyPointCloud.cpp:183, :162)
 	int photo2geo = 2;            // --n-photo2geo (DensifyPointCloud.cpp:175): first outer iteration that blends the prior term
+	int planePriors = 0;          // --plane-priors 1: the priors are GENERATED on outer iteration n - 2 from planes fitted inside the pixels labelled 255 of
+	                              // seman/<stem>.quad.pgm|ppm (hcmvs_generate_plane_prior_device); an image without a label file has none
+	std::string exportPriors;     // --export-priors <dir>: every generated prior as <dir>/depth%04u.prior.dmap, the raw 'DR' form --depth-priors reads
+	float ransacProbability = 0.01f, ransacEpsilon = 2.f, ransacMinPoints = 80.f; // --ransac-probability, --ransac-epsilon (eps = spacing x this),
+	                              // --ransac-min-points (a plane has at least 1 / this of the fitting set): the parameters of the plane detection
 	int device = 0, batch = 32;   // reference images per launch: 32 is the measured optimum (profiles/r02_knobs.txt); lowered when HBM is short
 	std::vector<int> devices;     // --devices 0,1,...: one context + host thread per entry; reference images sharded over them by their position in
 	                              // the fusion order (k mod N); post-filters and fusion on the first (an ordinal may repeat: two contexts on one GPU)
@@ -85,8 +90,8 @@ static const char* const kKnownOptions[] = {
 	// this driver's own
 	"--min-views-trust-point", "--fuse-order", "--fuse-count", "--device", "--devices", "--batch", "--seed", "--restore-hypothesis", "--n-postfilter", "--n-postfilter-interleave", "--resume", "--n-filter"};
 
-// ... and the option that feeds the depth priors (a table of its own: kKnownOptions is the reference's table plus the driver's first set)
-static const char* const kPriorOptions[] = {"--depth-priors"};
+// ... and the options that feed or make the depth priors (a table of its own: kKnownOptions is the reference's table plus the driver's first set)
+static const char* const kPriorOptions[] = {"--depth-priors", "--plane-priors", "--export-priors"};
 
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
@@ -97,6 +102,10 @@ static const char* const kUsage =
 	"                            level; an image without a file has none), blended into every score with --n-para_prior, --sigma-prior and\n"
 	"                            --n-photo2geo; registered on outer iteration n - 2 with two extra sweeps, kept through the last.  Not together with\n"
 	"                            --n-viewspread 1 or --restore-hypothesis 1\n"
+	"       --plane-priors 0|1   generate the priors instead: on outer iteration n - 2 planes are fitted inside the pixels labelled 255 of\n"
+	"                            seman/<stem>.quad.pgm|ppm of every image that has one (--ransac-probability, --ransac-epsilon, --ransac-min-points and\n"
+	"                            --seed feed the detection) and rendered into the image's prior; from there as --depth-priors.  --export-priors <dir>\n"
+	"                            writes them as <dir>/depth%04u.prior.dmap.  Not together with --depth-priors, --n-viewspread 1 or --restore-hypothesis 1\n"
 	"       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
 	"                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 	"                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
@@ -147,6 +156,9 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	geti("--n-filter", o.nFilter);
 	getf("--n-para_prior", o.paraPrior); getf("--sigma-prior", o.sigmaPrior); geti("--n-photo2geo", o.photo2geo);
 	if (kv.count("--depth-priors")) o.depthPriors = kv["--depth-priors"];
+	geti("--plane-priors", o.planePriors);
+	if (kv.count("--export-priors")) o.exportPriors = kv["--export-priors"];
+	getf("--ransac-probability", o.ransacProbability); getf("--ransac-epsilon", o.ransacEpsilon); getf("--ransac-min-points", o.ransacMinPoints);
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -175,9 +187,21 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (o.sampleMesh != 0 || o.thFilterPointCloud < 0) return PARSE_OK; // (no densify run)
 	if (o.fusionMode < 0) { err = "SGM fusion modes are not available"; return PARSE_ERROR; }
 	if (o.nFilter < 0 || o.nFilter > 2) { err = "--n-filter expects 0 (off), 1 (adjust) or 2 (strict)"; return PARSE_ERROR; }
-	if (!o.depthPriors.empty()) { // (without the folder the three prior options are read and have nothing to act on)
-		if (o.restoreHypothesis) { err = "--depth-priors is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
-		if (o.viewspread) { err = "--depth-priors is not combined with --n-viewspread 1 (the authors run priors with --n-viewspread 0)"; return PARSE_ERROR; }
+	if (o.planePriors != 0 && o.planePriors != 1) { err = "--plane-priors expects 0 or 1"; return PARSE_ERROR; }
+	if (!o.exportPriors.empty() && !o.planePriors) { err = "--export-priors writes the priors that --plane-priors 1 generates: give both"; return PARSE_ERROR; }
+	if (o.planePriors) {
+		if (!o.depthPriors.empty()) { err = "--plane-priors 1 is not combined with --depth-priors (an image has one prior: generated or supplied)"; return PARSE_ERROR; }
+		if (o.restoreHypothesis) { err = "--plane-priors 1 is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
+		if (o.viewspread) { err = "--plane-priors 1 is not combined with --n-viewspread 1 (the authors run priors with --n-viewspread 0)"; return PARSE_ERROR; }
+		if (!(o.ransacProbability > 0.f && o.ransacProbability < 1.f)) { err = "--ransac-probability expects a value inside (0, 1)"; return PARSE_ERROR; }
+		if (!(o.ransacEpsilon > 0.f) || !(o.ransacEpsilon < INFINITY)) { err = "--ransac-epsilon expects a finite value > 0"; return PARSE_ERROR; }
+		if (!(o.ransacMinPoints > 0.f) || !(o.ransacMinPoints < INFINITY)) { err = "--ransac-min-points expects a finite value > 0"; return PARSE_ERROR; }
+		if (kv.count("--ransac-cluster") && o.verbosity > 1)
+			o.notes.push_back("--ransac-cluster is read and unused: the plane detection does not cluster a plane's inliers into connected components");
+	}
+	if (!o.depthPriors.empty() || o.planePriors) { // (without either the three prior options are read and have nothing to act on)
+		if (!o.depthPriors.empty() && o.restoreHypothesis) { err = "--depth-priors is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
+		if (!o.depthPriors.empty() && o.viewspread) { err = "--depth-priors is not combined with --n-viewspread 1 (the authors run priors with --n-viewspread 0)"; return PARSE_ERROR; }
 		if (!(o.paraPrior >= 0.f && o.paraPrior <= 1.f)) { err = "--n-para_prior expects a value in [0, 1]"; return PARSE_ERROR; }
 		if (!(o.sigmaPrior > 0.f) || !(o.sigmaPrior < INFINITY)) { err = "--sigma-prior expects a finite value > 0"; return PARSE_ERROR; }
 		if (o.photo2geo < 0) { err = "--n-photo2geo expects a value >= 0"; return PARSE_ERROR; }
@@ -473,8 +497,16 @@ inline IterPlan plan_iteration(const Options& o, int it, bool anyWork) {
 // --depth-priors, the reference's schedule (SceneDensify.cpp:983-1031): on outer iteration n - 2, after the ordinary estimate of a batch, the
 // priors of its images are registered and two extra sweeps run (indices --n-EstimationIters and + 1); they stay registered through the last
 // iteration.  With fewer than two outer iterations the priors are never used.
-inline bool prior_sweeps_after(const Options& o, int it) { return !o.depthPriors.empty() && it == o.estimationItersExternal - 2; }
-inline bool priors_never_used(const Options& o) { return !o.depthPriors.empty() && o.estimationItersExternal < 2; }
+// --plane-priors 1 follows the same schedule: the priors are generated where --depth-priors registers the ones it read.
+inline bool has_priors(const Options& o) { return !o.depthPriors.empty() || o.planePriors != 0; }
+inline bool prior_sweeps_after(const Options& o, int it) { return has_priors(o) && it == o.estimationItersExternal - 2; }
+inline bool priors_never_used(const Options& o) { return has_priors(o) && o.estimationItersExternal < 2; }
+inline std::string export_prior_path(const Options& o, uint32_t id) { return sceneio::map_path(o.exportPriors, "/depth%04u.prior.dmap", id); }
+// the parameters of the plane detection as the options give them (the rest: the library's defaults, region label 255)
+inline hcmvs_plane_prior_params plane_prior_params(const Options& o, hcmvs_plane_prior_params p) {
+	p.region_label = 255; p.probability = o.ransacProbability; p.epsilon_mul = o.ransacEpsilon; p.min_points_div = o.ransacMinPoints; p.seed = o.sampleSeed;
+	return p;
+}
 inline std::string prior_path(const Options& o, uint32_t id) { return sceneio::map_path(o.depthPriors, "/depth%04u.prior.dmap", id); }
 // --n-filter: the filter stage hands the maps of every image that has them to the saver
 inline bool stage_submits_final(const Options& o) { return o.nFilter != 0; }

@@ -199,8 +199,9 @@ int hcmvs_get_spread_stats(hcmvs_ctx* ctx, hcmvs_spread_stats* out);
  *     dd = |prior - depth| / prior,  wP = exp(-dd^2 / (2 sigma_prior^2)),  score = score * (1 - para_prior) + 2 * (1 - wP) * para_prior
  * at the pixels whose prior is finite and > 0; a view that failed (thRobust) is not blended.  The prior of view `id` is ACTIVE in an
  * estimate of `id` when one is registered, para_prior > 0 and params->it_external >= photo2geo; without an active prior every call
- * computes exactly what it computes without this section.  The library consumes the map; making one (planes, a coarser level, a
- * rendering) is the caller's.  DESIGN.md section 5, D11 pins the association and the validity rule. */
+ * computes exactly what it computes without this section.  The library consumes the map; hcmvs_generate_plane_prior_device (below)
+ * makes one from planes fitted to a labelled region, any other kind (a coarser level, a rendering) is the caller's.  DESIGN.md
+ * section 5, D11 pins the association and the validity rule. */
 typedef struct {
 	float para_prior;   /* --n-para_prior: weight of the term, 0 .. 1 */
 	float sigma_prior;  /* --sigma-prior: width of the relative depth difference, > 0 */
@@ -234,6 +235,75 @@ typedef struct {
 	uint64_t pixels_prior; /* estimated pixels of the items with an active prior whose prior is usable (finite and > 0) */
 } hcmvs_prior_stats;
 int hcmvs_get_prior_stats(hcmvs_ctx* ctx, hcmvs_prior_stats* out);
+
+/* ---- plane priors (DepthMapsData::GenerateDepthPrior, SceneDensify.cpp:1550-1950, restated without CGAL) ------------------------------
+ * Planes are fitted inside a labelled region of a half-finished depth map and rendered into a prior depth map, which pulls the
+ * textureless pixels of the region onto them (the section above consumes it).  The rule -- samples, planarity, spacing and outliers,
+ * plane detection in rounds of 256 counter-based candidates, plane frames and image quads, rendering -- is DESIGN.md section 5, D13;
+ * all of it runs on the device in the camera frame of the view.  The result depends on (maps, region, params) only: parity with
+ * CGAL's randomised Efficient RANSAC is unpinned. */
+#define HCMVS_MAX_PRIOR_PLANES 64
+typedef struct {
+	int32_t region_label;   /* 255: the label a caller hands to hcmvs_set_prior_region (the generate call reads the registered region) */
+	float conf_max;         /* 0.18 (SceneDensify.cpp:1625): a sample's score lies below it */
+	float planarity_min;    /* 0.3: (l1 - l0) / l2 of a sample's neighbourhood is at least this */
+	int32_t n_neighbors;    /* 10, 3 .. 31: neighbourhood of the planarity and of the spacing */
+	float probability;      /* 0.01, --ransac-probability: chance of overlooking a plane, inside (0, 1) */
+	float min_points_div;   /* 80, --ransac-min-points: a plane has at least n0 / min_points_div samples (and 3) */
+	float epsilon_mul;      /* 2, --ransac-epsilon: eps = average spacing * epsilon_mul */
+	float normal_threshold; /* 0.25: |plane normal . sample normal| is at least this */
+	int32_t max_rounds;     /* 256, 1 .. 4096: rounds of 256 candidates at the most */
+	uint64_t seed;          /* of the counter-based candidate stream */
+} hcmvs_plane_prior_params;
+void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p);
+/* The region of view `id` in which planes are fitted: the pixels whose label equals region_label, from a 16-bit label image of any
+ * size on the HOST, resampled with cv::resize INTER_NEAREST as the ignore mask is.  labels == NULL removes the region; registering the
+ * view again or hcmvs_release_view drops it.  A view made by hcmvs_rescale_view is refused.  Blocking. */
+int hcmvs_set_prior_region(hcmvs_ctx* ctx, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, int32_t region_label);
+/* region: w*h bytes, 1 = inside (all 0 without a region) */
+int hcmvs_get_prior_region(hcmvs_ctx* ctx, uint32_t id, uint8_t* region);
+typedef struct {
+	float normal[3];       /* unit normal, camera frame, as the candidate had it */
+	uint32_t n_inliers;    /* cnt_0: the samples assigned to the plane */
+	double centre[3];      /* centroid of the inliers, camera frame */
+	double quad[8];        /* image quad x0 y0 .. x3 y3: lower-left, lower-right, upper-right, upper-left of the plane frame */
+	int32_t box_fallback;  /* 1: a corner fell behind the camera, quad = the box of the inliers' pixels widened by half a pixel */
+	int32_t reserved;
+} hcmvs_prior_plane;
+typedef struct {
+	uint64_t region_pixels, samples, planar_samples, fitting_samples; /* the stages S1 .. S3 */
+	double avg_spacing_all, avg_spacing; /* the average before the outliers went, and of the fitting set */
+	float eps;
+	int32_t min_points;
+	int32_t rounds, planes;
+	uint64_t candidates_valid; /* over all rounds */
+	uint64_t prior_pixels;     /* pixels of the prior map that are > 0 */
+	float ms_device;           /* first launch to the last, host round trips included */
+	float ms_gather, ms_search, ms_rounds, ms_render; /* host clock between the points where the call waits for the stream: S1; S2 + S3
+	                                                     (three neighbour searches); S4; S5 + S6 */
+	uint64_t device_bytes;     /* scratch of the call */
+} hcmvs_plane_prior_stats;
+/* The prior of view `id` from its maps in DEVICE memory in the state an estimate leaves between outer iterations (d_conf = the score,
+ * lower is better), which are read and never written: every pixel of d_prior (w*h floats) is written, 0 outside the region and where
+ * no plane applies; d_prior_normal (w*h*3 floats, or NULL) gets the plane normal turned towards the camera, 0 where the prior is 0.
+ * planes (HCMVS_MAX_PRIOR_PLANES entries, or NULL) and stats (or NULL) are HOST buffers; entries past stats->planes are zeroed.  Runs
+ * on the context's stream and is blocking (the plane table comes back).  The output feeds hcmvs_set_depth_prior_device unchanged.
+ * A pixel whose point ray * depth is not finite in float32 is not a sample.
+ * Success with an all-zero prior and no plane: no region registered, no region pixel, fewer than n_neighbors + 1 samples at any stage.
+ * HCMVS_ERR_INVALID before anything reaches the device: a null pointer, an unknown view, a K whose last row is not 0 0 1 or that
+ * cannot be inverted, probability outside (0, 1), min_points_div / epsilon_mul not > 0 and finite, n_neighbors outside 3 .. 31,
+ * max_rounds outside 1 .. 4096, an output overlapping an input map or the other output. */
+int hcmvs_generate_plane_prior_device(hcmvs_ctx* ctx, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf,
+                                      const hcmvs_plane_prior_params* params, float* d_prior, float* d_prior_normal,
+                                      hcmvs_prior_plane* planes, hcmvs_plane_prior_stats* stats);
+/* TEST SURFACE.  The decisions of the last hcmvs_generate_plane_prior_device of the context, into HOST buffers (each may be NULL); they are
+ * read out of that call's scratch, which the context keeps until the next call, its end, or a shortage of device memory (the trace is then
+ * gone: HCMVS_ERR_INVALID for stage / assignment):
+ * stage (w*h bytes of the view of that call: 0 outside the region, 1 region, 2 sample, 3 planar, 4 in the fitting set), assignment (w*h
+ * int32: the plane of a fitting-set sample, -1 otherwise), rounds (6 int32 per round run: winning candidate or -1, its cnt_0 .. cnt_3,
+ * the valid candidates of the round; at most rounds_capacity rounds are written), *n_rounds = the rounds run. */
+int hcmvs_get_plane_prior_trace(hcmvs_ctx* ctx, uint8_t* stage, int32_t* assignment, int32_t* rounds, int32_t rounds_capacity,
+                                int32_t* n_rounds);
 
 /* SceneDensify.cpp:783-808: splat n_points sparse world points (xyz f32) seen by view `id` as 5x5 blocks
  * into host maps depth (w*h) / normal (w*h*3); returns the depth range (min*0.9, max*1.1). Host-side helper. */
