@@ -106,7 +106,8 @@ class PriorStats(C.Structure):
 
 class PlanePriorParams(C.Structure):
     _fields_ = [("region_label", C.c_int32), ("conf_max", C.c_float), ("planarity_min", C.c_float), ("n_neighbors", C.c_int32), ("probability", C.c_float),
-                ("min_points_div", C.c_float), ("epsilon_mul", C.c_float), ("normal_threshold", C.c_float), ("max_rounds", C.c_int32), ("seed", C.c_uint64)]
+                ("min_points_div", C.c_float), ("epsilon_mul", C.c_float), ("normal_threshold", C.c_float), ("max_rounds", C.c_int32), ("seed", C.c_uint64),
+                ("cluster_mul", C.c_float)]
 
 
 class PriorPlane(C.Structure):
@@ -118,7 +119,8 @@ class PlanePriorStats(C.Structure):
     _fields_ = [("region_pixels", C.c_uint64), ("samples", C.c_uint64), ("planar_samples", C.c_uint64), ("fitting_samples", C.c_uint64),
                 ("avg_spacing_all", C.c_double), ("avg_spacing", C.c_double), ("eps", C.c_float), ("min_points", C.c_int32), ("rounds", C.c_int32),
                 ("planes", C.c_int32), ("candidates_valid", C.c_uint64), ("prior_pixels", C.c_uint64), ("ms_device", C.c_float), ("ms_gather", C.c_float), ("ms_search", C.c_float),
-                ("ms_rounds", C.c_float), ("ms_render", C.c_float), ("device_bytes", C.c_uint64)]
+                ("ms_rounds", C.c_float), ("ms_render", C.c_float), ("device_bytes", C.c_uint64), ("cluster_eps", C.c_float), ("cluster_rejects", C.c_int32),
+                ("cluster_left", C.c_uint64)]
 
 
 MAX_PRIOR_PLANES = 64
@@ -154,7 +156,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_default_prior_params", "hcmvs_set_prior_params", "hcmvs_set_depth_prior", "hcmvs_set_depth_prior_device",
            "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats",
            "hcmvs_default_plane_prior_params", "hcmvs_set_prior_region", "hcmvs_get_prior_region", "hcmvs_generate_plane_prior_device",
-           "hcmvs_get_plane_prior_trace"]
+           "hcmvs_get_plane_prior_trace", "hcmvs_get_plane_prior_cluster_trace"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -329,6 +331,7 @@ def lib():
         L.hcmvs_generate_plane_prior_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.POINTER(PlanePriorParams), vp, vp, C.POINTER(PriorPlane),
                                                         C.POINTER(PlanePriorStats)]
         L.hcmvs_get_plane_prior_trace.argtypes = [vp, u8p, i32p, i32p, C.c_int32, i32p]
+        L.hcmvs_get_plane_prior_cluster_trace.argtypes = [vp, i32p, C.c_int32, i32p]
         _lib = L
     return _lib
 
@@ -353,7 +356,8 @@ def default_prior_params(**kw):
 
 
 def default_plane_prior_params(**kw):
-    """hcmvs_default_plane_prior_params: the reference's values (255, 0.18, 0.3, 10, 0.01, 80, 2, 0.25), 256 rounds, seed 1; then the overrides"""
+    """hcmvs_default_plane_prior_params: the reference's values (255, 0.18, 0.3, 10, 0.01, 80, 2, 0.25), 256 rounds, seed 1, cluster_mul 0 (a
+    plane's inliers are not clustered into connected components; > 0: the cell edge in average spacings, --ransac-cluster); then the overrides"""
     p = PlanePriorParams()
     lib().hcmvs_default_plane_prior_params(C.byref(p))
     for k, v in kw.items():
@@ -660,6 +664,16 @@ class Context:
         rounds = np.zeros((max(n.value, 1), 6), np.int32)
         self._chk(lib().hcmvs_get_plane_prior_trace(self._h, None, None, rounds.ctypes.data_as(i32p), n.value, C.byref(n)))
         return dict(stage=stage, assignment=asg, rounds=rounds[:n.value])
+
+    def plane_prior_cluster_trace(self):
+        """what the clustering (cluster_mul) decided in every round of the last generate_plane_prior_device: (n, 4) i32 -- occupied cells,
+        components, size of the largest component, accepted 0 / 1; zeros for a round without a winner, 0, 0, cnt_0, 1 with clustering off"""
+        n = C.c_int32()
+        i32p = C.POINTER(C.c_int32)
+        self._chk(lib().hcmvs_get_plane_prior_cluster_trace(self._h, None, 0, C.byref(n)))
+        rows = np.zeros((max(n.value, 1), 4), np.int32)
+        self._chk(lib().hcmvs_get_plane_prior_cluster_trace(self._h, rows.ctypes.data_as(i32p), n.value, C.byref(n)))
+        return rows[:n.value]
 
     def stats(self):
         s = Stats()

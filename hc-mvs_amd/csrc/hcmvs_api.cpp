@@ -806,6 +806,7 @@ void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p) {
 	p->region_label = 255; p->conf_max = 0.18f; p->planarity_min = 0.3f; p->n_neighbors = 10; // SceneDensify.cpp:1625, :1648-1681
 	p->probability = 0.01f; p->min_points_div = 80.f; p->epsilon_mul = 2.f;                    // DensifyPointCloud.cpp --ransac-*
 	p->normal_threshold = 0.25f; p->max_rounds = 256; p->seed = 1;
+	p->cluster_mul = 0.f; // clustering off: what the call computed before it had the field
 }
 int hcmvs_set_prior_region(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, int32_t region_label) {
 	if (!c) return HCMVS_ERR_INVALID;
@@ -890,6 +891,15 @@ int hcmvs_get_plane_prior_trace(hcmvs_ctx* c, uint8_t* stage, int32_t* assignmen
 		for (size_t i = 0; i < px; ++i) assignment[i] = -1;
 		for (size_t i = 0; i < t.n0; ++i) assignment[pix[i]] = asg[i];
 	}
+	return HCMVS_OK;
+}
+int hcmvs_get_plane_prior_cluster_trace(hcmvs_ctx* c, int32_t* clusters, int32_t capacity, int32_t* n_rounds) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const PriorGenTrace& t = c->priorTrace;
+	if (clusters && capacity < 0) return fail(c, HCMVS_ERR_INVALID, "get_plane_prior_cluster_trace: negative capacity");
+	const size_t nRounds = t.clusters.size() / 4;
+	if (n_rounds) *n_rounds = (int32_t)nRounds;
+	if (clusters) memcpy(clusters, t.clusters.data(), sizeof(int32_t) * 4 * std::min(nRounds, (size_t)capacity));
 	return HCMVS_OK;
 }
 

@@ -20,6 +20,7 @@ constexpr int kPriorMaxRounds = 4096;
 constexpr int kPriorSpacingShift = 40;  // a spacing is summed as round(s * 2^40), s saturated below 2^23
 constexpr int kPriorCoordShift = 32;    // a coordinate is summed as round(P * 2^32), |P| saturated below 2^30
 constexpr int kPriorAccWords = 16;      // unsigned long long words a plane reduces into (prior_kernels.hip)
+constexpr uint32_t kPriorClusterCellCap = 1u << 30; // S4c: a cell coordinate is min(floor((u - u0) / cell), this); the cells at the cap merge (degenerate)
 
 struct PriorGenArgs {
 	uintptr_t depth, normal, conf, prior, priorNormal; // device addresses as integers (the checks do not read them); priorNormal may be 0
@@ -62,6 +63,7 @@ inline std::string prior_gen_check(const PriorGenArgs& a) {
 	if (p.n_neighbors < 3 || p.n_neighbors > 31) { snprintf(buf, sizeof buf, "n_neighbors %d outside 3..31", p.n_neighbors); return buf; }
 	if (p.max_rounds < 1 || p.max_rounds > kPriorMaxRounds) { snprintf(buf, sizeof buf, "max_rounds %d outside 1..%d", p.max_rounds, kPriorMaxRounds); return buf; }
 	if (p.conf_max != p.conf_max || p.planarity_min != p.planarity_min || p.normal_threshold != p.normal_threshold) return "a threshold is NaN";
+	if (!(p.cluster_mul >= 0.f) || !std::isfinite(p.cluster_mul)) { snprintf(buf, sizeof buf, "cluster_mul %g is not a finite number >= 0", (double)p.cluster_mul); return buf; }
 	const uint64_t px = (uint64_t)a.w * a.h;
 	const struct { uintptr_t at; uint64_t bytes; const char* what; } in[3] = {{a.depth, px * 4, "depth"}, {a.normal, px * 12, "normal"}, {a.conf, px * 4, "conf"}};
 	for (const auto& m : in) {
@@ -96,6 +98,10 @@ inline int prior_gen_fail_limit(float probability, int64_t minPoints, uint64_t n
 	return (int)rounds;
 }
 inline float prior_gen_eps(double avg, float epsilonMul) { return (float)(avg * (double)epsilonMul); }
+// S4c: the cell edge of the clustering, rounded to float32 as eps is.  A cell that is not a finite number > 0 (the product underflowed, or
+// overflowed) clusters nothing: all inliers of a winner are one component
+inline float prior_gen_cluster_cell(double avg, float clusterMul) { return (float)(avg * (double)clusterMul); }
+inline bool prior_gen_cluster_cell_usable(float cell) { return cell > 0.f && std::isfinite(cell); }
 
 // a fixed-point sum that came back as two words: sum of the (signed) high parts q >> 32 and of the low parts q & 0xffffffff of the
 // addends q = round(v * 2^shift).  The mean of the n values: (double)(hi * 2^32 + lo) / ((double)n * 2^shift), the integer exact
@@ -149,7 +155,8 @@ struct PriorPlaneDev {
 };
 
 // The one device buffer of a call.  px = w * h bounds every stage (a stage never has more samples than pixels); the two sets A and B
-// take the stages in turn (samples -> A, planar -> B, fitting set -> A)
+// take the stages in turn (samples -> A, planar -> B, fitting set -> A).  The clustering of S4c adds no piece: during S4 the pieces of the
+// neighbour search (knn.keys / keys2 / idx / idx2 / sorted / pos / sort), flags / scan / scanTmp and words are idle and have the sizes it needs
 struct PriorGenLayout {
 	size_t flags = 0, scan = 0, scanTmp = 0;             // uint32 per pixel / sample: keep flags, their exclusive scan, the scan's temporary
 	size_t xyzA = 0, nrmA = 0, pixA = 0, xyzB = 0, nrmB = 0, pixB = 0; // float3, float3, int32 per sample

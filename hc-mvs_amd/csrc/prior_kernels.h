@@ -16,11 +16,13 @@ struct PriorGenTrace {
 	uint64_t n0 = 0;             // fitting-set samples whose pixel and assignment the scratch holds (0: the call ended before S4)
 	PriorGenLayout lay;
 	std::vector<int32_t> rounds; // 6 per round: winner or -1, cnt_0 .. cnt_3, valid candidates
+	std::vector<int32_t> clusters; // 4 per round (S4c): occupied cells, components, size of the largest, accepted; zeros without a winner
 };
 
 // DESIGN.md section 5, D13.  region: the view's region mask as the ignore-mask kernel writes it (u8 per pixel, 0 = INSIDE the region), or
 // null (no region).  The arguments have passed prior_gen_check.  All device pointers; planes (64 entries, or null) and st are the host's.
-// Waits for the stream several times (stage sizes, one winner per round, the plane reductions).  0 = ok, 2 = device failure (err says which)
+// Waits for the stream several times (stage sizes, one winner per round -- with clustering one more per round that has a winner --, the
+// plane reductions).  0 = ok, 2 = device failure (err says which)
 int generate_plane_prior_device(int w, int h, const double K[9], const uint8_t* region, const float* depth, const float* normal, const float* conf,
                                 const hcmvs_plane_prior_params& p, float* prior, float* priorNormal, hcmvs_prior_plane* planes, hcmvs_plane_prior_stats& st,
                                 DevBuf& scratch, PriorGenTrace& trace, hipStream_t s, std::string& err);

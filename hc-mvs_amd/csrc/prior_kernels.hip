@@ -15,6 +15,9 @@
  *     lane in registers and walks the 4 KiB candidate table, which is uniform across the wave (scalar loads): four ballots and
  *     popcounts per candidate, added by one lane into LDS counters of the workgroup, then one integer global atomic per non-zero
  *     counter and workgroup.  One workgroup ranks the counters; only the winner (a few words) travels to the host.
+ * S4c (cluster_mul > 0) the winner's inliers keep their largest connected component on a grid of cells in the plane: cell keys, a radix
+ *     sort (hipcub), the distinct cells, a union-find over them (neighbours by binary search), integer sizes, one packed maximum; the
+ *     arrays live in the scratch of the neighbour search, which is idle during S4.  A 16-byte record travels to the host.
  * S5  per-plane reductions into integer words (fixed-point coordinate sums, pixel box, then the extent in the plane's frame as ordered
  *     doubles -- min and max do not depend on the order either); the frame and the quad are the host's (prior_gen_plan.h).
  * S6  render: one thread per pixel over the plane table.
@@ -297,6 +300,169 @@ __global__ __launch_bounds__(kBlockSize) void assign_kernel(unsigned n0, const f
 	}
 }
 
+__device__ __forceinline__ unsigned long long ordered(double v) {
+	const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+	return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double from_ordered_dev(unsigned long long k) { return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k)); }
+
+// ---- S4c ----
+// The winner's inliers on a grid of cells in the plane's frame; the largest 8-connected component is the plane.  Sparse: every array is
+// bounded by the number of samples, whatever the extent of the plane in cells.  Nothing depends on the order the threads run in: the
+// origin is a minimum of ordered doubles, a component's label is the smallest index among its cells (the distinct cell keys ascending:
+// (cv, cu) lexicographically), sizes are integer sums, the pick is one packed maximum.
+// rec (unsigned long long words): 0 / 1 ordered u0 / v0; 2 the pick (size << 32 | ~label); 3 inliers; 4 components;
+// then, as int32 from word 8: occupied cells, components, size of the pick, accepted
+struct ClusterFrame { double b1[3], b2[3], cell; };
+constexpr int kClusterRecOut = 8;
+
+struct WinnerPlane { float nx, ny, nz, d; };
+__device__ __forceinline__ WinnerPlane winner_plane(const int32_t* winner) {
+	const float* f = (const float*)winner;
+	return {f[8], f[9], f[10], f[11]};
+}
+// the set assign_kernel takes
+__device__ __forceinline__ bool is_inlier(const WinnerPlane& pl, const float* xyz, const float* nrm, const int32_t* assigned, unsigned i, float normalThr, float eps) {
+	if (assigned[i] >= 0) return false;
+	const float* N = nrm + 3 * (size_t)i; const float* P = xyz + 3 * (size_t)i;
+	return fabsf(dot3(pl.nx, pl.ny, pl.nz, N[0], N[1], N[2])) >= normalThr && fabsf(dot3(pl.nx, pl.ny, pl.nz, P[0], P[1], P[2]) - pl.d) <= eps;
+}
+__device__ __forceinline__ void plane_coords(const ClusterFrame& f, const float* P, double& u, double& v) {
+	const double x = (double)P[0], y = (double)P[1], z = (double)P[2];
+	u = (x * f.b1[0] + y * f.b1[1]) + z * f.b1[2];
+	v = (x * f.b2[0] + y * f.b2[1]) + z * f.b2[2];
+}
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+	for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+	return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+	for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+	return v;
+}
+__global__ void cluster_reset_kernel(unsigned long long* rec) {
+	if (threadIdx.x < 16) rec[threadIdx.x] = threadIdx.x < 2 ? ~0ull : 0ull;
+}
+__global__ __launch_bounds__(kBlockSize) void cluster_origin_kernel(unsigned n0, const float* xyz, const float* nrm, const int32_t* assigned, const int32_t* winner, float normalThr,
+                                                                    float eps, ClusterFrame f, unsigned long long* rec) {
+	__shared__ unsigned long long sh[2];
+	if (threadIdx.x < 2) sh[threadIdx.x] = ~0ull;
+	__syncthreads();
+	const WinnerPlane pl = winner_plane(winner);
+	unsigned long long mu = ~0ull, mv = ~0ull;
+	for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += gridDim.x * blockDim.x) {
+		if (!is_inlier(pl, xyz, nrm, assigned, i, normalThr, eps)) continue;
+		double u, v;
+		plane_coords(f, xyz + 3 * (size_t)i, u, v);
+		const unsigned long long ou = ordered(u), ov = ordered(v);
+		mu = ou < mu ? ou : mu; mv = ov < mv ? ov : mv;
+	}
+	mu = wave_min(mu); mv = wave_min(mv);
+	if ((threadIdx.x & 63) == 0) { if (mu != ~0ull) atomicMin(&sh[0], mu); if (mv != ~0ull) atomicMin(&sh[1], mv); }
+	__syncthreads();
+	if (threadIdx.x < 2 && sh[threadIdx.x] != ~0ull) atomicMin(&rec[threadIdx.x], sh[threadIdx.x]);
+}
+// keys[i] = cv << 32 | cu of an inlier, all ones otherwise; idx[i] = i
+__global__ __launch_bounds__(kBlockSize) void cluster_keys_kernel(unsigned n0, const float* xyz, const float* nrm, const int32_t* assigned, const int32_t* winner, float normalThr,
+                                                                  float eps, ClusterFrame f, const unsigned long long* rec, unsigned long long* keys, uint32_t* idx) {
+	const WinnerPlane pl = winner_plane(winner);
+	const double u0 = from_ordered_dev(rec[0]), v0 = from_ordered_dev(rec[1]);
+	for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += gridDim.x * blockDim.x) {
+		unsigned long long key = ~0ull;
+		if (is_inlier(pl, xyz, nrm, assigned, i, normalThr, eps)) {
+			double u, v;
+			plane_coords(f, xyz + 3 * (size_t)i, u, v);
+			const double cu = fmin(floor((u - u0) / f.cell), (double)kPriorClusterCellCap), cv = fmin(floor((v - v0) / f.cell), (double)kPriorClusterCellCap); // >= 0: u0, v0 are minima
+			key = (unsigned long long)cv << 32 | (unsigned long long)cu;
+		}
+		keys[i] = key; idx[i] = i;
+	}
+}
+// over the sorted keys: marks[j] = entry j is the first of its cell; rec[3] = the inliers (they sort before the others)
+__global__ __launch_bounds__(kBlockSize) void cluster_marks_kernel(unsigned n0, const unsigned long long* keys, uint32_t* marks, unsigned long long* rec) {
+	for (unsigned j = blockIdx.x * blockDim.x + threadIdx.x; j < n0; j += gridDim.x * blockDim.x) {
+		const unsigned long long k = keys[j];
+		const bool in = k != ~0ull;
+		marks[j] = in && (j == 0 || keys[j - 1] != k) ? 1u : 0u;
+		if (in && (j + 1 == n0 || keys[j + 1] == ~0ull)) rec[3] = (unsigned long long)j + 1ull;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) marks[n0] = 0;
+}
+// the distinct cells: key, first entry, a union-find node of its own, an empty size
+__global__ __launch_bounds__(kBlockSize) void cluster_cells_kernel(unsigned n0, const unsigned long long* keys, const uint32_t* marks, const uint32_t* scan, unsigned long long* cells,
+                                                                   uint32_t* start, uint32_t* parent, uint32_t* sizes) {
+	for (unsigned j = blockIdx.x * blockDim.x + threadIdx.x; j < n0; j += gridDim.x * blockDim.x) {
+		if (!marks[j]) continue;
+		const uint32_t d = scan[j];
+		cells[d] = keys[j]; start[d] = j; parent[d] = d; sizes[d] = 0;
+	}
+}
+// Union-find over the cells while other workgroups hook: a parent only ever decreases, so a value read late is still an ancestor; the
+// reads go to the device's coherent level (another XCD's hook is seen), and a hook is a compare-and-swap on a node that is its own parent
+__device__ __forceinline__ uint32_t uf_root(uint32_t* parent, uint32_t x) {
+	for (;;) {
+		const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (p == x) return x;
+		x = p;
+	}
+}
+__device__ __forceinline__ void uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+	for (;;) {
+		a = uf_root(parent, a); b = uf_root(parent, b);
+		if (a == b) return;
+		if (a < b) { const uint32_t t = a; a = b; b = t; } // the larger root goes under the smaller
+		const uint32_t old = atomicCAS(&parent[a], a, b);
+		if (old == a) return;
+		a = old; // someone hooked a first: go on from where it points (strictly smaller: the loop ends)
+	}
+}
+// every cell unites with its neighbours that come later in key order -- (cv, cu + 1) is the next cell if it exists, (cv + 1, cu - 1 .. cu + 1)
+// are contiguous: one binary search -- which covers all 8 directions
+__global__ __launch_bounds__(kBlockSize) void cluster_union_kernel(unsigned n0, const uint32_t* scan, const unsigned long long* cells, uint32_t* parent) {
+	const uint32_t m = scan[n0];
+	for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < m; d += gridDim.x * blockDim.x) {
+		const unsigned long long key = cells[d], cu = key & 0xffffffffull, row = (key >> 32) + 1ull;
+		if (d + 1 < m && cells[d + 1] == key + 1ull) uf_unite(parent, d, d + 1); // (cu <= 2^30: no carry into cv)
+		const unsigned long long first = row << 32 | (cu > 0 ? cu - 1ull : 0ull), last = row << 32 | (cu + 1ull);
+		for (unsigned long long e = lower_bound(cells, m, first); e < m && cells[e] <= last; ++e) uf_unite(parent, d, (uint32_t)e);
+	}
+}
+// parent[d] = the root; the samples of the cell are added to the root's size
+__global__ __launch_bounds__(kBlockSize) void cluster_sizes_kernel(unsigned n0, const uint32_t* scan, const uint32_t* start, const unsigned long long* rec, uint32_t* parent,
+                                                                   uint32_t* sizes) {
+	const uint32_t m = scan[n0], nIn = (uint32_t)rec[3];
+	for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < m; d += gridDim.x * blockDim.x) {
+		const uint32_t r = uf_root(parent, d);
+		parent[d] = r; // (whoever walks through d meets an ancestor either way)
+		atomicAdd(&sizes[r], (d + 1 < m ? start[d + 1] : nIn) - start[d]);
+	}
+}
+__global__ __launch_bounds__(kBlockSize) void cluster_pick_kernel(unsigned n0, const uint32_t* scan, const uint32_t* parent, const uint32_t* sizes, unsigned long long* rec) {
+	const uint32_t m = scan[n0];
+	unsigned long long best = 0, roots = 0;
+	for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < m; d += gridDim.x * blockDim.x) {
+		if (parent[d] != d) continue;
+		const unsigned long long cand = (unsigned long long)sizes[d] << 32 | (unsigned long long)(~d); // equal sizes: the smallest label
+		best = cand > best ? cand : best; ++roots;
+	}
+	best = wave_max(best); roots = wave_sum(roots);
+	if ((threadIdx.x & 63) == 0 && roots) { atomicMax(&rec[2], best); atomicAdd(&rec[4], roots); }
+}
+// the samples of the picked component get the plane when it is large enough; the record of the round
+__global__ __launch_bounds__(kBlockSize) void cluster_assign_kernel(unsigned n0, const uint32_t* marks, const uint32_t* scan, const uint32_t* idx, const uint32_t* parent,
+                                                                    unsigned long long minPoints, int32_t plane, unsigned long long* rec, int32_t* assigned) {
+	const unsigned long long pick = rec[2], size = pick >> 32;
+	const uint32_t label = ~(uint32_t)pick, nIn = (uint32_t)rec[3];
+	const bool accepted = size >= minPoints;
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		int32_t* out = (int32_t*)(rec + kClusterRecOut);
+		out[0] = (int32_t)scan[n0]; out[1] = (int32_t)rec[4]; out[2] = (int32_t)size; out[3] = accepted ? 1 : 0;
+	}
+	if (!accepted) return;
+	for (unsigned j = blockIdx.x * blockDim.x + threadIdx.x; j < nIn; j += gridDim.x * blockDim.x)
+		if (parent[scan[j] + marks[j] - 1u] == label) assigned[idx[j]] = plane;
+}
+
 // ---- S5 ----
 // words of a plane: 0..5 hi / lo of the x, y, z sums of round(P * 2^32); 6 count; 7 / 8 min / max pixel x; 9 / 10 min / max pixel y;
 // 11 / 12 min / max u; 13 / 14 min / max v (ordered doubles)
@@ -305,10 +471,6 @@ __global__ void init_acc_kernel(unsigned long long* acc) {
 	if (t >= HCMVS_MAX_PRIOR_PLANES * kPriorAccWords) return;
 	const int wd = t % kPriorAccWords;
 	acc[t] = (wd == 7 || wd == 9 || wd == 11 || wd == 13) ? ~0ull : 0ull;
-}
-__device__ __forceinline__ unsigned long long ordered(double v) {
-	const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-	return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 __global__ __launch_bounds__(kBlockSize) void plane_sums_kernel(unsigned n0, int w, const float* xyz, const int32_t* pix, const int32_t* assigned, unsigned long long* acc) {
 	__shared__ unsigned long long sh[HCMVS_MAX_PRIOR_PLANES * kPriorAccWords];
@@ -541,25 +703,67 @@ int generate_plane_prior_device(int w, int h, const double K[9], const uint8_t* 
 	std::vector<Found> found;
 	int64_t unassigned = n0;
 	int fails = 0, rounds = 0;
+	// S4c: with a usable cell the winner's inliers are clustered before anything is assigned (one more wait per round that has a winner);
+	// otherwise the round is what it was, assign_kernel behind the winner without a wait in between
+	const bool clustering = p.cluster_mul > 0.f;
+	const float cellF = clustering ? prior_gen_cluster_cell(avg, p.cluster_mul) : 0.f;
+	const bool chain = clustering && prior_gen_cluster_cell_usable(cellF);
+	st.cluster_eps = cellF;
+	// the pieces of the neighbour search and of the scans are idle during S4, and sized for px >= n0 entries
+	unsigned long long *cKeys = (unsigned long long*)(b + lay.knn.keys), *cKeys2 = (unsigned long long*)(b + lay.knn.keys2), *cCells = (unsigned long long*)(b + lay.knn.sorted);
+	uint32_t *cIdx = (uint32_t*)(b + lay.knn.idx), *cIdx2 = (uint32_t*)(b + lay.knn.idx2), *cStart = (uint32_t*)(b + lay.knn.pos);
+	uint32_t *cParent = (uint32_t*)(b + lay.knn.sorted + px * 8), *cSizes = (uint32_t*)(b + lay.knn.sorted + px * 12);
+	auto cluster_round = [&](const float n[3], int32_t plane, int32_t row[4]) {
+		ClusterFrame fr;
+		prior_gen_frame(n, fr.b1, fr.b2);
+		fr.cell = (double)cellF;
+		const dim3 grid(blocks_for(n0, 2048)), block(kBlockSize);
+		hipLaunchKernelGGL(cluster_reset_kernel, dim3(1), dim3(64), 0, s, words);
+		hipLaunchKernelGGL(cluster_origin_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, words);
+		hipLaunchKernelGGL(cluster_keys_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, words, cKeys, cIdx);
+		size_t sortBytes = lay.knn.sortBytes, tmp = scanBytes;
+		if (hipcub::DeviceRadixSort::SortPairs(b + lay.knn.sort, sortBytes, cKeys, cKeys2, cIdx, cIdx2, (int)n0, 0, 64, s) != hipSuccess) return false;
+		hipLaunchKernelGGL(cluster_marks_kernel, grid, block, 0, s, n0, cKeys2, flags, words);
+		if (hipcub::DeviceScan::ExclusiveSum(b + lay.scanTmp, tmp, flags, scan, (int)(n0 + 1), s) != hipSuccess) return false;
+		hipLaunchKernelGGL(cluster_cells_kernel, grid, block, 0, s, n0, cKeys2, flags, scan, cCells, cStart, cParent, cSizes);
+		hipLaunchKernelGGL(cluster_union_kernel, grid, block, 0, s, n0, scan, cCells, cParent);
+		hipLaunchKernelGGL(cluster_sizes_kernel, grid, block, 0, s, n0, scan, cStart, words, cParent, cSizes);
+		hipLaunchKernelGGL(cluster_pick_kernel, grid, block, 0, s, n0, scan, cParent, cSizes, words);
+		hipLaunchKernelGGL(cluster_assign_kernel, grid, block, 0, s, n0, flags, scan, cIdx2, cParent, (unsigned long long)minPoints, plane, words, assigned);
+		if (hipGetLastError() != hipSuccess) return false;
+		return hipMemcpyAsync(row, words + kClusterRecOut, 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+	};
 	while (unassigned >= minPoints && (int)found.size() < HCMVS_MAX_PRIOR_PLANES && rounds < p.max_rounds && fails < failLimit) {
 		hipLaunchKernelGGL(candidate_kernel, dim3(1), dim3(kPriorCandidates), 0, s, (unsigned)rounds, (unsigned long long)p.seed, n0, w, h, dLevels, nLevels, xyzA, nrmA, pixA,
 		                   sampleAt, assigned, p.normal_threshold, cand, counts);
 		hipLaunchKernelGGL(score_kernel, dim3(blocks_for(n0, kScoreMaxBlocks)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, assigned, cand, p.normal_threshold, eps, counts);
 		hipLaunchKernelGGL(winner_kernel, dim3(1), dim3(kPriorCandidates), 0, s, cand, counts, (unsigned long long)minPoints, winner);
-		hipLaunchKernelGGL(assign_kernel, dim3(blocks_for(n0, 2048)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, winner, p.normal_threshold, eps, (int32_t)found.size(), assigned);
+		if (!chain) hipLaunchKernelGGL(assign_kernel, dim3(blocks_for(n0, 2048)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, winner, p.normal_threshold, eps, (int32_t)found.size(), assigned);
 		int32_t hwin[12];
 		if (hipMemcpyAsync(hwin, winner, sizeof hwin, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("a round failed");
 		for (int q = 0; q < 6; ++q) trace.rounds.push_back(hwin[q]);
 		st.candidates_valid += (uint64_t)hwin[5];
 		++rounds;
+		int32_t row[4] = {0, 0, 0, 0}; // occupied cells, components, the largest size, accepted
 		if (hwin[0] >= 0) {
+			row[1] = clustering ? 1 : 0; row[2] = hwin[1]; row[3] = 1; // unclustered: all inliers are the plane
+			float wn[3];
+			memcpy(wn, hwin + 8, 12);
+			if (chain && !cluster_round(wn, (int32_t)found.size(), row)) return fail("clustering a round's winner failed");
+		}
+		for (int q = 0; q < 4; ++q) trace.clusters.push_back(row[q]);
+		if (row[3]) {
 			Found f;
 			memcpy(f.n, hwin + 8, 12);
-			f.cnt0 = (uint32_t)hwin[1];
+			f.cnt0 = (uint32_t)row[2];
 			found.push_back(f);
-			unassigned -= hwin[1];
+			unassigned -= row[2];
+			st.cluster_left += (uint64_t)(hwin[1] - row[2]);
 			fails = 0;
-		} else ++fails;
+		} else {
+			if (hwin[0] >= 0) ++st.cluster_rejects;
+			++fails;
+		}
 	}
 	st.rounds = rounds; st.planes = (int32_t)found.size();
 	lap(st.ms_rounds);

@@ -17,7 +17,8 @@
  * gates the fork's post-filters (RemoveSmallSegments + GapInterpolation) as in the reference; --n-viewspread 1 lets every pixel also try
  * the estimates of its source views' own maps from outer iteration 1 on (DepthMap.cpp:1504-1608; default 0 here, 1 in the reference, so
  * that existing command lines keep their results; one device); --plane-priors 1 generates depth priors from planes fitted inside the
- * label 255 of seman/<stem>.quad.pgm|ppm on outer iteration n - 2 (--export-priors <dir> writes them);
+ * label 255 of seman/<stem>.quad.pgm|ppm on outer iteration n - 2 (--export-priors <dir> writes them; --plane-clusters 1 keeps the largest
+ * connected component of a plane's inliers, on cells of --ransac-cluster average spacings);
  * optical flow, --use-semantic and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
  *
  * How the run is laid out in time (the reference overlaps image k + 1's InitViews with image k's estimate, SceneDensify.cpp:3699-3703;
@@ -596,6 +597,9 @@ bool generate_plane_prior(Run& r, hcmvs_ctx* dctx, ImageData& im, const hcmvs_ba
 	if (r.o.verbosity > 2)
 		printf("Plane prior of image %3u: %d planes from %llu samples (%llu in the fitting set), %llu prior pixels, %.1f ms\n", im.id, st.planes,
 		       (unsigned long long)st.samples, (unsigned long long)st.fitting_samples, (unsigned long long)st.prior_pixels, st.ms_device);
+	if (r.o.verbosity > 1 && pp.cluster_mul > 0.f)
+		printf("Plane clusters of image %3u: %d planes, %d rounds rejected, %llu inliers left (cell %g)\n", im.id, st.planes, st.cluster_rejects,
+		       (unsigned long long)st.cluster_left, (double)st.cluster_eps);
 	if (!r.o.exportPriors.empty()) {
 		DmapImage hd = im.file_header();
 		if (!save_dmap(export_prior_path(r.o, im.id), hd, im.prior.data(), nullptr, nullptr)) { err = "can not write '" + export_prior_path(r.o, im.id) + "'"; return false; }
@@ -1092,6 +1096,7 @@ bool set_prior_regions(Run& r) {
 	if (o.verbosity > 1)
 		printf("Plane priors: %zu of %zu images to estimate have a label image; probability %g, epsilon %g, min-points %g, seed %llu\n", nRegions, r.work.size(),
 		       (double)o.ransacProbability, (double)o.ransacEpsilon, (double)o.ransacMinPoints, o.sampleSeed);
+	if (o.verbosity > 1 && o.planeClusters) printf("Plane clusters: a plane keeps the largest connected component of its inliers, cells of %g average spacings\n", (double)o.ransacCluster);
 	return true;
 }
 // --depth-priors <folder>: <folder>/depth%04u.prior.dmap per image that is estimated, a raw 'DR' depth map of the image's size at the run's

@@ -64,6 +64,9 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	std::string exportPriors;     // --export-priors <dir>: every generated prior as <dir>/depth%04u.prior.dmap, the raw 'DR' form --depth-priors reads
 	float ransacProbability = 0.01f, ransacEpsilon = 2.f, ransacMinPoints = 80.f; // --ransac-probability, --ransac-epsilon (eps = spacing x this),
 	                              // --ransac-min-points (a plane has at least 1 / this of the fitting set): the parameters of the plane detection
+	int planeClusters = 0;        // --plane-clusters 1 (with --plane-priors 1): a plane keeps the largest connected component of its inliers, on cells of
+	                              // --ransac-cluster average spacings; 0 keeps the results of command lines written before it
+	float ransacCluster = 10.f;   // --ransac-cluster (the reference's default; the authors run 7): read and unused without --plane-clusters 1
 	int device = 0, batch = 32;   // reference images per launch: 32 is the measured optimum (profiles/r02_knobs.txt); lowered when HBM is short
 	std::vector<int> devices;     // --devices 0,1,...: one context + host thread per entry; reference images sharded over them by their position in
 	                              // the fusion order (k mod N); post-filters and fusion on the first (an ordinal may repeat: two contexts on one GPU)
@@ -92,6 +95,8 @@ static const char* const kKnownOptions[] = {
 
 // ... and the options that feed or make the depth priors (a table of its own: kKnownOptions is the reference's table plus the driver's first set)
 static const char* const kPriorOptions[] = {"--depth-priors", "--plane-priors", "--export-priors"};
+// ... and the switch of the inlier clustering of the generated priors (a third table: the two above are pinned as they are)
+static const char* const kPlaneClusterOptions[] = {"--plane-clusters"};
 
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
@@ -106,6 +111,9 @@ static const char* const kUsage =
 	"                            seman/<stem>.quad.pgm|ppm of every image that has one (--ransac-probability, --ransac-epsilon, --ransac-min-points and\n"
 	"                            --seed feed the detection) and rendered into the image's prior; from there as --depth-priors.  --export-priors <dir>\n"
 	"                            writes them as <dir>/depth%04u.prior.dmap.  Not together with --depth-priors, --n-viewspread 1 or --restore-hypothesis 1\n"
+	"       --plane-clusters 0|1 with --plane-priors 1: a plane keeps only the largest connected component of its inliers, on a grid of cells of\n"
+	"                            --ransac-cluster average spacings (default 10) in the plane, so that two coplanar surfaces with something else between\n"
+	"                            them become two planes (default 0: --ransac-cluster is read and unused, the results of earlier command lines)\n"
 	"       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
 	"                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 	"                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
@@ -131,6 +139,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		bool known = false;
 		for (const char* k : kKnownOptions) known = known || a == k;
 		for (const char* k : kPriorOptions) known = known || a == k;
+		for (const char* k : kPlaneClusterOptions) known = known || a == k;
 		if (!known) { err = "unrecognised option '" + a + "'"; return PARSE_ERROR; }
 		if (!haveVal) { // the value is the next argument, whatever it starts with (negative numbers are values)
 			if (i + 1 >= argc) { err = "the required argument for option '" + a + "' is missing"; return PARSE_ERROR; }
@@ -159,6 +168,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	geti("--plane-priors", o.planePriors);
 	if (kv.count("--export-priors")) o.exportPriors = kv["--export-priors"];
 	getf("--ransac-probability", o.ransacProbability); getf("--ransac-epsilon", o.ransacEpsilon); getf("--ransac-min-points", o.ransacMinPoints);
+	geti("--plane-clusters", o.planeClusters); getf("--ransac-cluster", o.ransacCluster);
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -189,6 +199,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (o.nFilter < 0 || o.nFilter > 2) { err = "--n-filter expects 0 (off), 1 (adjust) or 2 (strict)"; return PARSE_ERROR; }
 	if (o.planePriors != 0 && o.planePriors != 1) { err = "--plane-priors expects 0 or 1"; return PARSE_ERROR; }
 	if (!o.exportPriors.empty() && !o.planePriors) { err = "--export-priors writes the priors that --plane-priors 1 generates: give both"; return PARSE_ERROR; }
+	if (o.planeClusters != 0 && o.planeClusters != 1) { err = "--plane-clusters expects 0 or 1"; return PARSE_ERROR; }
+	if (o.planeClusters && !o.planePriors) { err = "--plane-clusters 1 clusters the inliers of the planes that --plane-priors 1 fits: give both"; return PARSE_ERROR; }
 	if (o.planePriors) {
 		if (!o.depthPriors.empty()) { err = "--plane-priors 1 is not combined with --depth-priors (an image has one prior: generated or supplied)"; return PARSE_ERROR; }
 		if (o.restoreHypothesis) { err = "--plane-priors 1 is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
@@ -196,8 +208,9 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		if (!(o.ransacProbability > 0.f && o.ransacProbability < 1.f)) { err = "--ransac-probability expects a value inside (0, 1)"; return PARSE_ERROR; }
 		if (!(o.ransacEpsilon > 0.f) || !(o.ransacEpsilon < INFINITY)) { err = "--ransac-epsilon expects a finite value > 0"; return PARSE_ERROR; }
 		if (!(o.ransacMinPoints > 0.f) || !(o.ransacMinPoints < INFINITY)) { err = "--ransac-min-points expects a finite value > 0"; return PARSE_ERROR; }
-		if (kv.count("--ransac-cluster") && o.verbosity > 1)
-			o.notes.push_back("--ransac-cluster is read and unused: the plane detection does not cluster a plane's inliers into connected components");
+		if (o.planeClusters && (!(o.ransacCluster > 0.f) || !(o.ransacCluster < INFINITY))) { err = "--ransac-cluster expects a finite value > 0 (with --plane-clusters 1)"; return PARSE_ERROR; }
+		if (!o.planeClusters && kv.count("--ransac-cluster") && o.verbosity > 1)
+			o.notes.push_back("--ransac-cluster is read and unused: the plane detection does not cluster a plane's inliers into connected components (--plane-clusters 1 does)");
 	}
 	if (!o.depthPriors.empty() || o.planePriors) { // (without either the three prior options are read and have nothing to act on)
 		if (!o.depthPriors.empty() && o.restoreHypothesis) { err = "--depth-priors is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
@@ -505,6 +518,7 @@ inline std::string export_prior_path(const Options& o, uint32_t id) { return sce
 // the parameters of the plane detection as the options give them (the rest: the library's defaults, region label 255)
 inline hcmvs_plane_prior_params plane_prior_params(const Options& o, hcmvs_plane_prior_params p) {
 	p.region_label = 255; p.probability = o.ransacProbability; p.epsilon_mul = o.ransacEpsilon; p.min_points_div = o.ransacMinPoints; p.seed = o.sampleSeed;
+	p.cluster_mul = o.planePriors && o.planeClusters ? o.ransacCluster : 0.f; // --plane-clusters 1: --ransac-cluster is the cell edge in average spacings
 	return p;
 }
 inline std::string prior_path(const Options& o, uint32_t id) { return sceneio::map_path(o.depthPriors, "/depth%04u.prior.dmap", id); }

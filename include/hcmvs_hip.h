@@ -239,7 +239,8 @@ int hcmvs_get_prior_stats(hcmvs_ctx* ctx, hcmvs_prior_stats* out);
 /* ---- plane priors (DepthMapsData::GenerateDepthPrior, SceneDensify.cpp:1550-1950, restated without CGAL) ------------------------------
  * Planes are fitted inside a labelled region of a half-finished depth map and rendered into a prior depth map, which pulls the
  * textureless pixels of the region onto them (the section above consumes it).  The rule -- samples, planarity, spacing and outliers,
- * plane detection in rounds of 256 counter-based candidates, plane frames and image quads, rendering -- is DESIGN.md section 5, D13;
+ * plane detection in rounds of 256 counter-based candidates, optionally the largest connected component of the winner's inliers
+ * (cluster_mul), plane frames and image quads, rendering -- is DESIGN.md section 5, D13;
  * all of it runs on the device in the camera frame of the view.  The result depends on (maps, region, params) only: parity with
  * CGAL's randomised Efficient RANSAC is unpinned. */
 #define HCMVS_MAX_PRIOR_PLANES 64
@@ -254,6 +255,8 @@ typedef struct {
 	float normal_threshold; /* 0.25: |plane normal . sample normal| is at least this */
 	int32_t max_rounds;     /* 256, 1 .. 4096: rounds of 256 candidates at the most */
 	uint64_t seed;          /* of the counter-based candidate stream */
+	float cluster_mul;      /* 0 (off), --ransac-cluster: a plane keeps the largest connected component of its inliers on a grid of cells of
+	                           average spacing * cluster_mul in the plane; finite and >= 0 */
 } hcmvs_plane_prior_params;
 void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p);
 /* The region of view `id` in which planes are fitted: the pixels whose label equals region_label, from a 16-bit label image of any
@@ -264,7 +267,7 @@ int hcmvs_set_prior_region(hcmvs_ctx* ctx, uint32_t id, const uint16_t* labels, 
 int hcmvs_get_prior_region(hcmvs_ctx* ctx, uint32_t id, uint8_t* region);
 typedef struct {
 	float normal[3];       /* unit normal, camera frame, as the candidate had it */
-	uint32_t n_inliers;    /* cnt_0: the samples assigned to the plane */
+	uint32_t n_inliers;    /* the samples assigned to the plane: cnt_0, with clustering the size of the component that was kept */
 	double centre[3];      /* centroid of the inliers, camera frame */
 	double quad[8];        /* image quad x0 y0 .. x3 y3: lower-left, lower-right, upper-right, upper-left of the plane frame */
 	int32_t box_fallback;  /* 1: a corner fell behind the camera, quad = the box of the inliers' pixels widened by half a pixel */
@@ -282,6 +285,9 @@ typedef struct {
 	float ms_gather, ms_search, ms_rounds, ms_render; /* host clock between the points where the call waits for the stream: S1; S2 + S3
 	                                                     (three neighbour searches); S4; S5 + S6 */
 	uint64_t device_bytes;     /* scratch of the call */
+	float cluster_eps;         /* the cell edge of the clustering, float32(avg_spacing * cluster_mul); 0 with clustering off */
+	int32_t cluster_rejects;   /* rounds whose winner was rejected: its largest component was smaller than min_points */
+	uint64_t cluster_left;     /* inliers that clustering left unassigned, summed over the accepted rounds */
 } hcmvs_plane_prior_stats;
 /* The prior of view `id` from its maps in DEVICE memory in the state an estimate leaves between outer iterations (d_conf = the score,
  * lower is better), which are read and never written: every pixel of d_prior (w*h floats) is written, 0 outside the region and where
@@ -292,7 +298,7 @@ typedef struct {
  * Success with an all-zero prior and no plane: no region registered, no region pixel, fewer than n_neighbors + 1 samples at any stage.
  * HCMVS_ERR_INVALID before anything reaches the device: a null pointer, an unknown view, a K whose last row is not 0 0 1 or that
  * cannot be inverted, probability outside (0, 1), min_points_div / epsilon_mul not > 0 and finite, n_neighbors outside 3 .. 31,
- * max_rounds outside 1 .. 4096, an output overlapping an input map or the other output. */
+ * max_rounds outside 1 .. 4096, cluster_mul negative, NaN or infinite, an output overlapping an input map or the other output. */
 int hcmvs_generate_plane_prior_device(hcmvs_ctx* ctx, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf,
                                       const hcmvs_plane_prior_params* params, float* d_prior, float* d_prior_normal,
                                       hcmvs_prior_plane* planes, hcmvs_plane_prior_stats* stats);
@@ -304,6 +310,11 @@ int hcmvs_generate_plane_prior_device(hcmvs_ctx* ctx, uint32_t id, const float* 
  * the valid candidates of the round; at most rounds_capacity rounds are written), *n_rounds = the rounds run. */
 int hcmvs_get_plane_prior_trace(hcmvs_ctx* ctx, uint8_t* stage, int32_t* assignment, int32_t* rounds, int32_t rounds_capacity,
                                 int32_t* n_rounds);
+/* TEST SURFACE.  What the clustering (cluster_mul, S4c) decided in every round of the same call, into a HOST buffer (may be NULL): 4 int32
+ * per round run -- occupied cells, components, size of the largest component, accepted 0 / 1; at most `capacity` rounds are written,
+ * *n_rounds = the rounds run.  A round without a winner is all zeros; with clustering off a round with a winner is 0, 0, cnt_0, 1 (and
+ * 0, 1, cnt_0, 1 when the cell edge is not a finite number > 0: all inliers are one component). */
+int hcmvs_get_plane_prior_cluster_trace(hcmvs_ctx* ctx, int32_t* clusters, int32_t capacity, int32_t* n_rounds);
 
 /* SceneDensify.cpp:783-808: splat n_points sparse world points (xyz f32) seen by view `id` as 5x5 blocks
  * into host maps depth (w*h) / normal (w*h*3); returns the depth range (min*0.9, max*1.1). Host-side helper. */
