@@ -155,8 +155,8 @@ struct PriorPlaneDev {
 };
 
 // The one device buffer of a call.  px = w * h bounds every stage (a stage never has more samples than pixels); the two sets A and B
-// take the stages in turn (samples -> A, planar -> B, fitting set -> A).  The clustering of S4c adds no piece: during S4 the pieces of the
-// neighbour search (knn.keys / keys2 / idx / idx2 / sorted / pos / sort), flags / scan / scanTmp and words are idle and have the sizes it needs
+// take the stages in turn (samples -> A, planar -> B, fitting set -> A).  The clustering of S4c adds no piece: it borrows pieces that are
+// idle during S4 (prior_gen_cluster_scratch below)
 struct PriorGenLayout {
 	size_t flags = 0, scan = 0, scanTmp = 0;             // uint32 per pixel / sample: keep flags, their exclusive scan, the scan's temporary
 	size_t xyzA = 0, nrmA = 0, pixA = 0, xyzB = 0, nrmB = 0, pixB = 0; // float3, float3, int32 per sample
@@ -186,6 +186,29 @@ inline PriorGenLayout prior_gen_layout(size_t px, size_t scanBytes, size_t sortB
 	l.knn = knn_layout(cv, px, sortBytes);
 	l.bytes = cv.size;
 	return l;
+}
+
+// The pieces S4 needs as they are, from its first round to the trace that is read after the call: the fitting set, the two maps of the
+// samples, the round's candidates and winner, and `stage` (written by S1 .. S3, read by the trace).  `acc` and `planes` are not among them:
+// S5 initialises both before it reads them.  Whatever S4c borrows must stay clear of these
+constexpr size_t PriorGenLayout::*kPriorLiveInS4[] = {&PriorGenLayout::xyzA, &PriorGenLayout::nrmA, &PriorGenLayout::pixA, &PriorGenLayout::sampleAt, &PriorGenLayout::assigned,
+                                                      &PriorGenLayout::stage, &PriorGenLayout::cand, &PriorGenLayout::counts, &PriorGenLayout::winner, &PriorGenLayout::levels};
+
+// The arrays of S4c inside the layout: where each starts and the bytes it needs for the n0 <= px samples of the fitting set.  keys / idx are
+// sorted into keys2 / idx2; cells, parent and sizes (one entry per distinct cell, at most n0) share knn.sorted, whose 16 bytes per pixel
+// they fill exactly; start borrows knn.pos; marks, scan and scanTmp are the layout's flags, scan and scanTmp doing what they do in S1 .. S3
+// (n0 + 1 words: the scan's total is read at n0); sortTmp is knn.sort; rec, the 16 words of the round's record, is `words`
+struct PriorScratchPiece { size_t off = 0, bytes = 0; };
+struct PriorClusterScratch { PriorScratchPiece keys, keys2, idx, idx2, cells, start, parent, sizes, marks, scan, scanTmp, sortTmp, rec; };
+inline PriorClusterScratch prior_gen_cluster_scratch(const PriorGenLayout& l, size_t px, size_t n0, size_t scanBytes) {
+	PriorClusterScratch c;
+	c.keys = {l.knn.keys, n0 * 8}; c.keys2 = {l.knn.keys2, n0 * 8}; c.idx = {l.knn.idx, n0 * 4}; c.idx2 = {l.knn.idx2, n0 * 4};
+	c.cells = {l.knn.sorted, n0 * 8}; c.parent = {l.knn.sorted + px * 8, n0 * 4}; c.sizes = {l.knn.sorted + px * 12, n0 * 4};
+	c.start = {l.knn.pos, n0 * 4};
+	c.marks = {l.flags, (n0 + 1) * 4}; c.scan = {l.scan, (n0 + 1) * 4}; c.scanTmp = {l.scanTmp, scanBytes};
+	c.sortTmp = {l.knn.sort, l.knn.sortBytes};
+	c.rec = {l.words, 16 * 8};
+	return c;
 }
 
 } // namespace hcmvs

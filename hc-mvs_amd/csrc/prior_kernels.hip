@@ -709,29 +709,30 @@ int generate_plane_prior_device(int w, int h, const double K[9], const uint8_t* 
 	const float cellF = clustering ? prior_gen_cluster_cell(avg, p.cluster_mul) : 0.f;
 	const bool chain = clustering && prior_gen_cluster_cell_usable(cellF);
 	st.cluster_eps = cellF;
-	// the pieces of the neighbour search and of the scans are idle during S4, and sized for px >= n0 entries
-	unsigned long long *cKeys = (unsigned long long*)(b + lay.knn.keys), *cKeys2 = (unsigned long long*)(b + lay.knn.keys2), *cCells = (unsigned long long*)(b + lay.knn.sorted);
-	uint32_t *cIdx = (uint32_t*)(b + lay.knn.idx), *cIdx2 = (uint32_t*)(b + lay.knn.idx2), *cStart = (uint32_t*)(b + lay.knn.pos);
-	uint32_t *cParent = (uint32_t*)(b + lay.knn.sorted + px * 8), *cSizes = (uint32_t*)(b + lay.knn.sorted + px * 12);
+	const PriorClusterScratch cs = prior_gen_cluster_scratch(lay, px, n0, scanBytes); // (pieces that are idle during S4)
+	unsigned long long *cKeys = (unsigned long long*)(b + cs.keys.off), *cKeys2 = (unsigned long long*)(b + cs.keys2.off), *cCells = (unsigned long long*)(b + cs.cells.off);
+	unsigned long long* cRec = (unsigned long long*)(b + cs.rec.off);
+	uint32_t *cIdx = (uint32_t*)(b + cs.idx.off), *cIdx2 = (uint32_t*)(b + cs.idx2.off), *cStart = (uint32_t*)(b + cs.start.off);
+	uint32_t *cParent = (uint32_t*)(b + cs.parent.off), *cSizes = (uint32_t*)(b + cs.sizes.off), *cMarks = (uint32_t*)(b + cs.marks.off), *cScan = (uint32_t*)(b + cs.scan.off);
 	auto cluster_round = [&](const float n[3], int32_t plane, int32_t row[4]) {
 		ClusterFrame fr;
 		prior_gen_frame(n, fr.b1, fr.b2);
 		fr.cell = (double)cellF;
 		const dim3 grid(blocks_for(n0, 2048)), block(kBlockSize);
-		hipLaunchKernelGGL(cluster_reset_kernel, dim3(1), dim3(64), 0, s, words);
-		hipLaunchKernelGGL(cluster_origin_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, words);
-		hipLaunchKernelGGL(cluster_keys_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, words, cKeys, cIdx);
-		size_t sortBytes = lay.knn.sortBytes, tmp = scanBytes;
-		if (hipcub::DeviceRadixSort::SortPairs(b + lay.knn.sort, sortBytes, cKeys, cKeys2, cIdx, cIdx2, (int)n0, 0, 64, s) != hipSuccess) return false;
-		hipLaunchKernelGGL(cluster_marks_kernel, grid, block, 0, s, n0, cKeys2, flags, words);
-		if (hipcub::DeviceScan::ExclusiveSum(b + lay.scanTmp, tmp, flags, scan, (int)(n0 + 1), s) != hipSuccess) return false;
-		hipLaunchKernelGGL(cluster_cells_kernel, grid, block, 0, s, n0, cKeys2, flags, scan, cCells, cStart, cParent, cSizes);
-		hipLaunchKernelGGL(cluster_union_kernel, grid, block, 0, s, n0, scan, cCells, cParent);
-		hipLaunchKernelGGL(cluster_sizes_kernel, grid, block, 0, s, n0, scan, cStart, words, cParent, cSizes);
-		hipLaunchKernelGGL(cluster_pick_kernel, grid, block, 0, s, n0, scan, cParent, cSizes, words);
-		hipLaunchKernelGGL(cluster_assign_kernel, grid, block, 0, s, n0, flags, scan, cIdx2, cParent, (unsigned long long)minPoints, plane, words, assigned);
+		hipLaunchKernelGGL(cluster_reset_kernel, dim3(1), dim3(64), 0, s, cRec);
+		hipLaunchKernelGGL(cluster_origin_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, cRec);
+		hipLaunchKernelGGL(cluster_keys_kernel, grid, block, 0, s, n0, xyzA, nrmA, assigned, winner, p.normal_threshold, eps, fr, cRec, cKeys, cIdx);
+		size_t sortBytes = cs.sortTmp.bytes, tmp = cs.scanTmp.bytes;
+		if (hipcub::DeviceRadixSort::SortPairs(b + cs.sortTmp.off, sortBytes, cKeys, cKeys2, cIdx, cIdx2, (int)n0, 0, 64, s) != hipSuccess) return false;
+		hipLaunchKernelGGL(cluster_marks_kernel, grid, block, 0, s, n0, cKeys2, cMarks, cRec);
+		if (hipcub::DeviceScan::ExclusiveSum(b + cs.scanTmp.off, tmp, cMarks, cScan, (int)(n0 + 1), s) != hipSuccess) return false;
+		hipLaunchKernelGGL(cluster_cells_kernel, grid, block, 0, s, n0, cKeys2, cMarks, cScan, cCells, cStart, cParent, cSizes);
+		hipLaunchKernelGGL(cluster_union_kernel, grid, block, 0, s, n0, cScan, cCells, cParent);
+		hipLaunchKernelGGL(cluster_sizes_kernel, grid, block, 0, s, n0, cScan, cStart, cRec, cParent, cSizes);
+		hipLaunchKernelGGL(cluster_pick_kernel, grid, block, 0, s, n0, cScan, cParent, cSizes, cRec);
+		hipLaunchKernelGGL(cluster_assign_kernel, grid, block, 0, s, n0, cMarks, cScan, cIdx2, cParent, (unsigned long long)minPoints, plane, cRec, assigned);
 		if (hipGetLastError() != hipSuccess) return false;
-		return hipMemcpyAsync(row, words + kClusterRecOut, 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+		return hipMemcpyAsync(row, cRec + kClusterRecOut, 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
 	};
 	while (unassigned >= minPoints && (int)found.size() < HCMVS_MAX_PRIOR_PLANES && rounds < p.max_rounds && fails < failLimit) {
 		hipLaunchKernelGGL(candidate_kernel, dim3(1), dim3(kPriorCandidates), 0, s, (unsigned)rounds, (unsigned long long)p.seed, n0, w, h, dLevels, nLevels, xyzA, nrmA, pixA,

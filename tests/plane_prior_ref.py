@@ -1,7 +1,10 @@
 """The plane-prior rule (hcmvs_generate_plane_prior_device) stated in numpy, from the text of the rule alone:
-brute-force neighbour search, numpy's eigen-solver, Python integers for the fixed-point sums.  What the device must reproduce: every
-integer decision, the two averages, eps, the plane table and the prior map bit for bit; S2's planarity up to the eigen-solver's
-rounding, for which `flags["S2"]` marks the samples whose decision a last-ulp difference could turn (|p - planarity_min| < 1e-6)."""
+brute-force neighbour search, numpy's eigen-solver, Python integers for the fixed-point sums, and for S4c a plain flood fill over a dict of
+cells.  What the device must reproduce: every integer decision, the two averages, eps, the plane table and the prior map bit for bit; S2's
+planarity up to the eigen-solver's rounding, for which `flags["S2"]` marks the samples whose decision a last-ulp difference could turn
+(|p - planarity_min| < 1e-6).  tests/golden/plane_prior_statement.json holds what generate() returns, with S4c and without."""
+import copy
+
 import numpy as np
 
 F32 = np.float32
@@ -9,6 +12,7 @@ M = 256                      # candidates of a round
 MAX_PLANES = 64
 SPACING_SHIFT, COORD_SHIFT = 40, 32
 MASK = (1 << 64) - 1
+CELL_CAP = 1 << 30           # S4c: the largest cell coordinate
 
 DEFAULTS = dict(conf_max=0.18, planarity_min=0.3, n_neighbors=10, probability=0.01, min_points_div=80.0, epsilon_mul=2.0, normal_threshold=0.25,
                 max_rounds=256, seed=1)
@@ -217,15 +221,60 @@ def fitting_set(depth, normal, conf, region, K, **params):
     return state
 
 
-def generate(depth, normal, conf, region, K, state=None, **params):
-    """region: (h, w) bool.  Returns dict(prior, prior_normal, planes, stats, stage, assignment, rounds, flags).  state: what fitting_set
-    returned for the same inputs and parameters (the stages before the plane detection do not depend on the seed)"""
-    import copy
+def cluster_cell(avg, mul):
+    """float32(avg * float32(mul)) as a double"""
+    with np.errstate(all="ignore"):
+        return float(F32(float(avg) * float(F32(mul))))
+
+
+def largest_component(P, n, cell):
+    """S4c steps 2 .. 4 on the inliers P (m, 3) f32 of the plane with normal n: (indices into P of the winning component, occupied cells,
+    components, its size)"""
+    b1, b2 = frame(n)
+    P64 = P.astype(np.float64)
+    u = (P64[:, 0] * b1[0] + P64[:, 1] * b1[1]) + P64[:, 2] * b1[2]
+    v = (P64[:, 0] * b2[0] + P64[:, 1] * b2[1]) + P64[:, 2] * b2[2]
+    with np.errstate(all="ignore"):
+        cu = np.minimum(np.floor((u - u.min()) / cell), float(CELL_CAP))
+        cv = np.minimum(np.floor((v - v.min()) / cell), float(CELL_CAP))
+    cells = {}
+    for i in range(len(P)):
+        cells.setdefault((int(cv[i]), int(cu[i])), []).append(i)
+    label, comps = {}, []          # comps: (size, smallest (cv, cu) cell, members)
+    for start in sorted(cells):     # ascending (cv, cu): a component is met at its smallest cell first
+        if start in label:
+            continue
+        label[start] = len(comps)
+        stack, members = [start], []
+        while stack:
+            c = stack.pop()
+            members += cells[c]
+            for dv in (-1, 0, 1):
+                for du in (-1, 0, 1):
+                    nb = (c[0] + dv, c[1] + du)
+                    if nb in cells and nb not in label:
+                        label[nb] = len(comps)
+                        stack.append(nb)
+        comps.append((len(members), start, members))
+    best = None
+    for size, start, members in comps:
+        if best is None or size > best[0] or (size == best[0] and start < best[1]):
+            best = (size, start, members)
+    return np.array(sorted(best[2]), np.int64), len(cells), len(comps), best[0]
+
+
+def generate(depth, normal, conf, region, K, state=None, cluster_mul=0.0, **params):
+    """region: (h, w) bool.  Returns dict(prior, prior_normal, planes, stats, stage, assignment, rounds, clusters, flags).  state: what
+    fitting_set returned for the same inputs and parameters (the stages before the plane detection do not depend on the seed).
+    cluster_mul > 0 applies S4c to the winner of a round before anything is assigned.  clusters: 4 int32 per round (occupied cells,
+    components, size of the largest component, accepted 0 / 1); without S4c a winner's row is 0, 0, its inliers, 1"""
     p = dict(DEFAULTS); p.update(params)
     if state is None:
         state = fitting_set(depth, normal, conf, region, K, **params)
     out = copy.deepcopy(state["out"])
     st = out["stats"]
+    st.update(cluster_eps=F32(0), cluster_rejects=0, cluster_left=0)
+    out["clusters"] = np.zeros((0, 4), np.int32)
     if state["fit"] is None:
         return out
     depth, region, ray, K = state["depth"], state["region"], state["ray"], state["K"]
@@ -237,13 +286,17 @@ def generate(depth, normal, conf, region, K, state=None, **params):
     eps = F32(avg * float(F32(p["epsilon_mul"])))
     minp = min_points(n0, p["min_points_div"])
     st["eps"] = eps; st["min_points"] = minp
+    clustering = float(F32(cluster_mul)) > 0
+    cell = cluster_cell(avg, cluster_mul) if clustering else 0.0
+    cell_ok = cell > 0 and np.isfinite(cell)
+    st["cluster_eps"] = F32(cell)
     # S4
     lv = levels(w, h)
     sample_at = np.full(w * h, -1, np.int64); sample_at[pix] = np.arange(n0)
     assigned = np.full(n0, -1, np.int32)
     limit = fail_limit(p["probability"], minp, n0, p["max_rounds"])
     eps_k = [eps, eps * F32(0.5), eps * F32(0.25), eps * F32(0.125)]
-    found, rounds, fails, unassigned, seed = [], [], 0, n0, int(p["seed"]) & MASK
+    found, rounds, clusters, fails, unassigned, seed = [], [], [], 0, n0, int(p["seed"]) & MASK
     Px, Py, Pz, Nx, Ny, Nz = P[:, 0], P[:, 1], P[:, 2], N[:, 0], N[:, 1], N[:, 2]
     while unassigned >= minp and len(found) < MAX_PLANES and len(rounds) < int(p["max_rounds"]) and fails < limit:
         r = len(rounds)
@@ -291,13 +344,28 @@ def generate(depth, normal, conf, region, K, state=None, **params):
             nx, ny, nz, d = cands[best]
             with np.errstate(invalid="ignore"):
                 inl = free & (np.abs(dot3(nx, ny, nz, Nx, Ny, Nz)) >= thr) & (np.abs(dot3(nx, ny, nz, Px, Py, Pz) - d) <= eps)
-            assigned[inl] = len(found)
-            found.append((np.array([nx, ny, nz], F32), best_counts[0]))
-            unassigned -= best_counts[0]
-            fails = 0
+            take = np.nonzero(inl)[0]
+            assert len(take) == best_counts[0]
+            size, row = best_counts[0], [0, 1 if clustering else 0, best_counts[0], 1]
+            if clustering and cell_ok:                                            # S4c
+                keep, n_cells, n_comps, size = largest_component(P[take], np.array([nx, ny, nz], F32), cell)
+                take = take[keep]
+                row = [n_cells, n_comps, size, int(size >= minp)]
+            clusters.append(row)
+            if row[3]:
+                assigned[take] = len(found)
+                found.append((np.array([nx, ny, nz], F32), size))
+                unassigned -= size
+                st["cluster_left"] += best_counts[0] - size
+                fails = 0
+            else:
+                st["cluster_rejects"] += 1
+                fails += 1
         else:
+            clusters.append([0, 0, 0, 0])
             fails += 1
     out["rounds"] = np.array(rounds, np.int32).reshape(-1, 6)
+    out["clusters"] = np.array(clusters, np.int32).reshape(-1, 4)
     out["assignment"].reshape(-1)[pix] = assigned
     st["rounds"] = len(rounds); st["planes"] = len(found)
     if not found:

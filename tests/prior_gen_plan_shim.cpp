@@ -21,6 +21,8 @@ int pgp_levels(int w, int h, int32_t* levels) { return prior_gen_levels(w, h, le
 long long pgp_min_points(unsigned long long n0, float div) { return (long long)prior_gen_min_points(n0, div); }
 int pgp_fail_limit(float probability, long long minPoints, unsigned long long n0, int maxRounds) { return prior_gen_fail_limit(probability, minPoints, n0, maxRounds); }
 float pgp_eps(double avg, float mul) { return prior_gen_eps(avg, mul); }
+float pgp_cell(double avg, float mul) { return prior_gen_cluster_cell(avg, mul); }
+int pgp_cell_usable(float cell) { return prior_gen_cluster_cell_usable(cell) ? 1 : 0; }
 double pgp_mean(long long hi, unsigned long long lo, unsigned long long n, int shift) { return prior_gen_mean(hi, lo, n, shift); }
 void pgp_frame(const float* n, double* b1, double* b2) { prior_gen_frame(n, b1, b2); }
 int pgp_quad(const double* K, const double* c, const double* b1, const double* b2, const double* uv, const int32_t* box, double* quad) {
@@ -35,9 +37,28 @@ int pgp_layout(unsigned long long px, unsigned long long scanBytes, unsigned lon
 	for (int i = 0; i < n; ++i) out[i] = v[i];
 	return n;
 }
-void pgp_constants(int* out) {
+// (offset, bytes) of the arrays of S4c for n0 samples, in the order of PriorClusterScratch; returns how many arrays
+int pgp_cluster_scratch(unsigned long long px, unsigned long long scanBytes, unsigned long long sortBytes, unsigned long long n0, unsigned long long* out) {
+	const PriorClusterScratch c = prior_gen_cluster_scratch(prior_gen_layout((size_t)px, (size_t)scanBytes, (size_t)sortBytes), (size_t)px, (size_t)n0, (size_t)scanBytes);
+	const PriorScratchPiece v[] = {c.keys, c.keys2, c.idx, c.idx2, c.cells, c.start, c.parent, c.sizes, c.marks, c.scan, c.scanTmp, c.sortTmp, c.rec};
+	const int n = (int)(sizeof v / sizeof v[0]);
+	for (int i = 0; i < n; ++i) { out[2 * i] = v[i].off; out[2 * i + 1] = v[i].bytes; }
+	return n;
+}
+// the offsets of the pieces that are live during S4; returns how many
+int pgp_live_in_s4(unsigned long long px, unsigned long long scanBytes, unsigned long long sortBytes, unsigned long long* out) {
+	const PriorGenLayout l = prior_gen_layout((size_t)px, (size_t)scanBytes, (size_t)sortBytes);
+	int n = 0;
+	for (const auto piece : kPriorLiveInS4) out[n++] = l.*piece;
+	return n;
+}
+// 0..5 the constants, 6..9 struct sizes, 10 the cap of a cell coordinate, 11..14 offsetof cluster_mul / cluster_eps / cluster_rejects / cluster_left
+void pgp_constants(long long* out) {
 	out[0] = kPriorCandidates; out[1] = kPriorMaxLevels; out[2] = kPriorMaxRounds; out[3] = kPriorSpacingShift; out[4] = kPriorCoordShift; out[5] = HCMVS_MAX_PRIOR_PLANES;
-	out[6] = (int)sizeof(PriorPlaneDev); out[7] = (int)sizeof(hcmvs_prior_plane); out[8] = (int)sizeof(hcmvs_plane_prior_params); out[9] = (int)sizeof(hcmvs_plane_prior_stats);
+	out[6] = (long long)sizeof(PriorPlaneDev); out[7] = (long long)sizeof(hcmvs_prior_plane); out[8] = (long long)sizeof(hcmvs_plane_prior_params);
+	out[9] = (long long)sizeof(hcmvs_plane_prior_stats); out[10] = (long long)kPriorClusterCellCap;
+	out[11] = (long long)offsetof(hcmvs_plane_prior_params, cluster_mul); out[12] = (long long)offsetof(hcmvs_plane_prior_stats, cluster_eps);
+	out[13] = (long long)offsetof(hcmvs_plane_prior_stats, cluster_rejects); out[14] = (long long)offsetof(hcmvs_plane_prior_stats, cluster_left);
 }
 
 } // extern "C"
@@ -74,9 +95,26 @@ int main() {
 	unsigned long long lay[40];
 	const int m = pgp_layout(px, 1000, 3000, lay);
 	for (int i = 1; i < m; ++i) if (lay[i] <= lay[i - 1] || lay[i] % 256) return 11;
-	int k[10];
+	p.n_neighbors = 10;
+	if (pgp_check(good, 96, 80, K, &p, why, (int)sizeof why) != 0) return 12;
+	p.cluster_mul = 7.f;
+	if (pgp_check(good, 96, 80, K, &p, why, (int)sizeof why) != 0) return 13;
+	p.cluster_mul = -1.f;
+	if (pgp_check(good, 96, 80, K, &p, why, (int)sizeof why) == 0 || !strstr(why, "cluster_mul")) return 14;
+	p.cluster_mul = NAN;
+	if (pgp_check(good, 96, 80, K, &p, why, 8) == 0) return 15; // (a short buffer again)
+	p.cluster_mul = INFINITY;
+	if (pgp_check(good, 96, 80, K, &p, why, (int)sizeof why) == 0) return 16;
+	if (pgp_cell(0.5, 2.f) != 1.f || !pgp_cell_usable(pgp_cell(0.05, 7.f))) return 17;
+	if (pgp_cell(0.05, 1e-45f) != 0.f || pgp_cell_usable(pgp_cell(0.05, 1e-45f)) || pgp_cell_usable(pgp_cell(1e30, 1e30f)) || pgp_cell_usable(-1.f)) return 18;
+	unsigned long long cl[26], live[16];
+	if (pgp_cluster_scratch(px, 1000, 3000, px, cl) != 13 || pgp_live_in_s4(px, 1000, 3000, live) != 10) return 19;
+	for (int i = 0; i < 13; ++i) if (cl[2 * i] + cl[2 * i + 1] > lay[m - 1]) return 20;
+	long long k[15];
 	pgp_constants(k);
+	if (k[10] != (1ll << 30)) return 21;
 	printf("prior_gen_plan ok %d %llu\n", m, lay[m - 1]);
+	printf("prior_cluster_plan ok %lld %lld\n", k[8], k[9]);
 	return 0;
 }
 #endif

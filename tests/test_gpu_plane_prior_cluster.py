@@ -1,21 +1,19 @@
 """hcmvs_generate_plane_prior_device with cluster_mul > 0 (a plane keeps the largest connected component of its
-inliers) against the numpy statement tests/plane_prior_cluster_ref.py, on the inputs of tests/plane_prior_cluster_cases.py and on three of
-tests/plane_prior_cases.py: everything test_gpu_plane_prior.assert_same compares, the cluster trace and the three cluster stats, exactly."""
+inliers) against the numpy statement tests/plane_prior_ref.py, on the inputs of plane_prior_cases.CLUSTER_CASES and on three of
+plane_prior_cases.CASES: everything test_gpu_plane_prior.assert_same compares, the cluster trace and the three cluster stats, exactly."""
 import importlib
 
 import numpy as np
 import pytest
 
 import plane_prior_cases as cases
-import plane_prior_cluster_cases as ccases
-import plane_prior_cluster_ref as cref
 import plane_prior_ref as ref
 import test_gpu_plane_prior as GP
 
 pytestmark = pytest.mark.gpu
 binding = importlib.import_module("hc-mvs_amd.binding")
 SEEDS = (1, 2)
-NAMES = list(ccases.CASES) + ["crease", "two_blobs", "plane_and_sphere"]
+NAMES = list(cases.CLUSTER_CASES) + ["crease", "two_blobs", "plane_and_sphere"]
 
 torch = GP.torch
 ctx = GP.ctx
@@ -27,7 +25,7 @@ def case_of(name):
     if name in cases.CASES:
         return GP.case_of(name), GP._states[name]
     if name not in _inputs:
-        _inputs[name] = ccases.CASES[name]()
+        _inputs[name] = cases.CLUSTER_CASES[name]()
         c = _inputs[name]
         _states[name] = ref.fitting_set(c["depth"], c["normal"], c["conf"], c["region"], c["K"])
     return _inputs[name], _states[name]
@@ -35,7 +33,7 @@ def case_of(name):
 
 def expected(name, **params):
     c, state = case_of(name)
-    return cref.generate(c["depth"], c["normal"], c["conf"], c["region"], c["K"], state=state, **params)
+    return ref.generate(c["depth"], c["normal"], c["conf"], c["region"], c["K"], state=state, **params)
 
 
 def device(torch, ctx, name, **params):
@@ -60,7 +58,7 @@ def gap_share(case, prior):
 
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("mul", [2.0, 3.0])
-@pytest.mark.parametrize("name", list(ccases.CASES))
+@pytest.mark.parametrize("name", list(cases.CLUSTER_CASES))
 def test_device_equals_the_statement_on_the_new_cases(torch, ctx, name, mul, seed):
     want = expected(name, cluster_mul=mul, seed=seed)
     got, trace, clusters = device(torch, ctx, name, cluster_mul=mul, seed=seed)

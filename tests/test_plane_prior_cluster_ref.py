@@ -1,35 +1,24 @@
-"""The plane-prior rule with inlier clustering as its numpy statement computes it
-(tests/plane_prior_cluster_ref.py): with cluster_mul = 0 it is tests/plane_prior_ref.py field for field and bit for bit, and on the inputs
-of tests/plane_prior_cluster_cases.py it separates what the unclustered rule paints across -- the figures in the assertions follow from
-the rule (components, ties, the rejected round), none is a value the device gave."""
+"""The plane-prior rule with inlier clustering as its numpy statement computes it (tests/plane_prior_ref.py
+with cluster_mul > 0): on the inputs of plane_prior_cases.CLUSTER_CASES it separates what the unclustered rule paints across -- the figures
+in the assertions follow from the rule (components, ties, the rejected round), none is a value the device gave.  That cluster_mul = 0
+leaves the unclustered rule's bits is held by tests/test_plane_prior_golden.py."""
 import numpy as np
 import pytest
 
-import plane_prior_cluster_cases as ccases
-import plane_prior_cluster_ref as cref
 import plane_prior_ref as ref
 import test_plane_prior_ref as TR
 
 SEEDS = (1, 2)
-_cache = {}
-
-
-def stages(name):
-    if name in TR.cases.CASES:
-        return TR.stages(name)
-    if name not in _cache:
-        c = ccases.CASES[name]()
-        _cache[name] = (c, ref.fitting_set(c["depth"], c["normal"], c["conf"], c["region"], c["K"]))
-    return _cache[name]
+stages = TR.stages
 
 
 def generate(name, **params):
     c, state = stages(name)
-    return c, cref.generate(c["depth"], c["normal"], c["conf"], c["region"], c["K"], state=state, **params)
+    return c, ref.generate(c["depth"], c["normal"], c["conf"], c["region"], c["K"], state=state, **params)
 
 
 def same_bits(a, b):
-    """every field plane_prior_ref.generate returns, compared exactly"""
+    """the maps, the round trace, the flags, every stat of b and the planes, compared exactly"""
     for k in ("prior", "prior_normal", "stage", "assignment", "rounds"):
         assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
     assert np.array_equal(a["flags"]["S2"], b["flags"]["S2"])
@@ -50,20 +39,7 @@ def gap_share(c, res):
     return float((res["prior"][c["gap"]] > 0).mean())
 
 
-@pytest.mark.parametrize("seed", SEEDS)
-@pytest.mark.parametrize("name", list(TR.cases.CASES))
-def test_without_clustering_it_is_the_unclustered_statement(name, seed):
-    c, state = stages(name)
-    want = ref.generate(c["depth"], c["normal"], c["conf"], c["region"], c["K"], state=state, seed=seed)
-    _, got = generate(name, cluster_mul=0.0, seed=seed)
-    same_bits(got, want)
-    win = want["rounds"][:, 0] >= 0
-    assert got["clusters"].shape == (len(want["rounds"]), 4) and not got["clusters"][~win].any()
-    assert np.array_equal(got["clusters"][win], [[0, 0, n, 1] for n in want["rounds"][win, 1]])
-    assert got["stats"]["cluster_eps"] == 0 and got["stats"]["cluster_rejects"] == 0 and got["stats"]["cluster_left"] == 0
-
-
-@pytest.mark.parametrize("name", list(ccases.CASES))
+@pytest.mark.parametrize("name", list(TR.cases.CLUSTER_CASES))
 def test_no_new_input_carries_a_flagged_sample(name):
     c, state = stages(name)
     flags = state["out"]["flags"]["S2"]

@@ -23,8 +23,9 @@ _cache = {}
 
 
 def stages(name):
+    """a case of either dict and its fitting set, made once"""
     if name not in _cache:
-        c = cases.CASES[name]()
+        c = (cases.CASES.get(name) or cases.CLUSTER_CASES[name])()
         _cache[name] = (c, ref.fitting_set(c["depth"], c["normal"], c["conf"], c["region"], c["K"]))
     return _cache[name]
 

@@ -1,6 +1,8 @@
 """The host half of hcmvs_generate_plane_prior_device (hc-mvs_amd/csrc/prior_gen_plan.h) on the CPU: every refusal, Kinv against numpy, the
 level table, min_points, the stop rule, the decoding of the fixed-point sums, frame and quad bit for bit against the numpy statement of the
-rule (tests/plane_prior_ref.py), and the scratch layout.  tests/prior_gen_plan_shim.cpp is compiled with g++ alone, with -ffp-contract=off as
+rule (tests/plane_prior_ref.py), the scratch layout, and what the inlier clustering adds: the refusals of
+cluster_mul, the cell edge against numpy (a product that underflows to 0 included), the cap, the sizes and offsets of the two structs
+against the binding, and the arrays it borrows from the layout during S4.  tests/prior_gen_plan_shim.cpp is compiled with g++ alone, with -ffp-contract=off as
 the library is: no HIP, no library; the same file is also built as a stand-alone program under the address and undefined-behaviour
 sanitizers and run once."""
 import ctypes as C
@@ -46,7 +48,11 @@ def lib():
     L.pgp_frame.argtypes = [fp, dp, dp]; L.pgp_frame.restype = None
     L.pgp_quad.argtypes = [dp, dp, dp, dp, dp, C.POINTER(I32), dp]
     L.pgp_layout.argtypes = [C.c_ulonglong] * 3 + [C.POINTER(C.c_ulonglong)]
-    L.pgp_constants.argtypes = [C.POINTER(C.c_int)]; L.pgp_constants.restype = None
+    L.pgp_cell.argtypes = [F64, F32]; L.pgp_cell.restype = F32
+    L.pgp_cell_usable.argtypes = [F32]
+    L.pgp_cluster_scratch.argtypes = [C.c_ulonglong] * 4 + [C.POINTER(C.c_ulonglong)]
+    L.pgp_live_in_s4.argtypes = [C.c_ulonglong] * 3 + [C.POINTER(C.c_ulonglong)]
+    L.pgp_constants.argtypes = [C.POINTER(C.c_longlong)]; L.pgp_constants.restype = None
     return L
 
 
@@ -55,7 +61,7 @@ def dptr(a):
 
 
 def params(**kw):
-    p = binding.PlanePriorParams(255, 0.18, 0.3, 10, 0.01, 80.0, 2.0, 0.25, 256, 1)  # the documented defaults, without the library
+    p = binding.PlanePriorParams(255, 0.18, 0.3, 10, 0.01, 80.0, 2.0, 0.25, 256, 1)  # the documented defaults, without the library: cluster_mul is 0
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -74,9 +80,14 @@ def check(lib, addr=None, w=96, h=80, K=K0, p=None, null_K=False, null_p=False):
     return buf.value.decode()
 
 
-def test_constants_and_struct_sizes(lib):
-    k = (C.c_int * 10)()
+def constants(lib):
+    k = (C.c_longlong * 15)()
     lib.pgp_constants(k)
+    return list(k)
+
+
+def test_constants_and_struct_sizes(lib):
+    k = constants(lib)
     assert list(k[:6]) == [ref.M, 16, 4096, ref.SPACING_SHIFT, ref.COORD_SHIFT, ref.MAX_PLANES] and ref.MAX_PLANES == binding.MAX_PRIOR_PLANES
     assert k[6] % 8 == 0 and k[7] == C.sizeof(binding.PriorPlane) and k[8] == C.sizeof(binding.PlanePriorParams) and k[9] == C.sizeof(binding.PlanePriorStats)
 
@@ -212,15 +223,95 @@ def test_scratch_layout_is_monotone_and_aligned(lib):
 
 
 def k_plane_dev(lib):
-    k = (C.c_int * 10)()
-    lib.pgp_constants(k)
-    return k[6]
+    return constants(lib)[6]
 
 
-def test_the_plan_runs_clean_under_the_host_sanitizers(tmp_path):
+def test_cluster_mul_is_refused_unless_finite_and_not_negative(lib):
+    assert params().cluster_mul == 0.0 and check(lib) == ""
+    for v in (0.0, 1e-45, 2.0, 7.0, 10.0, 3e38):
+        assert check(lib, p=params(cluster_mul=v)) == ""
+    for v in (-1.0, -1e-45, float("nan"), float("inf"), float("-inf")):
+        assert "cluster_mul" in check(lib, p=params(cluster_mul=v)), v
+    assert "probability" in check(lib, p=params(cluster_mul=-1.0, probability=0.0))          # the earlier refusals keep their order
+
+
+def test_the_cell_edge_against_numpy(lib):
+    rng = np.random.RandomState(5)
+    for avg, mul in list(zip(rng.uniform(1e-3, 0.5, 200), rng.uniform(0.1, 20, 200))) + [(0.0921947, 7.0), (0.05, 1e-45), (0.4, 1e-45), (1e30, 1e30), (1e-300, 2.0), (0.07, 1e-9)]:
+        got = lib.pgp_cell(avg, mul)
+        with np.errstate(all="ignore"):
+            want = np.float32(np.float64(avg) * np.float64(np.float32(mul)))
+        assert np.float32(got).tobytes() == want.tobytes(), (avg, mul)
+        assert float(np.float32(got)) == ref.cluster_cell(avg, mul)
+        assert lib.pgp_cell_usable(got) == int(want > 0 and np.isfinite(want))
+    assert lib.pgp_cell(0.05, 1e-45) == 0.0 and lib.pgp_cell_usable(0.0) == 0        # the product underflowed: nothing is clustered
+    assert np.isinf(lib.pgp_cell(1e30, 1e30)) and lib.pgp_cell_usable(float("inf")) == 0 and lib.pgp_cell_usable(float("nan")) == 0
+    assert lib.pgp_cell_usable(-1.0) == 0 and lib.pgp_cell_usable(1e-45) == 1
+
+
+def test_constants_and_struct_layout_against_the_binding(lib):
+    k = constants(lib)
+    assert k[10] == 1 << 30 == ref.CELL_CAP
+    P, S = binding.PlanePriorParams, binding.PlanePriorStats
+    assert k[8] == C.sizeof(P) and k[9] == C.sizeof(S)
+    assert k[11] == P.cluster_mul.offset and P._fields_[-1][0] == "cluster_mul"           # the new last field
+    assert [k[12], k[13], k[14]] == [S.cluster_eps.offset, S.cluster_rejects.offset, S.cluster_left.offset]
+    assert [f for f, _ in S._fields_][-4:] == ["device_bytes", "cluster_eps", "cluster_rejects", "cluster_left"]
+
+
+# pgp_layout's order, and pgp_cluster_scratch's
+PIECES = ("flags", "scan", "scanTmp", "xyzA", "nrmA", "pixA", "xyzB", "nrmB", "pixB", "spacing", "sampleAt", "assigned", "stage", "cand", "counts", "winner", "acc", "planes",
+          "words", "levels", "knn.keys", "knn.keys2", "knn.idx", "knn.idx2", "knn.sorted", "knn.pos", "knn.box", "knn.sort", "bytes")
+CLUSTER_ARRAYS = ("keys", "keys2", "idx", "idx2", "cells", "start", "parent", "sizes", "marks", "scan", "scanTmp", "sortTmp", "rec")
+LIVE_IN_S4 = ("xyzA", "nrmA", "pixA", "sampleAt", "assigned", "stage", "cand", "counts", "winner", "levels")
+
+
+@pytest.mark.parametrize("px", [1, 255, 96 * 80, 1920 * 1080, 2 ** 29 - 1])
+def test_the_cluster_scratch_stays_inside_idle_pieces(lib, px):
+    """S4c at n0 = px, the most samples a call can have: every array ends inside the piece it borrows, no two overlap, none touches a
+    piece S4 keeps live, and the offsets are the expressions generate_plane_prior_device had inline before the plan stated them"""
+    out, cl, lv = (C.c_ulonglong * 40)(), (C.c_ulonglong * 26)(), (C.c_ulonglong * 16)()
+    for scan, sort in ((0, 0), (1, 1), (1000, 3000), (70000, 9000000), (767, 4 * px + 12345)):
+        assert lib.pgp_layout(px, scan, sort, out) == len(PIECES)
+        lay = dict(zip(PIECES, out))
+        after = dict(zip(PIECES, list(out)[1:]))                                  # where the next piece starts
+        assert lib.pgp_cluster_scratch(px, scan, sort, px, cl) == len(CLUSTER_ARRAYS)
+        got = {name: (cl[2 * i], cl[2 * i + 1]) for i, name in enumerate(CLUSTER_ARRAYS)}
+        srt = lay["knn.sorted"]
+        want = dict(keys=(lay["knn.keys"], px * 8), keys2=(lay["knn.keys2"], px * 8), idx=(lay["knn.idx"], px * 4), idx2=(lay["knn.idx2"], px * 4), cells=(srt, px * 8),
+                    start=(lay["knn.pos"], px * 4), parent=(srt + px * 8, px * 4), sizes=(srt + px * 12, px * 4), marks=(lay["flags"], (px + 1) * 4),
+                    scan=(lay["scan"], (px + 1) * 4), scanTmp=(lay["scanTmp"], scan), sortTmp=(lay["knn.sort"], sort), rec=(lay["words"], 128))
+        assert got == want
+        borrowed = dict(keys="knn.keys", keys2="knn.keys2", idx="knn.idx", idx2="knn.idx2", cells="knn.sorted", start="knn.pos", parent="knn.sorted", sizes="knn.sorted",
+                        marks="flags", scan="scan", scanTmp="scanTmp", sortTmp="knn.sort", rec="words")
+        for name, (off, size) in got.items():
+            assert lay[borrowed[name]] <= off and off + size <= after[borrowed[name]], name
+        spans = sorted(v for v in got.values() if v[1])
+        assert all(a[0] + a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+        assert lib.pgp_live_in_s4(px, scan, sort, lv) == len(LIVE_IN_S4) and list(lv[:len(LIVE_IN_S4)]) == [lay[name] for name in LIVE_IN_S4]
+        assert not set(LIVE_IN_S4) & set(borrowed.values())
+        for name in LIVE_IN_S4:
+            assert all(off + size <= lay[name] or after[name] <= off for off, size in got.values()), name
+        # fewer samples need no more
+        assert lib.pgp_cluster_scratch(px, scan, sort, px // 2, cl) == len(CLUSTER_ARRAYS)
+        assert all(cl[2 * i] == got[name][0] and cl[2 * i + 1] <= got[name][1] for i, name in enumerate(CLUSTER_ARRAYS))
+
+
+@pytest.fixture(scope="module")
+def sanitizer_run(tmp_path_factory):
     """the same file with its own main, built with -fsanitize=address,undefined, run once: host code, no library, no device"""
-    exe = tmp_path / "prior_gen_plan_main"
+    exe = tmp_path_factory.mktemp("pgp") / "prior_gen_plan_main"
     subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-DPGP_MAIN", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", "-o", str(exe), SRC])
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+
+
+def test_the_plan_runs_clean_under_the_host_sanitizers(sanitizer_run):
+    out = sanitizer_run
     assert out.returncode == 0 and "prior_gen_plan ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_the_cluster_entries_run_clean_under_the_host_sanitizers(sanitizer_run):
+    """the one main walks the refusals of cluster_mul, the cell edge, the cap and the S4c scratch after the rest"""
+    out = sanitizer_run
+    assert out.returncode == 0 and "prior_cluster_plan ok" in out.stdout, out.stdout + out.stderr

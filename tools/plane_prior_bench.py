@@ -1,6 +1,6 @@
 """diagnostic (not a test): what the plane detection (S4) of hcmvs_generate_plane_prior_device costs with and without the clustering of a
 plane's inliers (cluster_mul), from hcmvs_plane_prior_stats.ms_rounds (host clock between the waits):
-  doorway  96 x 80, tests/plane_prior_cluster_cases.py, cluster_mul 0 and 2
+  doorway  96 x 80, tests/plane_prior_cases.py::doorway, cluster_mul 0 and 2
   crease   1920 x 1080, the two planes of tests/plane_prior_cases.py::crease at a focal length of 1800, region = the middle half of the
            rows, cluster_mul 0 and 7
 --reps calls each after a discarded first one (it allocates).  One JSON line per scene and cluster_mul: ms_rounds of every call, rounds,
@@ -21,7 +21,6 @@ import numpy as np
 import torch
 binding = importlib.import_module("hc-mvs_amd.binding")
 import plane_prior_cases as PC
-import plane_prior_cluster_cases as CC
 
 
 def big_crease(w=1920, h=1080, focal=1800.0):
@@ -40,7 +39,7 @@ def big_crease(w=1920, h=1080, focal=1800.0):
 has_field = hasattr(binding.PlanePriorParams(), "cluster_mul")
 ctx = binding.Context(0)
 lines = []
-for vid, (name, case, muls) in enumerate((("doorway", CC.doorway(), (0.0, 2.0)), ("crease_1080p", big_crease(), (0.0, 7.0)))):
+for vid, (name, case, muls) in enumerate((("doorway", PC.doorway(), (0.0, 2.0)), ("crease_1080p", big_crease(), (0.0, 7.0)))):
     h, w = case["depth"].shape
     ctx.upload_view(vid, np.zeros((h, w), np.float32), case["K"], np.eye(3), np.zeros(3))
     ctx.set_prior_region(vid, np.where(case["region"], 255, 7).astype(np.uint16), 255)
