@@ -104,6 +104,15 @@ class PriorStats(C.Structure):
     _fields_ = [("evals_prior", C.c_uint64), ("pixels_prior", C.c_uint64)]
 
 
+class GeoParams(C.Structure):
+    _fields_ = [("on", C.c_int32), ("para_tapa", C.c_float), ("para_tapa2", C.c_float), ("txthreshold", C.c_float), ("txthreshold2", C.c_float),
+                ("photo2geo", C.c_int32), ("max_px", C.c_float)]
+
+
+class GeoStats(C.Structure):
+    _fields_ = [("evals_geo", C.c_uint64), ("pixels_geo", C.c_uint64)]
+
+
 class PlanePriorParams(C.Structure):
     _fields_ = [("region_label", C.c_int32), ("conf_max", C.c_float), ("planarity_min", C.c_float), ("n_neighbors", C.c_int32), ("probability", C.c_float),
                 ("min_points_div", C.c_float), ("epsilon_mul", C.c_float), ("normal_threshold", C.c_float), ("max_rounds", C.c_int32), ("seed", C.c_uint64),
@@ -153,6 +162,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_handoff_maps", "hcmvs_handoff_maps_device", "hcmvs_get_handoff_stats",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats",
+           "hcmvs_default_geo_params", "hcmvs_set_geo_params", "hcmvs_get_geo_stats",
            "hcmvs_default_prior_params", "hcmvs_set_prior_params", "hcmvs_set_depth_prior", "hcmvs_set_depth_prior_device",
            "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats",
            "hcmvs_default_plane_prior_params", "hcmvs_set_prior_region", "hcmvs_get_prior_region", "hcmvs_generate_plane_prior_device",
@@ -317,6 +327,10 @@ def lib():
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.hcmvs_get_spread_stats.argtypes = [vp, C.POINTER(SpreadStats)]
+        L.hcmvs_default_geo_params.argtypes = [C.POINTER(GeoParams)]
+        L.hcmvs_default_geo_params.restype = None
+        L.hcmvs_set_geo_params.argtypes = [vp, C.POINTER(GeoParams)]
+        L.hcmvs_get_geo_stats.argtypes = [vp, C.POINTER(GeoStats)]
         L.hcmvs_default_prior_params.argtypes = [C.POINTER(PriorParams)]
         L.hcmvs_default_prior_params.restype = None
         L.hcmvs_set_prior_params.argtypes = [vp, C.POINTER(PriorParams)]
@@ -363,6 +377,16 @@ def default_plane_prior_params(**kw):
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_geo_params(**kw):
+    """hcmvs_default_geo_params (off, 0.25, 0.15, 150, 160, 2, 3.0), then the overrides"""
+    p = GeoParams()
+    lib().hcmvs_default_geo_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
         setattr(p, k, v)
     return p
 
@@ -679,6 +703,21 @@ class Context:
         s = Stats()
         self._chk(lib().hcmvs_get_stats(self._h, C.byref(s)))
         return s
+
+    # ---- geometric consistency (--geo-consistency) -------------------------------
+
+    def set_geo_params(self, on=True, **kw):
+        """the geometric-consistency term for the estimates that follow: on, para_tapa, para_tapa2, txthreshold, txthreshold2, photo2geo,
+        max_px; a missing key keeps its default (hcmvs_default_geo_params).  The source views' maps are the ones registered with
+        set_spread_maps_device."""
+        p = default_geo_params(on=int(bool(on)), **kw)
+        self._chk(lib().hcmvs_set_geo_params(self._h, C.byref(p)))
+
+    def get_geo_stats(self):
+        """counters of the term of the last estimate: dict(evals_geo, pixels_geo)"""
+        s = GeoStats()
+        self._chk(lib().hcmvs_get_geo_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in GeoStats._fields_}
 
     # ---- view spread (--n-viewspread, DepthMap.cpp:1504-1608) ----------------------------------------------
 

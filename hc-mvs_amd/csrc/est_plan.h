@@ -67,7 +67,10 @@ enum EstBad {
 	kEstBorder,     // item `at`: its reference image has no pixel inside the border
 	kEstPriorHint,  // item `at` has the `restore` hint in effect while an item of the batch has an active depth prior
 	kEstPriorSpread, // item `at` has view spread doing work while an item of the batch has an active depth prior
-	kEstSweepRange  // sweeps-only call: first_sweep < 0, n_sweeps < 1 or an index beyond HCMVS_MAX_SWEEP_INDEX
+	kEstSweepRange, // sweeps-only call: first_sweep < 0, n_sweeps < 1 or an index beyond HCMVS_MAX_SWEEP_INDEX
+	kEstGeoHint,    // item `at` has the `restore` hint in effect while the geometric-consistency term is active for an item of the batch
+	kEstGeoSpread,  // item `at` has view spread doing work while the term is active for an item of the batch
+	kEstGeoPrior    // item `at` has an active depth prior while the term is active for an item of the batch
 };
 struct EstCheck {
 	EstBad broken = kEstOk;
@@ -164,8 +167,8 @@ inline void est_spread_consts(const EstCamera& ref, const EstCamera& s, SpreadVi
 }
 
 // what plan_sweeps needs of an item whose constants and pointers are set
-inline SweepItem est_sweep_item(const EstConst& k, int nSweeps, bool prior = false) {
-	return {k.H - 2 * k.border, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == nSweeps - 1, k.keep != nullptr, k.spread != nullptr, prior};
+inline SweepItem est_sweep_item(const EstConst& k, int nSweeps, bool prior = false, bool geo = false) {
+	return {k.H - 2 * k.border, k.W - 2 * k.border, k.V, k.hintDepth && k.hintIter == nSweeps - 1, k.keep != nullptr, k.spread != nullptr, prior, geo};
 }
 
 // ---- the image window ----
@@ -234,6 +237,58 @@ inline EstCheck est_check_sweeps(int firstSweep, int nSweeps) {
 	return {};
 }
 
+// ---- geometric consistency ----
+// what hcmvs_set_geo_params refuses: a weight outside [0, 1] or not finite, a threshold that is not finite, max_px not finite and > 0,
+// photo2geo < 0
+enum GeoBad { kGeoOk = 0, kGeoWeight, kGeoThreshold, kGeoMaxPx, kGeoPhoto2geo };
+inline GeoBad est_check_geo_params(const hcmvs_geo_params& gp) {
+	if (!(gp.para_tapa >= 0.f && gp.para_tapa <= 1.f) || !(gp.para_tapa2 >= 0.f && gp.para_tapa2 <= 1.f)) return kGeoWeight; // (a NaN fails both comparisons)
+	if (!(fabsf(gp.txthreshold) < INFINITY) || !(fabsf(gp.txthreshold2) < INFINITY)) return kGeoThreshold;
+	if (!(gp.max_px > 0.f) || !(gp.max_px < INFINITY)) return kGeoMaxPx;
+	if (gp.photo2geo < 0) return kGeoPhoto2geo;
+	return kGeoOk;
+}
+// a source view offers maps to the term when it has some registered (hcmvs_set_spread_maps_device) and was not made by hcmvs_rescale_view
+inline bool est_geo_offers(bool offersMaps, bool rescaled) { return offersMaps && !rescaled; }
+// the activity rule: the switch is set, the outer iteration has reached photo2geo, and a source view of the item offers maps
+inline bool est_geo_active(const hcmvs_geo_params& gp, const hcmvs_params& p, bool anyViewOffers) {
+	return gp.on != 0 && p.it_external >= gp.photo2geo && anyViewOffers;
+}
+// The value members of source view s's entry (the map pointers are the caller's).  A point Xc of view j's camera lands in the reference
+// image at B Xc + b (homogeneous) with B = K_i R_i R_j^T and b = K_i R_i (C_j - C_i); a normal of view j's camera frame is Rr = R_i R_j^T
+// times it in the reference camera's.  Computed in double, rounded once.
+inline void est_geo_view(const EstCamera& ref, const EstCamera& s, GeoView& gv) {
+	gv.w = s.w; gv.h = s.h; gv.pad = 0;
+	gv.cx = (float)s.K[2]; gv.cy = (float)s.K[5]; gv.ifx = (float)(1.0 / s.K[0]); gv.ify = (float)(1.0 / s.K[4]);
+	double KR[9], B[9], Rr[9];
+	mat3_mul(ref.K, ref.R, KR);
+	mat3_mul_bt(KR, s.R, B);
+	mat3_mul_bt(ref.R, s.R, Rr);
+	const double dC[3] = {s.C[0] - ref.C[0], s.C[1] - ref.C[1], s.C[2] - ref.C[2]};
+	for (int i = 0; i < 9; ++i) { gv.B[i] = (float)B[i]; gv.Rr[i] = (float)Rr[i]; }
+	for (int i = 0; i < 3; ++i) gv.b[i] = (float)(KR[i * 3] * dC[0] + KR[i * 3 + 1] * dC[1] + KR[i * 3 + 2] * dC[2]);
+}
+// the term's constants of an item (GeoItem::views itself is the context's pointer).  countIter: as PriorItem::countIter
+inline void est_geo_consts(const hcmvs_geo_params& gp, int countIter, GeoItem& k) {
+	k.w1 = gp.para_tapa; k.w2 = gp.para_tapa2;
+	k.keep1 = 1.f - gp.para_tapa; k.keep2 = 1.f - gp.para_tapa2;
+	k.tx1 = gp.txthreshold; k.tx2 = gp.txthreshold2;
+	k.maxPx = gp.max_px;
+	k.countIter = countIter;
+}
+// Per item of a batch: has the term active, has the hint in effect, has view spread doing work, has an active depth prior.  A batch is
+// one set of launches, so the term active anywhere in it is refused together with any of the three anywhere in it; `at` is the first
+// item with the hint (or, failing that, with view spread, or, failing that, with a prior) that stands in the way.
+inline EstCheck est_check_geo_batch(const bool* geoActive, const bool* hintInEffect, const bool* spreadWork, const bool* priorActive, int nItems) {
+	bool any = false;
+	for (int i = 0; i < nItems; ++i) any = any || geoActive[i];
+	if (!any) return {};
+	for (int i = 0; i < nItems; ++i) if (hintInEffect[i]) return {kEstGeoHint, i};
+	for (int i = 0; i < nItems; ++i) if (spreadWork[i]) return {kEstGeoSpread, i};
+	for (int i = 0; i < nItems; ++i) if (priorActive[i]) return {kEstGeoPrior, i};
+	return {};
+}
+
 // ---- view spread: a launch must not read what it writes ----
 // The in/out maps of no item may share a byte with the spread maps of a source view of any item (depth and conf: 4 bytes per pixel,
 // normal: 12).  k, spread ([nItems][kMaxViews]) and items describe the batch as it is about to be launched; the first offender in
@@ -259,6 +314,27 @@ inline EstOverlap est_spread_overlap(const EstConst* k, const SpreadView* spread
 				const size_t spn[3] = {m * 4, m * 12, m * 4};
 				for (int a = 0; a < 3; ++a)
 					for (int b = 0; b < 3; ++b)
+						if (est_ranges_overlap(io[a], ion[a], sp[b], spn[b])) return {i, j, v};
+			}
+	}
+	return {};
+}
+// the same rule for the maps the geometric-consistency term reads (depth and normal): geo is [nItems][kMaxViews], active[j] tells
+// whether item j's term is active
+inline EstOverlap est_geo_overlap(const EstConst* k, const GeoView* geo, const bool* active, const hcmvs_batch_item* items, int nItems) {
+	for (int i = 0; i < nItems; ++i) {
+		const size_t n = (size_t)k[i].W * k[i].H;
+		const void* io[3] = {items[i].d_depth, items[i].d_normal, items[i].d_conf};
+		const size_t ion[3] = {n * 4, n * 12, n * 4};
+		for (int j = 0; j < nItems; ++j)
+			for (int v = 0; v < items[j].n_src; ++v) {
+				const GeoView& gv = geo[(size_t)j * kMaxViews + v];
+				if (!active[j] || !gv.depth) continue;
+				const size_t m = (size_t)gv.w * gv.h;
+				const void* sp[2] = {gv.depth, gv.normal};
+				const size_t spn[2] = {m * 4, m * 12};
+				for (int a = 0; a < 3; ++a)
+					for (int b = 0; b < 2; ++b)
 						if (est_ranges_overlap(io[a], ion[a], sp[b], spn[b])) return {i, j, v};
 			}
 	}

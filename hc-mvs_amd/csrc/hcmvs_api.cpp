@@ -100,6 +100,10 @@ struct hcmvs_ctx final : Reclaimer {
 	bool haveSpreadStats = false;         // the last estimate ran with view spread in effect
 	hcmvs_prior_params prior = {0.5f, 0.2f, 2}; // hcmvs_set_prior_params (the reference's defaults)
 	bool havePriorStats = false;          // the last estimate had an item with an active prior
+	hcmvs_geo_params geo = {0, 0.25f, 0.15f, 150.f, 160.f, 2, 3.f}; // hcmvs_set_geo_params (hcmvs_default_geo_params)
+	bool haveGeoStats = false;            // the last estimate had an item with the geometric-consistency term active
+	DevBuf dGeo{this};                    // GeoView [kMaxBatch][kMaxViews]
+	std::vector<GeoView> hGeo;
 	DevBuf sync{this};                    // int32_t: [0] unused, [1] error word, [16 .. 16 + kMaxBatch) row tickets of the batch items, then kMaxBatch rows-done counters
 	SweepKnobs knobs;                     // the HCMVS_* tuning knobs of the environment (sweep_plan.h)
 	DevBuf evals{this};                   // unsigned long long [16]: SweepSync::evals
@@ -223,8 +227,10 @@ int hcmvs_create(int device, hcmvs_ctx** out) {
 	for (Event& e : c->ev)
 		if (e.ensure() != hipSuccess) { hcmvs_destroy(c); return HCMVS_ERR_NO_DEVICE; }
 	c->hViews.resize((size_t)kMaxBatch * kViewSlotEntries); c->hItems.resize(kMaxBatch); c->hSpread.resize((size_t)kMaxBatch * kMaxViews);
+	c->hGeo.resize((size_t)kMaxBatch * kMaxViews);
 	if (c->dViews.reserve(sizeof(DevView) * kViewSlotEntries * kMaxBatch, c->stream) != hipSuccess || c->evals.reserve(128, c->stream) != hipSuccess ||
 	    c->dSpread.reserve(sizeof(SpreadView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess ||
+	    c->dGeo.reserve(sizeof(GeoView) * kMaxViews * kMaxBatch, c->stream) != hipSuccess ||
 	    c->dItems.reserve(sizeof(EstConst) * kMaxBatch, c->stream) != hipSuccess || c->sync.reserve(64 + sizeof(int32_t) * 2 * kMaxBatch, c->stream) != hipSuccess) {
 		hcmvs_destroy(c);
 		return HCMVS_ERR_NO_DEVICE;
@@ -527,6 +533,15 @@ static int refuse_estimate(hcmvs_ctx* c, EstCheck bad, const hcmvs_batch_item* i
 	case kEstSweepRange:
 		return fail(c, HCMVS_ERR_INVALID, "estimate_sweeps: first_sweep >= 0, n_sweeps >= 1 and a last index <= %d are needed (the random stream of a sweep "
 		            "is it_external * 64 + 1 + index)", HCMVS_MAX_SWEEP_INDEX);
+	case kEstGeoHint:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: item %d (view %u) offers the `restore` hint in its last outer iteration while the geometric-consistency "
+		            "term is active for an item of the batch: the term is not combined with the hint (remove one of the two)", bad.at, items[bad.at].ref_id);
+	case kEstGeoSpread:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: view spread has maps to try for item %d (view %u) while the geometric-consistency term is active for an "
+		            "item of the batch: the term is not combined with view spread (hcmvs_set_viewspread(ctx, 0))", bad.at, items[bad.at].ref_id);
+	case kEstGeoPrior:
+		return fail(c, HCMVS_ERR_INVALID, "estimate: item %d (view %u) has an active depth prior while the geometric-consistency term is active for an item of "
+		            "the batch: the two terms are not combined (remove the prior, or switch the term off)", bad.at, items[bad.at].ref_id);
 	}
 	return HCMVS_ERR_INVALID;
 }
@@ -599,6 +614,21 @@ static int build_item(hcmvs_ctx* c, int slot, const hcmvs_batch_item* items, int
 		pi.prior = ref.prior;
 		est_prior_consts(c->prior, sweepsOnly ? firstSweep : -1, pi); // (no init-score pass: the call's first sweep counts the pixels with a usable prior)
 	}
+	GeoItem& gi = *geo_item(hv); // behind the PriorItem
+	memset(&gi, 0, sizeof gi);
+	GeoView* hg = c->hGeo.data() + (size_t)slot * kMaxViews;
+	memset(hg, 0, sizeof(GeoView) * kMaxViews);
+	bool offers = false;
+	for (int v = 0; v < n_src; ++v) offers = offers || est_geo_offers(src[v]->sDepth != nullptr, src[v]->rescaled);
+	if (est_geo_active(c->geo, *p, offers)) {
+		for (int v = 0; v < n_src; ++v) {
+			const View& s = *src[v];
+			est_geo_view(camera_of(ref), cam[v], hg[v]);
+			if (est_geo_offers(s.sDepth != nullptr, s.rescaled)) { hg[v].depth = s.sDepth; hg[v].normal = s.sNormal; }
+		}
+		gi.views = c->dGeo.get<GeoView>() + (size_t)slot * kMaxViews;
+		est_geo_consts(c->geo, sweepsOnly ? firstSweep : -1, gi);
+	}
 	return HCMVS_OK;
 }
 
@@ -629,10 +659,24 @@ static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n
 		}
 		rc = refuse_estimate(c, est_check_prior_batch(priorActive, hintInEffect, spreadWork, n_items), items, n_items, p);
 		if (rc) return rc;
+		// the geometric-consistency term active anywhere in the batch: refused together with a hint, view spread at work or an active prior
+		std::vector<char> gflags((size_t)n_items, 0);
+		bool* geoActive = (bool*)gflags.data();
+		for (int i = 0; i < n_items; ++i) {
+			const hcmvs_batch_item& it = items[i];
+			bool offers = false;
+			for (int v = 0; it.src_ids && v < it.n_src && v < kMaxViews; ++v) {
+				auto sv = c->views.find(it.src_ids[v]);
+				if (sv != c->views.end() && est_geo_offers(sv->second.sDepth != nullptr, sv->second.rescaled)) offers = true;
+			}
+			geoActive[i] = est_geo_active(c->geo, *p, offers);
+		}
+		rc = refuse_estimate(c, est_check_geo_batch(geoActive, hintInEffect, spreadWork, priorActive, n_items), items, n_items, p);
+		if (rc) return rc;
 	}
 	HIPCHK(c, hipSetDevice(c->device));
 	int maxRows = 0;
-	bool spread = false, prior = false;
+	bool spread = false, prior = false, geo = false;
 	hcmvs::SweepBatch batch;
 	batch.big = p->adapthalfwin > kHalfWindow; batch.nSweeps = nSweeps; batch.firstSweep = firstSweep; batch.nCU = c->nCU;
 	batch.sweepPerLaunch = c->knobs.perLaunch; batch.sweepSegment = c->knobs.segment; batch.wavesPerRow = c->knobs.wavesPerRow;
@@ -642,10 +686,12 @@ static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n
 		if (rc) return rc;
 		const EstConst& k = c->hItems[i];
 		const bool itemPrior = prior_item(c->hViews.data() + (size_t)i * kViewSlotEntries)->prior != nullptr;
-		batch.items.push_back(est_sweep_item(k, batch.nSweeps, itemPrior));
+		const bool itemGeo = geo_item(c->hViews.data() + (size_t)i * kViewSlotEntries)->views != nullptr;
+		batch.items.push_back(est_sweep_item(k, batch.nSweeps, itemPrior, itemGeo));
 		maxRows = std::max(maxRows, batch.items.back().rows);
 		spread = spread || k.spread;
 		prior = prior || itemPrior;
+		geo = geo || itemGeo;
 	}
 	if (spread) { // a launch must not read what it writes
 		const EstOverlap o = est_spread_overlap(c->hItems.data(), c->hSpread.data(), items, n_items);
@@ -654,8 +700,19 @@ static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n
 			            "a launch must not read what it writes (register a copy, or estimate the two images in separate calls)", o.item, items[o.item].ref_id,
 			            items[o.other].src_ids[o.view], o.other);
 	}
+	if (geo) { // the same rule for the maps the geometric-consistency term reads
+		std::vector<char> act((size_t)n_items, 0);
+		for (int i = 0; i < n_items; ++i) act[i] = batch.items[i].geo;
+		const EstOverlap o = est_geo_overlap(c->hItems.data(), c->hGeo.data(), (const bool*)act.data(), items, n_items);
+		if (o.item >= 0)
+			return fail(c, HCMVS_ERR_INVALID, "estimate: the in/out maps of item %d (view %u) overlap the maps source view %u of item %d offers to the "
+			            "geometric-consistency term: a launch must not read what it writes (register a copy, or estimate the two images in separate calls)",
+			            o.item, items[o.item].ref_id, items[o.other].src_ids[o.view], o.other);
+	}
 	hipStream_t s = c->stream;
 	// same stream => the previous call's kernels are done with these tables before the copies land
+	if (geo) HIPCHK(c, hipMemcpyAsync(c->dGeo.get(), c->hGeo.data(), sizeof(GeoView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
+	c->haveGeoStats = geo;
 	if (spread) HIPCHK(c, hipMemcpyAsync(c->dSpread.get(), c->hSpread.data(), sizeof(SpreadView) * kMaxViews * n_items, hipMemcpyHostToDevice, s));
 	c->haveSpreadStats = spread;
 	c->havePriorStats = prior;
@@ -676,7 +733,7 @@ static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n
 			launch_median3(items[i].d_depth, c->slots[i].tmpDepth.get<float>(), k.W, k.H, s);
 			depthIn = c->slots[i].tmpDepth.get<float>();
 		}
-		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s, batch.items[i].prior);
+		launch_score_pass(k, depthIn, items[i].d_normal, c->evals.get<unsigned long long>(), s, batch.items[i].prior, batch.items[i].geo);
 	}
 	HIPCHK(c, hipEventRecord(c->ev[1].get(), s));
 	int32_t* sync = c->sync.get<int32_t>();
@@ -687,8 +744,8 @@ static int estimate_batch(hcmvs_ctx* c, const hcmvs_batch_item* items, int32_t n
 		for (int i = 0; i < n_items; ++i)
 			HIPCHK(c, hipMemsetAsync(c->slots[i].progress.get(), 0, (size_t)batch.items[i].rows * kProgressStride * sizeof(int32_t), s));
 		if (!launch_sweep(sa, l, s))
-			return fail(c, HCMVS_ERR_INVALID, "estimate: no sweep kernel for %d waves per row, big %d two %d pack %d hint %d mask %d spread %d prior %d",
-			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread, l.v.prior);
+			return fail(c, HCMVS_ERR_INVALID, "estimate: no sweep kernel for %d waves per row, big %d two %d pack %d hint %d mask %d spread %d prior %d geo %d",
+			            l.v.nw, l.v.big, l.v.two, l.v.pack, l.v.hint, l.v.mask, l.v.spread, l.v.prior, l.v.geo);
 	}
 	c->lastSweepLaunches = (int)plan.size();
 	HIPCHK(c, hipEventRecord(c->ev[2].get(), s));
@@ -793,6 +850,39 @@ int hcmvs_get_prior_stats(hcmvs_ctx* c, hcmvs_prior_stats* out) {
 	unsigned long long ev[2];
 	HIPCHK(c, hipMemcpy(ev, c->evals.get<unsigned long long>() + 8, sizeof ev, hipMemcpyDeviceToHost));
 	out->evals_prior = ev[0]; out->pixels_prior = ev[1];
+	return HCMVS_OK;
+}
+
+// ---- geometric consistency ----
+
+void hcmvs_default_geo_params(hcmvs_geo_params* p) {
+	if (!p) return;
+	p->on = 0; p->para_tapa = 0.25f; p->para_tapa2 = 0.15f; p->txthreshold = 150.f; p->txthreshold2 = 160.f; // DensifyPointCloud.cpp:176-181
+	p->photo2geo = 2; p->max_px = 3.f;
+}
+int hcmvs_set_geo_params(hcmvs_ctx* c, const hcmvs_geo_params* p) {
+	if (!c) return HCMVS_ERR_INVALID;
+	if (!p) return fail(c, HCMVS_ERR_INVALID, "set_geo_params: null argument");
+	switch (est_check_geo_params(*p)) {
+	case kGeoOk: break;
+	case kGeoWeight: return fail(c, HCMVS_ERR_INVALID, "set_geo_params: para_tapa %g and para_tapa2 %g must lie in [0, 1]", (double)p->para_tapa, (double)p->para_tapa2);
+	case kGeoThreshold: return fail(c, HCMVS_ERR_INVALID, "set_geo_params: txthreshold %g and txthreshold2 %g must be finite", (double)p->txthreshold, (double)p->txthreshold2);
+	case kGeoMaxPx: return fail(c, HCMVS_ERR_INVALID, "set_geo_params: max_px %g is not a finite number > 0", (double)p->max_px);
+	case kGeoPhoto2geo: return fail(c, HCMVS_ERR_INVALID, "set_geo_params: photo2geo %d is negative", p->photo2geo);
+	}
+	c->geo = *p;
+	return HCMVS_OK;
+}
+int hcmvs_get_geo_stats(hcmvs_ctx* c, hcmvs_geo_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	memset(out, 0, sizeof *out);
+	if (!c->haveStats) return fail(c, HCMVS_ERR_INVALID, "get_geo_stats: no estimate has run");
+	if (!c->haveGeoStats) return HCMVS_OK; // the term was active for no item of the last estimate: all zero
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	unsigned long long ev[2];
+	HIPCHK(c, hipMemcpy(ev, c->evals.get<unsigned long long>() + 10, sizeof ev, hipMemcpyDeviceToHost));
+	out->evals_geo = ev[0]; out->pixels_geo = ev[1];
 	return HCMVS_OK;
 }
 

@@ -19,7 +19,8 @@ struct SweepSync {
 	int32_t* error;    // set non-zero when a worker times out
 	unsigned long long* evals;  // [0] ScorePixel calls of the sequential algorithm, [1] evaluations issued (incl. speculative), [2] patch taps of [0],
 	                            // [4 .. 8) view spread: slots scored, slots accepted, slots dropped (depth <= 0), candidates outside the view's map,
-	                            // [8 .. 10) depth prior: evaluations that blended the term, pixels with a usable prior
+	                            // [8 .. 10) depth prior: evaluations that blended the term, pixels with a usable prior,
+	                            // [10 .. 12) geometric consistency: evaluations that blended the term, pixels with a weight
 };
 
 // what all sweep launches of one call share
@@ -38,8 +39,9 @@ void launch_median3(const float* in, float* out, int W, int H, hipStream_t s);
 void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, hipStream_t s); // DepthData::ApplyIgnoreMask
 void launch_quads(const float* gray, float4* out, int W, int H, hipStream_t s); // 2 x 2 footprint layout of a source view
 // prior: the item has an active depth prior (the PriorItem behind c.views is set): the PRIOR instance of the score kernel
+// geo: the item has the geometric-consistency term active (the GeoItem behind it is set): the GEO instance (never together with prior)
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
-                       hipStream_t s, bool prior = false);
+                       hipStream_t s, bool prior = false, bool geo = false);
 // the sweeps-only entry: the working state from maps that hold depth, normal and conf = the score; nothing is scored
 void launch_import_state(const EstConst& c, const float* depthIn, const float* normalIn, const float* confIn, hipStream_t s);
 bool launch_sweep(const SweepArgs& a, const SweepLaunch& l, hipStream_t s); // false: the library holds no instance l.v (nothing is launched)

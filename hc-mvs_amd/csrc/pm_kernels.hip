@@ -698,14 +698,87 @@ __device__ __forceinline__ PriorConst prior_const(const EstConst& c) {
 // the validity rule of a prior value: finite and > 0; everything else -- 0, negative, NaN, infinite -- is "no prior here"
 __device__ __forceinline__ bool prior_usable(float prior) { return prior > 0.f && prior < __builtin_huge_valf(); }
 
+// ---- geometric consistency: a per-(hypothesis, source view) reprojection term ----
+// what a GEO instance holds of its item's GeoItem while it works on the item (wave-uniform: scalar registers)
+struct GeoConst {
+	const GeoView* views; // null: the term is not active for the item
+	float w1, w2, keep1, keep2, tx1, tx2, maxPx;
+	int countIter;
+};
+__device__ __forceinline__ GeoConst geo_const(const EstConst& c) {
+	const HC_GLOBAL GeoItem* gi = (const HC_GLOBAL GeoItem*)(const HC_GLOBAL void*)((const HC_GLOBAL char*)(as_global(c.views) + kMaxViews) + sizeof(PriorItem));
+	return {gi->views, gi->w1, gi->w2, gi->keep1, gi->keep2, gi->tx1, gi->tx2, gi->maxPx, gi->countIter};
+}
+// the term of one pixel, uniform over the wave: w <= 0 -- the item's term is not active, or the pixel's texture leaves it no weight --
+// is a plain pixel
+struct GeoPix {
+	const GeoView* views;
+	float w, keep, maxPx; // the pixel's weight (DepthMap.cpp:917-928), 1 - w, the truncation
+	float px, py;         // the pixel
+};
+__device__ __forceinline__ GeoPix geo_pix(const GeoConst& gc, uint8_t gra, int x, int y) {
+	const float g = (float)gra;
+	const bool lo = g < gc.tx1, mid = g < gc.tx2;
+	const float w = gc.views ? (lo ? gc.w1 : (mid ? gc.w2 : 0.f)) : 0.f;
+	return {gc.views, w, lo ? gc.keep1 : gc.keep2, gc.maxPx, (float)x, (float)y};
+}
+// steps 1-2 of D14 for the pair whose homography is H and whose source view is j (a lane's own): where the centre pixel lands in view j,
+// and the gathers of view j's depth and normal there.  z == 0: the pair is neutral (no maps, outside the map; a depth that is not usable
+// is kept as it is and tested in geo_finish).  The loads are plain gathers of maps no launch writes (the aliasing refusal of the estimate).
+struct GeoTap { float x1x, x1y, z, N0, N1, N2; };
+__device__ __forceinline__ GeoTap geo_gather(const GeoPix& gp, int j, bool exists, const float (&H)[9]) {
+	const HC_GLOBAL GeoView* gv = as_global(gp.views) + (exists ? j : 0);
+	gcfptr dep = (gcfptr)gv->depth;
+	gcfptr nrm = (gcfptr)gv->normal;
+	const int gw = gv->w, gh = gv->h;
+	const float Xx = fmaf(H[1], gp.py, fmaf(H[0], gp.px, H[2]));
+	const float Xy = fmaf(H[4], gp.py, fmaf(H[3], gp.px, H[5]));
+	const float Xz = fmaf(H[7], gp.py, fmaf(H[6], gp.px, H[8]));
+	const float iz = 1.0f / Xz;
+	GeoTap t;
+	t.x1x = Xx * iz; t.x1y = Xy * iz;
+	const float fu = floorf(t.x1x + 0.5f), fv = floorf(t.x1y + 0.5f);
+	const bool in = exists && dep && fu >= 0.f && fv >= 0.f && fu < (float)gw && fv < (float)gh; // false for a NaN
+	const size_t at = in ? (size_t)(int)fv * (size_t)gw + (size_t)(int)fu : 0;
+	t.z = 0.f; t.N0 = t.N1 = t.N2 = 0.f;
+	if (in) { t.z = dep[at]; t.N0 = nrm[3 * at]; t.N1 = nrm[3 * at + 1]; t.N2 = nrm[3 * at + 2]; }
+	return t;
+}
+// steps 2-5 of D14: the pair's geo value from what geo_gather left, for the hypothesis' normal (n0, n1, n2).  All float; the fused
+// operations are the ones spelled out; the divisions and square roots are IEEE.
+__device__ __forceinline__ float geo_finish(const GeoPix& gp, int j, bool exists, const GeoTap& t, float n0, float n1, float n2) {
+	if (!(t.z > 0.f && t.z < __builtin_huge_valf())) return 1.f; // D11's validity rule: finite and > 0
+	const HC_GLOBAL GeoView* gv = as_global(gp.views) + (exists ? j : 0);
+	const float Xc0 = ((t.x1x - gv->cx) * t.z) * gv->ifx, Xc1 = ((t.x1y - gv->cy) * t.z) * gv->ify;
+	float p[3], m[3];
+#pragma unroll
+	for (int i = 0; i < 3; ++i) {
+		p[i] = fmaf(gv->B[3 * i + 2], t.z, fmaf(gv->B[3 * i + 1], Xc1, fmaf(gv->B[3 * i], Xc0, gv->b[i])));
+		m[i] = fmaf(gv->Rr[3 * i + 2], t.N2, fmaf(gv->Rr[3 * i + 1], t.N1, gv->Rr[3 * i] * t.N0));
+	}
+	if (!(p[2] > 0.f)) return 1.f;
+	const float ip = 1.0f / p[2];
+	const float ex = gp.px - p[0] * ip, ey = gp.py - p[1] * ip;
+	const float e = sqrtf(fmaf(ey, ey, ex * ex));
+	const float nn = fmaf(n2, n2, fmaf(n1, n1, n0 * n0)), mm = fmaf(m[2], m[2], fmaf(m[1], m[1], m[0] * m[0]));
+	const float q = nn * mm;
+	if (!(q > 0.f)) return 1.f;
+	const float dt = fmaf(n2, m[2], fmaf(n1, m[1], n0 * m[0]));
+	const float cs = fminf(1.f, fabsf(dt) / sqrtf(q));
+	return e < gp.maxPx ? e / gp.maxPx + (1.f - cs) : 2.f;
+}
+
 // DepthMap.cpp:597-615, 890-893: score of one view from its ZNCC sums, times the smoothness factor of the hypothesis
+// GEO: where the pixel has a weight (gw > 0, uniform over the wave), the view's score is blended with the pair's geo value as
+// s * (1 - w) + w * geo, two multiplications and an addition, unfused, at the place of the PRIOR blend (D14, step 6)
 // PRIOR: where the pixel carries a usable prior (pkeep >= 0: it is 1 - para_prior then, uniform over the wave, and -1 otherwise), the
 // view's score is blended with the hypothesis' addend (prior_addend) as s * (1 - para_prior) + addend, a multiplication and an addition,
 // unfused -- after the photometric scale and before the thRobust override, so that a failed view stays thRobust unblended
 // (DepthMap.cpp:558, 591)
-template <bool PRIOR = false>
+template <bool PRIOR = false, bool GEO = false>
 __device__ __forceinline__ float view_score(const EstConst& c, float sum, float sumSq, float num, bool viewBad, float invSumW,
-                                            float normSq0, float smoothF, float padd = 0.f, float pkeep = -1.f) {
+                                            float normSq0, float smoothF, float padd = 0.f, float pkeep = -1.f, float gw = 0.f, float gkeep = 1.f,
+                                            float geo = 0.f) {
 	const float normSq1 = sumSq - HC_SQ(sum) * invSumW;
 	const float nrmSq = normSq0 * normSq1;
 	float ncc = num / sqrtf(nrmSq);
@@ -713,6 +786,7 @@ __device__ __forceinline__ float view_score(const EstConst& c, float sum, float 
 	float s = (1.f - ncc) * smoothF;
 	s = c.pfScale * s;
 	if constexpr (PRIOR) { if (pkeep >= 0.f) s = s * pkeep + padd; }
+	if constexpr (GEO) { if (gw > 0.f) s = s * gkeep + gw * geo; }
 	if (viewBad || !(nrmSq > 0.f)) s = c.thRobust;
 	return s;
 }
@@ -730,13 +804,16 @@ __device__ __forceinline__ void min2_merge(float& a1, float& a2, float b1, float
 
 // one hypothesis, everything in one go (init-score pass): the two best view scores of the views of L's set are merged into
 // (r1, r2); two_best() of those is the pixel's score (an estimate with 9..16 source views runs a second set of eight)
-template <int S, bool BIG, class ST, bool PRIOR = false>
+// GEO: every lane of a view group holds the group's pair: it issues the pair's gathers before the taps and finishes geo after them
+template <int S, bool BIG, class ST, bool PRIOR = false, bool GEO = false>
 __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>& L, const Patch<S>& P, const ST& st, float v0, float v1,
                                             float smoothF, float depth, float n0, float n1, float n2, float& r1, float& r2,
-                                            float padd = 0.f, float pkeep = -1.f) {
+                                            float padd = 0.f, float pkeep = -1.f, const GeoPix& gp = GeoPix{nullptr, 0.f, 1.f, 1.f, 0.f, 0.f}) {
 	float vA[9], vHm[3], H[9];
 	st.get_view(vA, vHm);
 	make_homography(c, vA, vHm, v0, v1, depth, n0, n1, n2, H);
+	GeoTap gt = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+	if constexpr (GEO) { if (gp.w > 0.f) gt = geo_gather(gp, L.view, L.vact, H); }
 	float sum, sumSq, num;
 	bool viewBad;
 	if (BIG && P.a > kHalfWindow) {
@@ -746,7 +823,9 @@ __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>&
 		else if (P.a == 5) score_taps<S, 6>(c, L, P, st, H, sum, sumSq, num, viewBad);
 		else score_taps<S, 8>(c, L, P, st, H, sum, sumSq, num, viewBad);
 	}
-	const float s = view_score<PRIOR>(c, sum, sumSq, num, viewBad, P.invSumW, P.normSq0, smoothF, padd, pkeep);
+	float geo = 0.f;
+	if constexpr (GEO) { if (gp.w > 0.f) geo = geo_finish(gp, L.view, L.vact, gt, n0, n1, n2); }
+	const float s = view_score<PRIOR, GEO>(c, sum, sumSq, num, viewBad, P.invSumW, P.normSq0, smoothF, padd, pkeep, gp.w, gp.keep, geo);
 	float m1 = L.vact ? s : __builtin_huge_valf(), m2 = __builtin_huge_valf();
 	min2_across<S>(m1, m2);
 	min2_merge(r1, r2, m1, m2);
@@ -761,10 +840,14 @@ __device__ __forceinline__ void score_pixel(const EstConst& c, const LaneCtx<S>&
 // hypothesis t merged into (r1, r2); two_best() of those is the hypothesis' score.  L selects the view set (views
 // L.view - L.vloc ... + 7): an estimate with 9..16 source views calls this twice per chunk.
 // PRIOR: PA holds the prior addend of hypothesis t in lane t (prior_addend), pkeep is 1 - para_prior where the pixel's prior is usable, else -1
-template <int S, bool BIG, bool PACK = false, bool PRIOR = false>
+// GEO: where the pixel has a weight (gp.w > 0), the lane that holds a pair's homography in (1) issues the pair's depth and normal gathers
+// there -- their latency rides under the tap sums of (2) -- parks where the centre pixel landed beside the homography, and finishes the
+// pair's geo value in (3), where the same lane holds the pair again
+template <int S, bool BIG, bool PACK = false, bool PRIOR = false, bool GEO = false>
 __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>& L, const Patch<S>& P, const LdsStore<S>& st, float v0, float v1,
                                             float F, float hd, float h0, float h1, float h2, unsigned long long todoIn, int baseIn,
-                                            int fallbackIn, float& r1, float& r2, unsigned& issued, float PA = 0.f, float pkeep = -1.f) {
+                                            int fallbackIn, float& r1, float& r2, unsigned& issued, float PA = 0.f, float pkeep = -1.f,
+                                            const GeoPix& gp = GeoPix{nullptr, 0.f, 1.f, 1.f, 0.f, 0.f}) {
 	// the list of hypotheses is the same in every lane: keep it (and the loop over it) on the scalar unit
 	const unsigned long long todo = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(todoIn >> 32)) << 32) |
 	                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)todoIn);
@@ -781,6 +864,8 @@ __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>&
 		vA[0] = a.x; vA[1] = a.y; vA[2] = a.z; vA[3] = a.w; vA[4] = b.x; vA[5] = b.y; vA[6] = b.z; vA[7] = b.w; vA[8] = cc.x;
 		vHm[0] = cc.y; vHm[1] = cc.z; vHm[2] = cc.w;
 	}
+	static_assert(!GEO || HP == 8, "GEO: one pair-pass, so that a lane holds the same pair in (1) and in (3)");
+	GeoTap gt = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
 	for (int p0 = 0; p0 < 8; p0 += HP) {
 		if ((todo >> (base + p0)) == 0ull) break;
@@ -790,9 +875,10 @@ __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>&
 		if (pg < HP) {
 			float H[9];
 			make_homography(c, vA, vHm, v0, v1, gd, g0, g1, g2, H);
+			if constexpr (GEO) { if (gp.w > 0.f) gt = geo_gather(gp, vbase + pv, vbase + pv < c.V, H); }
 			pk->hl[g][pv][0] = make_float4(H[0], H[1], H[2], H[3]);
 			pk->hl[g][pv][1] = make_float4(H[4], H[5], H[6], H[7]);
-			pk->hl[g][pv][2] = make_float4(H[8], 0.f, 0.f, 0.f);
+			pk->hl[g][pv][2] = make_float4(H[8], gt.x1x, gt.x1y, 0.f);
 		}
 	}
 	// views of this set that exist: with fewer than eight, the idle view groups take (hypothesis, view) pairs of their own --
@@ -878,7 +964,15 @@ __device__ __forceinline__ void score_chunk(const EstConst& c, const LaneCtx<S>&
 		const float Fg = __shfl(F, g * 8, 64);
 		float pag = 0.f;
 		if constexpr (PRIOR) pag = __shfl(PA, ((todo >> (base + g)) & 1ull) ? base + g : fallback, 64); // the pair's hypothesis, as in (1)
-		const float s = view_score<PRIOR>(c, rs[0], rs[1], rs[2], false, P.invSumW, P.normSq0, Fg, pag, pkeep);
+		float geo = 0.f;
+		if constexpr (GEO) { if (gp.w > 0.f) { // the pair's hypothesis, as in (1); where the centre pixel landed comes back from beside the homography
+			const int src = ((todo >> (base + g)) & 1ull) ? base + g : fallback;
+			const float g0 = __shfl(h0, src, 64), g1 = __shfl(h1, src, 64), g2 = __shfl(h2, src, 64);
+			const float4 cc = pk->hl[g][pv][2];
+			gt.x1x = cc.y; gt.x1y = cc.z;
+			geo = geo_finish(gp, vbase + pv, vbase + pv < c.V, gt, g0, g1, g2);
+		} }
+		const float s = view_score<PRIOR, GEO>(c, rs[0], rs[1], rs[2], false, P.invSumW, P.normSq0, Fg, pag, pkeep, gp.w, gp.keep, geo);
 		float m1 = vbase + pv < c.V ? s : __builtin_huge_valf(), m2 = __builtin_huge_valf();
 		min2_group<NV>(m1, m2);
 		// hypothesis base + p0 + k sits in lanes k * NV ... of (m1, m2)
@@ -1162,11 +1256,14 @@ struct SpreadCount { unsigned scored, accepted, dropped, outside; };
 // PRIOR: some item of the launch has an active depth prior (PriorItem, pc); `prior` is this pixel's usable prior value, 0 where it
 // has none -- every evaluation of the pixel then blends the prior term (view_score); every other launch runs the instance without
 // that code.  A PRIOR instance has neither the hint nor view spread (sweep_variant_exists).
-template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT, bool SPREAD, bool PRIOR = false>
+// GEO: some item of the launch has the geometric-consistency term active (GeoItem); gp is this pixel's weight and what the pairs need
+// (gp.w <= 0: a plain pixel).  A GEO instance has neither the hint, nor view spread, nor the prior (sweep_variant_exists).
+template <int S, int NW, bool BIG, bool TWO, bool PACK, bool HINT, bool SPREAD, bool PRIOR = false, bool GEO = false>
 __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S>& L, const LaneCtx<S>& L1, RowShared<NW>& sh, int& par, int wv,
                                               int x, int y, int q, int iter, const PixIn<S>& in, const Patch<S>& P,
-                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued, SpreadCount& spc, const PriorConst& pc, float prior STAMP_ARGS) {
+                                              const LdsStore<S>& st, RowPipe<S>& pp, unsigned& evals, unsigned& issued, SpreadCount& spc, const PriorConst& pc, float prior, const GeoPix& gp STAMP_ARGS) {
 	static_assert(!PRIOR || !(HINT || SPREAD), "the prior term comes without the hint and without view spread");
+	static_assert(!GEO || !(HINT || SPREAD || PRIOR), "the geometric-consistency term comes without the hint, view spread and the prior");
 	const int W = c.W, lane = L.lane;
 	PixelGeom G;
 	pixel_geom(c, x, y, G);
@@ -1323,10 +1420,10 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 			STAMP(4)
 			if (todo) {
 				BLOCK(blk_score_chunk, 5)
-				score_chunk<S, BIG, PACK, PRIOR>(c, L, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, issued, PA, pkeep);
+				score_chunk<S, BIG, PACK, PRIOR, GEO>(c, L, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, issued, PA, pkeep, gp);
 				if constexpr (TWO) {
 					unsigned again = 0;
-					score_chunk<S, BIG, PACK, PRIOR>(c, L1, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, again, PA, pkeep);
+					score_chunk<S, BIG, PACK, PRIOR, GEO>(c, L1, P, st, G.v0, G.v1, F, hd, h0, h1, h2, todo, base, __builtin_ctzll(todo), best1, best2, again, PA, pkeep, gp);
 				}
 			}
 		}
@@ -1534,7 +1631,8 @@ __device__ __forceinline__ void process_pixel(const EstConst& c, const LaneCtx<S
 // MASK: some item of the batch has a keep-mask (--ignore-mask-label); every other launch runs the instance without that code
 // SPREAD: the call has view spread on and some source view of the batch offers maps (EstConst::spread of some item is set)
 // PRIOR: some item of the batch has an active depth prior (PriorItem::prior of some item is set)
-template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false, bool SPREAD = false, bool PRIOR = false>
+// GEO: some item of the batch has the geometric-consistency term active (GeoItem::views of some item is set)
+template <int S, int NW, bool BIG, bool TWO = false, bool PACK = false, bool HINT = false, bool MASK = false, bool SPREAD = false, bool PRIOR = false, bool GEO = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? HCMVS_OCC : 1, !BIG ? HCMVS_OCC : 2))) void sweep_kernel(const EstConst* __restrict__ items, int nItems, int maxRows, SweepSync sy,
                                                         int iter0, int nSweeps, int lag, int affinity, int segLen) {
 	__shared__ RowShared<NW> sh;
@@ -1544,6 +1642,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 	unsigned evals = 0, issued = 0;
 	unsigned long long taps = 0; // patch taps of the sequential algorithm's evaluations (per source view)
 	SpreadCount spc = {0u, 0u, 0u, 0u};
+	// GEO: the pixel's term (set per pixel).  Declared out here: a local of the pixel loop costs the other instances their code (the
+	// lifetime markers of one more object change how the loop's tail is if-converted, and with it seven PRIOR instances' spills)
+	GeoPix gp = {nullptr, 0.f, 1.f, 1.f, 0.f, 0.f};
+	unsigned evalsGeo = 0, pixelsGeo = 0; // GEO: evaluations that blended the term; pixels with a weight (counted in one sweep)
 	unsigned evalsPrior = 0, pixelsPrior = 0; // PRIOR: evaluations that blended the term; pixels with a usable prior (counted in one sweep)
 	int par = 0, rot = (int)blockIdx.x;
 	STAMP_DECL
@@ -1649,6 +1751,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 		}
 		PriorConst pc = {nullptr, 0.f, 0.f, 0.f, -1};
 		if constexpr (PRIOR) pc = prior_const(c);
+		GeoConst gc = {nullptr, 0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 1.f, -1};
+		if constexpr (GEO) gc = geo_const(c);
 		const int y = rev ? c.H - 1 - bd - r : bd + r;
 		pp.r = r; pp.y = y;
 		pp.upWord = as_global(c.progress) + (size_t)(r > 0 ? r - 1 : 0) * kProgressStride;
@@ -1750,9 +1854,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			}
 			const unsigned e0 = evals;
 			if constexpr (PRIOR) prior = pc.map && prior_usable(prior) ? prior : 0.f;
-			process_pixel<S, NW, BIG, TWO, PACK, HINT, SPREAD, PRIOR>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued, spc, pc, prior STAMP_PASS);
+			if constexpr (GEO) gp = geo_pix(gc, uniform_byte(c.gra, y * c.W + x), x, y); // the pixel's weight by its texture, uniform over the wave
+			process_pixel<S, NW, BIG, TWO, PACK, HINT, SPREAD, PRIOR, GEO>(c, L, L1, sh, par, wv, x, y, q, iter, in, P, st, pp, evals, issued, spc, pc, prior, gp STAMP_PASS);
 			taps += (unsigned long long)(evals - e0) * (unsigned)((P.a + 1) * (P.a + 1));
 			if constexpr (PRIOR) if (prior > 0.f) { evalsPrior += evals - e0; pixelsPrior += iter == pc.countIter ? 1u : 0u; }
+			if constexpr (GEO) if (gp.w > 0.f) { evalsGeo += evals - e0; pixelsGeo += iter == gc.countIter ? 1u : 0u; }
 			STAMP(5) // (the pixel loop's back-edge is stamp 13's alone)
 		}
 		if (pp.fail) break;
@@ -1776,6 +1882,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(!BIG ? 
 			if (spc.accepted) atomicAdd(sy.evals + 5, (unsigned long long)spc.accepted);
 			if (spc.dropped) atomicAdd(sy.evals + 6, (unsigned long long)spc.dropped);
 			if (spc.outside) atomicAdd(sy.evals + 7, (unsigned long long)spc.outside);
+		}
+		if constexpr (GEO) if (wv == 0) { // the geometric-consistency counters (hcmvs_get_geo_stats) follow the prior counters
+			if (evalsGeo) atomicAdd(sy.evals + 10, (unsigned long long)evalsGeo);
+			if (pixelsGeo) atomicAdd(sy.evals + 11, (unsigned long long)pixelsGeo);
 		}
 		if constexpr (PRIOR) if (wv == 0) { // the prior counters (hcmvs_get_prior_stats) follow the view-spread counters
 			if (evalsPrior) atomicAdd(sy.evals + 8, (unsigned long long)evalsPrior);
@@ -1818,7 +1928,8 @@ __global__ void import_state_kernel(EstConst c, const float* depthIn, const floa
 }
 
 // PRIOR: the item has an active depth prior (its PriorItem): the pixel's one evaluation blends the prior term where its prior is usable
-template <int S, bool BIG, bool TWO = false, bool MASK = false, bool PRIOR = false>
+// GEO: the item has the geometric-consistency term active (its GeoItem): the pixel's one evaluation blends it where the pixel has a weight
+template <int S, bool BIG, bool TWO = false, bool MASK = false, bool PRIOR = false, bool GEO = false>
 __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long long* evalsOut) {
 	LaneCtx<S> L;
 	lane_init<S>(c, L);
@@ -1838,10 +1949,12 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 	const int total = nrows * ncols;
 	const int wavesPerBlock = blockDim.x >> 6;
 	const int gw = blockIdx.x * wavesPerBlock + (threadIdx.x >> 6), nw = gridDim.x * wavesPerBlock;
-	unsigned evals = 0, evalsPrior = 0;
+	unsigned evals = 0, evalsPrior = 0, evalsGeo = 0;
 	unsigned long long taps = 0;
 	PriorConst pc = {nullptr, 0.f, 0.f, 0.f, -1};
 	if constexpr (PRIOR) pc = prior_const(c);
+	GeoConst gc = {nullptr, 0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 1.f, -1};
+	if constexpr (GEO) gc = geo_const(c);
 	const uint32_t stream0 = (uint32_t)c.itExternal * 64u;
 	for (int p = gw; p < total; p += nw) {
 		const int x = c.border + p % ncols, y = c.border + p / ncols;
@@ -1869,10 +1982,12 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 			const float prior = uniform_float(pc.map, idx); // (one wave per pixel: uniform)
 			if (prior_usable(prior)) { padd = prior_addend(pc.sigma, pc.para, prior, d); pkeep = pc.keep; ++evalsPrior; }
 		}
-		score_pixel<S, BIG, RegStore<S>, PRIOR>(c, L, P, st, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep);
+		GeoPix gp = {nullptr, 0.f, 1.f, 1.f, 0.f, 0.f};
+		if constexpr (GEO) { gp = geo_pix(gc, uniform_byte(c.gra, idx), x, y); if (gp.w > 0.f) ++evalsGeo; } // (one wave per pixel: uniform)
+		score_pixel<S, BIG, RegStore<S>, PRIOR, GEO>(c, L, P, st, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep, gp);
 		if constexpr (TWO) {
 			st1.copy_patch(st); // the pixel's patch tables (registers) with the second set's view constants
-			score_pixel<S, BIG, RegStore<S>, PRIOR>(c, L1, P, st1, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep);
+			score_pixel<S, BIG, RegStore<S>, PRIOR, GEO>(c, L1, P, st1, G.v0, G.v1, 1.f, d, n0, n1, n2, m1, m2, padd, pkeep, gp);
 		}
 		const float s = two_best(c, m1, m2);
 		++evals;
@@ -1889,6 +2004,10 @@ __global__ __launch_bounds__(256) void score_kernel(EstConst c, unsigned long lo
 		if constexpr (PRIOR) if (evalsPrior) { // one evaluation per pixel: the pixels with a usable prior are the evaluations that blended
 			atomicAdd(evalsOut + 8, (unsigned long long)evalsPrior);
 			if (pc.countIter < 0) atomicAdd(evalsOut + 9, (unsigned long long)evalsPrior);
+		}
+		if constexpr (GEO) if (evalsGeo) { // likewise: the pixels with a weight are the evaluations that blended
+			atomicAdd(evalsOut + 10, (unsigned long long)evalsGeo);
+			if (gc.countIter < 0) atomicAdd(evalsOut + 11, (unsigned long long)evalsGeo);
 		}
 	}
 }
@@ -2045,42 +2164,43 @@ void launch_apply_mask(const uint8_t* keep, float* depth, float* normal, int n, 
 	hipLaunchKernelGGL(apply_mask_kernel, dim3(2048), dim3(256), 0, s, keep, depth, normal, n);
 }
 
-// score_kernel<8, BIG, TWO, MASK, PRIOR> by (PRIOR, BIG, TWO, MASK): all sixteen exist
+// score_kernel<8, BIG, TWO, MASK, PRIOR, GEO> by (GEO, PRIOR, BIG, TWO, MASK): the sixteen without GEO and the eight GEO ones
+// (entries 16 .. 23; the term comes without the prior)
 template <class K, int N>
 struct KernelTable { K at[N]; };
 using ScoreKernel = void (*)(EstConst, unsigned long long*);
 template <int... I>
 static constexpr KernelTable<ScoreKernel, sizeof...(I)> score_table(std::integer_sequence<int, I...>) {
-	return {{score_kernel<8, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, (I & 8) != 0>...}};
+	return {{score_kernel<8, (I & 4) != 0, (I & 2) != 0, (I & 1) != 0, (I & 24) == 8, (I & 16) != 0>...}};
 }
-static constexpr auto kScoreKernels = score_table(std::make_integer_sequence<int, 16>{});
+static constexpr auto kScoreKernels = score_table(std::make_integer_sequence<int, 24>{});
 void launch_score_pass(const EstConst& c, const float* depthIn, const float* normalIn, unsigned long long* evals,
-                       hipStream_t s, bool prior) {
+                       hipStream_t s, bool prior, bool geo) {
 	hipLaunchKernelGGL(import_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn);
 	// 9..16 views: two sets of eight
-	hipLaunchKernelGGL(kScoreKernels.at[(prior ? 8 : 0) | (c.adapthalfwin > kHalfWindow ? 4 : 0) | (c.V > 8 ? 2 : 0) | (c.keep ? 1 : 0)], dim3(4096), dim3(256), 0, s, c, evals);
+	hipLaunchKernelGGL(kScoreKernels.at[(geo ? 16 : (prior ? 8 : 0)) | (c.adapthalfwin > kHalfWindow ? 4 : 0) | (c.V > 8 ? 2 : 0) | (c.keep ? 1 : 0)], dim3(4096), dim3(256), 0, s, c, evals);
 }
 void launch_import_state(const EstConst& c, const float* depthIn, const float* normalIn, const float* confIn, hipStream_t s) {
 	hipLaunchKernelGGL(import_state_kernel, dim3(2048), dim3(256), 0, s, c, depthIn, normalIn, confIn);
 }
 
-// sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD, PRIOR> by SweepVariant: exactly the instances sweep_variant_exists admits, null elsewhere
+// sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD, PRIOR, GEO> by SweepVariant: exactly the instances sweep_variant_exists admits, null elsewhere
 using SweepKernel = void (*)(const EstConst*, int, int, SweepSync, int, int, int, int, int);
 constexpr int sweep_variant_index(SweepVariant v) {
-	return v.prior << 8 | (v.nw - 1) << 6 | v.big << 5 | v.two << 4 | v.pack << 3 | v.hint << 2 | v.mask << 1 | (int)v.spread;
+	return v.geo << 9 | v.prior << 8 | (v.nw - 1) << 6 | v.big << 5 | v.two << 4 | v.pack << 3 | v.hint << 2 | v.mask << 1 | (int)v.spread;
 }
 constexpr SweepVariant sweep_variant_at(int i) {
-	return {((i >> 6) & 3) + 1, (i & 32) != 0, (i & 16) != 0, (i & 8) != 0, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0, (i & 256) != 0};
+	return {((i >> 6) & 3) + 1, (i & 32) != 0, (i & 16) != 0, (i & 8) != 0, (i & 4) != 0, (i & 2) != 0, (i & 1) != 0, (i & 256) != 0, (i & 512) != 0};
 }
 template <int I>
 static constexpr SweepKernel sweep_instance() {
 	constexpr SweepVariant v = sweep_variant_at(I);
-	if constexpr (sweep_variant_exists(v)) return sweep_kernel<8, v.nw, v.big, v.two, v.pack, v.hint, v.mask, v.spread, v.prior>;
+	if constexpr (sweep_variant_exists(v)) return sweep_kernel<8, v.nw, v.big, v.two, v.pack, v.hint, v.mask, v.spread, v.prior, v.geo>;
 	else return nullptr;
 }
 template <int... I>
 static constexpr KernelTable<SweepKernel, sizeof...(I)> sweep_table(std::integer_sequence<int, I...>) { return {{sweep_instance<I>()...}}; }
-static constexpr auto kSweepKernels = sweep_table(std::make_integer_sequence<int, 2 * 4 * 64>{});
+static constexpr auto kSweepKernels = sweep_table(std::make_integer_sequence<int, 2 * 2 * 4 * 64>{});
 
 bool launch_sweep(const SweepArgs& a, const SweepLaunch& l, hipStream_t s) {
 	const SweepKernel k = sweep_variant_exists(l.v) ? kSweepKernels.at[sweep_variant_index(l.v)] : nullptr;

@@ -96,6 +96,34 @@ static_assert(sizeof(PriorItem) <= 2 * sizeof(DevView) && (kMaxViews * sizeof(De
 inline const PriorItem* prior_item(const DevView* views) { return (const PriorItem*)(const void*)(views + kMaxViews); }
 inline PriorItem* prior_item(DevView* views) { return (PriorItem*)(void*)(views + kMaxViews); }
 
+// Geometric consistency (GEO instances of the kernels): what a lane needs of one source view j whose own maps
+// of the previous outer iteration score a hypothesis.  depth == null: the view offers none.  The maps have the view's image size and are
+// the ones registered with hcmvs_set_spread_maps_device.  Everything is held as float: computed in double on the host, rounded once.
+struct GeoView {
+	const float* depth;   // w * h
+	const float* normal;  // w * h * 3, view j's camera frame
+	int32_t w, h;
+	float cx, cy, ifx, ify; // view j's principal point and 1 / focal
+	float B[9];           // K_i R_i R_j^T: a point of view j's camera into the reference image (homogeneous)
+	float b[3];           // K_i R_i (C_j - C_i)
+	float Rr[9];          // R_i R_j^T: a normal of view j's camera frame into the reference camera's
+	int32_t pad;
+};
+// The term's constants of one item, behind the item's PriorItem in the slot of the DevView table (geo_item()); only the GEO instances
+// ever look there.  views == null: the term is not active for the item.
+struct GeoItem {
+	const GeoView* views; // [V] entries in the estimate's view order
+	float w1, w2;         // para_tapa, para_tapa2
+	float keep1, keep2;   // 1 - para_tapa, 1 - para_tapa2, rounded once
+	float tx1, tx2;       // txthreshold, txthreshold2
+	float maxPx;          // the reprojection error at and beyond which a pair is "worst"
+	int32_t countIter;    // the sweep index in which the pixels with a weight are counted; -1: the init-score pass counts them
+};
+static_assert(sizeof(PriorItem) % 8 == 0 && sizeof(PriorItem) + sizeof(GeoItem) <= 2 * sizeof(DevView) && sizeof(GeoView) % 8 == 0,
+              "the GeoItem behind an item's PriorItem must fit the slot and be 8-byte aligned");
+inline const GeoItem* geo_item(const DevView* views) { return (const GeoItem*)(const void*)((const char*)prior_item(views) + sizeof(PriorItem)); }
+inline GeoItem* geo_item(DevView* views) { return (GeoItem*)(void*)((char*)prior_item(views) + sizeof(PriorItem)); }
+
 
 } // namespace hcmvs
 #endif

@@ -24,27 +24,30 @@ constexpr int kSweepGridCap = 8192;  // one workgroup per ticket; tickets beyond
 constexpr int kSweepStretch = 256;   // columns of an automatic stretch
 constexpr int kSweepStretchMin = 32; // (the ring of a row's latest results is re-read from memory at the start of a stretch)
 
-// one instance of sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD, PRIOR>
+// one instance of sweep_kernel<8, NW, BIG, TWO, PACK, HINT, MASK, SPREAD, PRIOR, GEO>
 struct SweepVariant {
 	int nw; // waves per row
 	bool big, two, pack, hint, mask, spread;
 	bool prior = false; // some item of the launch has an active depth prior
+	bool geo = false;   // some item of the launch has the geometric-consistency term active
 };
-// THE set of sweep instances the library holds (200: 152 without the prior term, 48 with it -- a prior comes without the hint and
-// without view spread): the launcher's table is generated from this predicate, so nothing else is compiled and nothing else can be
-// launched
+// THE set of sweep instances the library holds (248: 152 without the prior term, 48 with it -- a prior comes without the hint and
+// without view spread -- and 48 with the geometric-consistency term, which comes without the hint, view spread and the prior, so a GEO
+// instance exists exactly where the PRIOR instance of the same shape does): the launcher's table is generated from this predicate, so
+// nothing else is compiled and nothing else can be launched
 constexpr bool sweep_variant_exists(SweepVariant v) {
-	return v.nw >= 1 && v.nw <= 4 && (v.nw <= 2 || !(v.big || v.hint)) && (v.nw <= 3 || !v.spread) && (!v.prior || !(v.hint || v.spread));
+	return v.nw >= 1 && v.nw <= 4 && (v.nw <= 2 || !(v.big || v.hint)) && (v.nw <= 3 || !v.spread) && (!v.prior || !(v.hint || v.spread)) &&
+	       (!v.geo || !(v.hint || v.spread || v.prior));
 }
 // The instance for `requested` waves per row in a launch whose selecting item has V source views (plan_sweeps: vSel).  Patches beyond
 // 64 taps and the one sweep of a run that carries the hint run with one or two waves per row; a launch with view spread has no
 // four-wave instance (three waves compute the same maps); a request outside 1..4 gets two.
-constexpr SweepVariant resolve_sweep_variant(int requested, int V, bool big, bool hint, bool mask, bool spread, bool prior = false) {
+constexpr SweepVariant resolve_sweep_variant(int requested, int V, bool big, bool hint, bool mask, bool spread, bool prior = false, bool geo = false) {
 	int nw = 2;
 	if (big || hint) nw = requested >= 2 ? 2 : 1;
 	else if (requested == 1 || requested == 3) nw = requested;
 	else if (requested == 4) nw = spread ? 3 : 4;
-	return {nw, big, V > 8, view_count_packs(V), hint, mask, spread, prior};
+	return {nw, big, V > 8, view_count_packs(V), hint, mask, spread, prior, geo};
 }
 
 struct SweepItem {
@@ -52,6 +55,7 @@ struct SweepItem {
 	bool hintLast;          // offers the `restore` variant's extra hypothesis in the last sweep
 	bool mask, spread;      // has a keep-mask (EstConst::keep), has view spread to do (EstConst::spread)
 	bool prior = false;     // has an active depth prior (PriorItem::prior)
+	bool geo = false;       // has the geometric-consistency term active (GeoItem::views)
 };
 struct SweepBatch {
 	std::vector<SweepItem> items;
@@ -85,20 +89,20 @@ inline SweepKnobs parse_sweep_knobs(const char* lag, const char* affinity, const
 // One launch for the sweeps first .. first + count - 1 of every item (indices as the kernel sees them: SweepBatch::firstSweep included) (tickets, rowsDone and the progress words of the items must be zero)
 struct SweepLaunch {
 	int first, count;
-	SweepVariant v;  // hint: some item offers its hint in one of these sweeps; mask / spread / prior: some item has a keep-mask / view spread to do / an active prior
+	SweepVariant v;  // hint: some item offers its hint in one of these sweeps; mask / spread / prior / geo: some item has a keep-mask / view spread to do / an active prior / the geometric-consistency term active
 	int segLen;      // > 0: a ticket is a stretch of segLen columns of a row; 0: a whole row
 	int tickets, grid;
 };
 
 inline std::vector<SweepLaunch> plan_sweeps(const SweepBatch& b) {
 	int totalRows = 0;
-	bool hintLast = false, mask = false, spread = false, prior = false;
+	bool hintLast = false, mask = false, spread = false, prior = false, geo = false;
 	// the kernel variant goes by view count: an item whose count leaves two or more view groups idle wants the pair-packing variant,
 	// which is correct for the other items of its layout class too
 	int vSel = b.items.empty() ? 0 : b.items[0].nSrc;
 	for (const SweepItem& it : b.items) {
 		totalRows += it.rows;
-		hintLast = hintLast || it.hintLast; mask = mask || it.mask; spread = spread || it.spread; prior = prior || it.prior;
+		hintLast = hintLast || it.hintLast; mask = mask || it.mask; spread = spread || it.spread; prior = prior || it.prior; geo = geo || it.geo;
 		if (view_count_packs(it.nSrc)) vSel = it.nSrc;
 	}
 	// Waves per row, by how the batch's rows compare with the workers the chip holds at once (12 per CU: 4 SIMDs x 3 sweep workers; the
@@ -129,7 +133,7 @@ inline std::vector<SweepLaunch> plan_sweeps(const SweepBatch& b) {
 		// The rule counts the REQUESTED waves, the kernel runs with the resolved ones (a hint or big-patch launch asked for 3 runs 2, and
 		// still goes in stretches where 2 * totalRows <= slots).  The maps are the same either way; which is faster is not measured
 		// (last item) and is left to a change that measures it.
-		SweepLaunch l{b.firstSweep + first, count, resolve_sweep_variant(requested, vSel, b.big, hint, mask, spread, prior), 0, totalRows, 0};
+		SweepLaunch l{b.firstSweep + first, count, resolve_sweep_variant(requested, vSel, b.big, hint, mask, spread, prior, geo), 0, totalRows, 0};
 		if (b.sweepSegment > 0 || (b.sweepSegment < 0 && count == 1 && requested * totalRows > slots && totalRows < 4 * slots)) {
 			l.segLen = b.sweepSegment > 0 ? b.sweepSegment : kSweepStretch;
 			if (l.segLen < kSweepStretchMin) l.segLen = kSweepStretchMin;

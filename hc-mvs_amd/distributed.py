@@ -133,7 +133,7 @@ def _handoff(ctx, dev, mode, jobs, w, h):
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
                   fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
                   geometric_filter=None, gf_kw=None, hints=None, fuse=True, priors=None, prior_params=None,
-                  plane_priors=None, plane_prior_params=None):
+                  plane_priors=None, plane_prior_params=None, geo=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -200,6 +200,11 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                iterations the priors are never registered -- the result then carries priors_used = False; nothing is raised.  Priors belong
                to reference images, so ranks exchange nothing new: a rank registers those of its own images.  Not together with viewspread
                or hints (ValueError: the library refuses the combination)
+    geo:       the geometric-consistency term: True for the defaults or a dict of the options of
+               binding.Context.set_geo_params (para_tapa, para_tapa2, txthreshold, txthreshold2, photo2geo, max_px).  From outer iteration 1
+               on every image offers the maps the previous outer iteration left it to the estimates it is a source view of, as for
+               viewspread (and across ranks by the same exchange); the term blends from outer iteration max(1, photo2geo) on.  Not together
+               with viewspread, hints, priors or plane_priors (ValueError: the library refuses the combinations)
     plane_priors: optional {image id: label image (any size, 16-bit)}: the priors of those REFERENCE images are GENERATED on the device
                (binding.Context.generate_plane_prior_device) from planes fitted inside the pixels labelled
                plane_prior_params.region_label (binding.default_plane_prior_params(); None: the defaults, label 255): on outer iteration
@@ -216,6 +221,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     Returns the fused cloud dict of binding.Context.fuse plus `maps`: {id: (depth, normal, conf) device tensors}."""
     import copy
     import numpy as np
+    if geo and (viewspread or hints or priors or plane_priors):
+        raise ValueError("densify_scene: geo is not combined with viewspread, hints, priors or plane_priors (the library refuses the term together with each)")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -342,9 +349,15 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
         if extra:
             ctx.estimate_sweeps_batch_device(extra, p, p.n_estimation_iters, 2)
 
+    geo_kw = None
+    if geo:
+        geo_kw = dict(geo) if isinstance(geo, dict) else {}
+        geo_kw.pop("on", None)
+        ctx.set_geo_params(on=True, **geo_kw)
+    offer = bool(viewspread) or geo_kw is not None      # the source views offer their previous maps: to view spread, or to the term
     if viewspread:
         ctx.set_viewspread(True)
-    snapshot = torch.empty_like(slabs) if viewspread and world == 1 and not interleave and n_external_iters > 1 else None
+    snapshot = torch.empty_like(slabs) if offer and world == 1 and not interleave and n_external_iters > 1 else None
 
     def register(allm):
         for k, img in enumerate(ids):
@@ -359,7 +372,7 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
     for it in range(int(n_external_iters)):
         p.it_external = it
         filt = postfilter and it in (1, 2)
-        spread = bool(viewspread) and it >= 1
+        spread = offer and it >= 1
         if (filt or spread) and interleave:
             # the reference's order: estimate(k) -> post-filter(k) -> estimate(k + 1), image ids ascending.  The gathered buffer is the
             # state of the whole scene on every rank; an image is estimated in place by its owner and broadcast before its filter runs
@@ -433,6 +446,9 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
             cloud["filter"] = filter_stats
         if viewspread:
             ctx.set_viewspread(False)
+        if geo_kw is not None:
+            ctx.set_geo_params(on=False)
+        if offer:
             for img in ids:
                 ctx.set_spread_maps_device(img, None, None, None)
         if priors or plane_priors:

@@ -19,7 +19,9 @@
  * that existing command lines keep their results; one device); --plane-priors 1 generates depth priors from planes fitted inside the
  * label 255 of seman/<stem>.quad.pgm|ppm on outer iteration n - 2 (--export-priors <dir> writes them; --plane-clusters 1 keeps the largest
  * connected component of a plane's inliers, on cells of --ransac-cluster average spacings);
- * optical flow, --use-semantic and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
+ * --geo-consistency 1 blends every view score with a reprojection term against the source views' maps of the previous outer iteration
+ * (fed by --n-para_tapa, --n-para_tapa2, --n-txthreshold, --n-txthreshold2, --n-photo2geo, --geo-max-px; one device; D14);
+ * optical flow, --use-semantic, --n-usegeoconsistency and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
  *
  * How the run is laid out in time (the reference overlaps image k + 1's InitViews with image k's estimate, SceneDensify.cpp:3699-3703;
  * here the unit is a batch of reference images):
@@ -845,6 +847,7 @@ bool contexts_ready(Run& r) {
 		if (d.createRc != HCMVS_OK) { fprintf(stderr, "error: device %d is not a usable MI355X (there is no CPU path)\n", d.ordinal); return false; }
 	r.ctx = r.devs[0].ctx;
 	if (hipSetDevice(o.device) != hipSuccess) { fprintf(stderr, "error: hipSetDevice failed\n"); return false; }
+	if (r.nDev > 1 && o.geoConsistency) { fprintf(stderr, "error: --geo-consistency 1 runs on one device: every estimate reads the depth maps of its source views, which other devices would hold (drop --devices)\n"); return false; }
 	if (r.nDev > 1 && o.viewspread) { fprintf(stderr, "error: --n-viewspread 1 runs on one device: every estimate reads the depth maps of its source views, which other devices would hold (drop --devices)\n"); return false; }
 	if (r.nDev > 1 && o.postFilterInterleave) { fprintf(stderr, "error: --n-postfilter-interleave 1 estimates one image at a time and runs on one device (drop --devices)\n"); return false; }
 	return true;
@@ -1137,6 +1140,12 @@ bool start_saver_and_workers(Run& r) {
 	r.tInit = now_s();
 	HIPOK(hipStreamCreateWithFlags(&r.xs.s, hipStreamNonBlocking));
 	if (r.o.viewspread) CHK(hcmvs_set_viewspread(ctx, 1));
+	if (r.o.geoConsistency) { // the geometric-consistency term: the source views' maps are offered as for view spread (plan_iteration)
+		const hcmvs_geo_params gp = geo_params(r.o);
+		CHK(hcmvs_set_geo_params(ctx, &gp));
+		printf("Geometric consistency: para_tapa %g (texture < %g), para_tapa2 %g (texture < %g), photo2geo %d, max_px %g\n", (double)gp.para_tapa,
+		       (double)gp.txthreshold, (double)gp.para_tapa2, (double)gp.txthreshold2, gp.photo2geo, (double)gp.max_px);
+	}
 	r.workers.reset(new Workers(r));
 	return true;
 }

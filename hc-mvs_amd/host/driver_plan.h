@@ -59,6 +59,13 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	                              // an image without a file has no prior (DepthMap.cpp:941-954)
 	float paraPrior = 0.5f, sigmaPrior = 0.2f; // --n-para_prior, --sigma-prior (DensifyPointCloud.cpp:183, :162)
 	int photo2geo = 2;            // --n-photo2geo (DensifyPointCloud.cpp:175): first outer iteration that blends the prior term
+	int geoConsistency = 0;       // --geo-consistency 1: the geometric-consistency term: from outer iteration max(1, --n-photo2geo)
+	                              // on every view score is blended with a reprojection term against the source views' maps of the previous outer iteration
+	float paraTapa = 0.25f;       // --n-para_tapa (DensifyPointCloud.cpp:176-181): the term's weight where the pixel has low texture
+	float paraTapa2 = 0.15f;      // --n-para_tapa2: ... medium texture
+	float txThreshold = 150.f;    // --n-txthreshold: the texture threshold of --n-para_tapa
+	float txThreshold2 = 160.f;   // --n-txthreshold2: the texture threshold of --n-para_tapa2
+	float geoMaxPx = 3.f;         // --geo-max-px: the reprojection error, in pixels, at and beyond which a pair is "worst"
 	int planePriors = 0;          // --plane-priors 1: the priors are GENERATED on outer iteration n - 2 from planes fitted inside the pixels labelled 255 of
 	                              // seman/<stem>.quad.pgm|ppm (hcmvs_generate_plane_prior_device); an image without a label file has none
 	std::string exportPriors;     // --export-priors <dir>: every generated prior as <dir>/depth%04u.prior.dmap, the raw 'DR' form --depth-priors reads
@@ -97,6 +104,9 @@ static const char* const kKnownOptions[] = {
 static const char* const kPriorOptions[] = {"--depth-priors", "--plane-priors", "--export-priors"};
 // ... and the switch of the inlier clustering of the generated priors (a third table: the two above are pinned as they are)
 static const char* const kPlaneClusterOptions[] = {"--plane-clusters"};
+// ... and the geometric-consistency term's own (a fourth table; --n-para_tapa, --n-para_tapa2, --n-txthreshold, --n-txthreshold2 and
+// --n-photo2geo, which feed it, are the reference's and stand in kKnownOptions)
+static const char* const kGeoOptions[] = {"--geo-consistency", "--geo-max-px"};
 
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
@@ -107,6 +117,12 @@ static const char* const kUsage =
 	"                            level; an image without a file has none), blended into every score with --n-para_prior, --sigma-prior and\n"
 	"                            --n-photo2geo; registered on outer iteration n - 2 with two extra sweeps, kept through the last.  Not together with\n"
 	"                            --n-viewspread 1 or --restore-hypothesis 1\n"
+	"       --geo-consistency 0|1  geometric consistency: from outer iteration max(1, --n-photo2geo) on every view score is blended with a reprojection\n"
+	"                            term against the source view's own depth and normal map of the previous outer iteration, with the weight\n"
+	"                            --n-para_tapa where the pixel's texture is below --n-txthreshold, --n-para_tapa2 where it is below --n-txthreshold2;\n"
+	"                            --geo-max-px (default 3) is the error at which a pair counts as worst (default 0; --n-usegeoconsistency, the fork's dead\n"
+	"                            blend, stays unavailable).  One device.  Not together with --n-viewspread 1, --restore-hypothesis 1, --depth-priors or\n"
+	"                            --plane-priors 1\n"
 	"       --plane-priors 0|1   generate the priors instead: on outer iteration n - 2 planes are fitted inside the pixels labelled 255 of\n"
 	"                            seman/<stem>.quad.pgm|ppm of every image that has one (--ransac-probability, --ransac-epsilon, --ransac-min-points and\n"
 	"                            --seed feed the detection) and rendered into the image's prior; from there as --depth-priors.  --export-priors <dir>\n"
@@ -140,6 +156,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		for (const char* k : kKnownOptions) known = known || a == k;
 		for (const char* k : kPriorOptions) known = known || a == k;
 		for (const char* k : kPlaneClusterOptions) known = known || a == k;
+		for (const char* k : kGeoOptions) known = known || a == k;
 		if (!known) { err = "unrecognised option '" + a + "'"; return PARSE_ERROR; }
 		if (!haveVal) { // the value is the next argument, whatever it starts with (negative numbers are values)
 			if (i + 1 >= argc) { err = "the required argument for option '" + a + "' is missing"; return PARSE_ERROR; }
@@ -169,6 +186,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (kv.count("--export-priors")) o.exportPriors = kv["--export-priors"];
 	getf("--ransac-probability", o.ransacProbability); getf("--ransac-epsilon", o.ransacEpsilon); getf("--ransac-min-points", o.ransacMinPoints);
 	geti("--plane-clusters", o.planeClusters); getf("--ransac-cluster", o.ransacCluster);
+	geti("--geo-consistency", o.geoConsistency); getf("--geo-max-px", o.geoMaxPx);
+	getf("--n-para_tapa", o.paraTapa); getf("--n-para_tapa2", o.paraTapa2); getf("--n-txthreshold", o.txThreshold); getf("--n-txthreshold2", o.txThreshold2);
 	geti("--device", o.device); geti("--batch", o.batch);
 	if (kv.count("--devices")) { // comma-separated HIP ordinals
 		std::stringstream ss(kv["--devices"]);
@@ -217,6 +236,18 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		if (!o.depthPriors.empty() && o.viewspread) { err = "--depth-priors is not combined with --n-viewspread 1 (the authors run priors with --n-viewspread 0)"; return PARSE_ERROR; }
 		if (!(o.paraPrior >= 0.f && o.paraPrior <= 1.f)) { err = "--n-para_prior expects a value in [0, 1]"; return PARSE_ERROR; }
 		if (!(o.sigmaPrior > 0.f) || !(o.sigmaPrior < INFINITY)) { err = "--sigma-prior expects a finite value > 0"; return PARSE_ERROR; }
+		if (o.photo2geo < 0) { err = "--n-photo2geo expects a value >= 0"; return PARSE_ERROR; }
+	}
+	if (o.geoConsistency != 0 && o.geoConsistency != 1) { err = "--geo-consistency expects 0 or 1"; return PARSE_ERROR; }
+	if (o.geoConsistency) { // (without it the options that feed the term are read and have nothing to act on)
+		if (o.viewspread) { err = "--geo-consistency 1 is not combined with --n-viewspread 1 (the library refuses the term together with view spread at work)"; return PARSE_ERROR; }
+		if (o.restoreHypothesis) { err = "--geo-consistency 1 is not combined with --restore-hypothesis 1 (the term does not come with the hint)"; return PARSE_ERROR; }
+		if (!o.depthPriors.empty()) { err = "--geo-consistency 1 is not combined with --depth-priors (the term does not come with the prior term)"; return PARSE_ERROR; }
+		if (o.planePriors) { err = "--geo-consistency 1 is not combined with --plane-priors 1 (the term does not come with the prior term)"; return PARSE_ERROR; }
+		if (!(o.paraTapa >= 0.f && o.paraTapa <= 1.f)) { err = "--n-para_tapa expects a value in [0, 1]"; return PARSE_ERROR; }
+		if (!(o.paraTapa2 >= 0.f && o.paraTapa2 <= 1.f)) { err = "--n-para_tapa2 expects a value in [0, 1]"; return PARSE_ERROR; }
+		if (!(fabsf(o.txThreshold) < INFINITY) || !(fabsf(o.txThreshold2) < INFINITY)) { err = "--n-txthreshold and --n-txthreshold2 expect finite values"; return PARSE_ERROR; }
+		if (!(o.geoMaxPx > 0.f) || !(o.geoMaxPx < INFINITY)) { err = "--geo-max-px expects a finite value > 0"; return PARSE_ERROR; }
 		if (o.photo2geo < 0) { err = "--n-photo2geo expects a value >= 0"; return PARSE_ERROR; }
 	}
 	if (o.batch < 1) o.batch = 1;
@@ -496,7 +527,8 @@ struct IterPlan {
 };
 inline IterPlan plan_iteration(const Options& o, int it, bool anyWork) {
 	const bool last = it == o.estimationItersExternal - 1;
-	const bool filterNow = o.postFilter && (it == 1 || it == 2), spreadNow = o.viewspread && it >= 1;
+	// (the source views offer their maps to view spread or to the geometric-consistency term: the same copies, the same registry)
+	const bool filterNow = o.postFilter && (it == 1 || it == 2), spreadNow = (o.viewspread || o.geoConsistency) && it >= 1;
 	IterPlan p;
 	p.filtered = filterNow && anyWork;
 	p.serial = o.postFilterInterleave && anyWork && (filterNow || spreadNow);
@@ -511,6 +543,10 @@ inline IterPlan plan_iteration(const Options& o, int it, bool anyWork) {
 // priors of its images are registered and two extra sweeps run (indices --n-EstimationIters and + 1); they stay registered through the last
 // iteration.  With fewer than two outer iterations the priors are never used.
 // --plane-priors 1 follows the same schedule: the priors are generated where --depth-priors registers the ones it read.
+// --geo-consistency 1: the term's options as the library takes them
+inline hcmvs_geo_params geo_params(const Options& o) {
+	return {o.geoConsistency, o.paraTapa, o.paraTapa2, o.txThreshold, o.txThreshold2, o.photo2geo, o.geoMaxPx};
+}
 inline bool has_priors(const Options& o) { return !o.depthPriors.empty() || o.planePriors != 0; }
 inline bool prior_sweeps_after(const Options& o, int it) { return has_priors(o) && it == o.estimationItersExternal - 2; }
 inline bool priors_never_used(const Options& o) { return has_priors(o) && o.estimationItersExternal < 2; }

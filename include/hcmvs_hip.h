@@ -182,7 +182,9 @@ int hcmvs_set_viewspread(hcmvs_ctx* ctx, int32_t on);
  * caller-owned, not copied, read by the estimates that follow.  All three NULL removes them; registering the view again or
  * hcmvs_release_view drops them.  A view without maps, and a view made by hcmvs_rescale_view (refused here: there are no maps of
  * its size), never spreads.  An estimate must not write the maps it reads: hcmvs_estimate_batch_device fails with
- * HCMVS_ERR_INVALID when the in/out maps of an item overlap the spread maps of a source view of any item of the same call. */
+ * HCMVS_ERR_INVALID when the in/out maps of an item overlap the spread maps of a source view of any item of the same call.
+ * The registry has a second consumer: the geometric-consistency term (hcmvs_set_geo_params, below) reads the depth and the normal map
+ * a source view offers here, under the same rules. */
 int hcmvs_set_spread_maps_device(hcmvs_ctx* ctx, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf);
 /* counters of the view spread of the last estimate (summed over the items of a batch and its sweeps); synchronises */
 typedef struct {
@@ -235,6 +237,43 @@ typedef struct {
 	uint64_t pixels_prior; /* estimated pixels of the items with an active prior whose prior is usable (finite and > 0) */
 } hcmvs_prior_stats;
 int hcmvs_get_prior_stats(hcmvs_ctx* ctx, hcmvs_prior_stats* out);
+
+/* ---- geometric consistency (DensifyPointCloud --geo-consistency) -------------------------------------------
+ * A hypothesis is also scored by whether the source views' own depth maps agree with it.  While the term is active for an estimate,
+ * every ScorePixel evaluation blends, per source view j and before the two best views are taken,
+ *     score = score * (1 - w) + w * geo
+ * where w goes by the reference pixel's texture g (the gradient map): para_tapa where g < txthreshold, else para_tapa2 where
+ * g < txthreshold2, else 0 (such a pixel is evaluated as without this section); and geo of the pair (hypothesis, view j): the centre
+ * pixel goes through the hypothesis' homography into view j, view j's depth at the nearest pixel there takes that position back into
+ * the reference image, e is the distance in pixels to where it started, c the cosine between the hypothesis' normal and view j's
+ * normal there;  geo = e / max_px + (1 - c) where e < max_px, 2 elsewhere, and 1 (neutral) where view j offers no maps, the position
+ * lies outside its map, its depth there is not finite and > 0 or the point falls behind the reference camera.  A view that failed
+ * (thRobust) is not blended.  The maps of view j are those registered with hcmvs_set_spread_maps_device (depth and normal are read;
+ * the aliasing refusal of that entry applies unchanged): the caller keeps the previous outer iteration's maps there.
+ * The term is ACTIVE for an item when `on` is set, params->it_external >= photo2geo and a source view of the item offers maps;
+ * without it every call computes exactly what it computes without this section.  The stored confidence of a blended pixel is the
+ * blended score.  Refused (HCMVS_ERR_INVALID, nothing enqueued): a batch in which the term is active for an item while an item has the
+ * `restore` hint in effect, view spread doing work, or an active depth prior. */
+typedef struct {
+	int32_t on;          /* --geo-consistency: 0 = off (the default) */
+	float para_tapa;     /* --n-para_tapa: weight where the pixel has low texture, 0 .. 1 */
+	float para_tapa2;    /* --n-para_tapa2: weight where the pixel has medium texture, 0 .. 1 */
+	float txthreshold;   /* --n-txthreshold */
+	float txthreshold2;  /* --n-txthreshold2 */
+	int32_t photo2geo;   /* --n-photo2geo: first outer iteration that blends the term, >= 0 */
+	float max_px;        /* --geo-max-px: reprojection error in pixels at and beyond which a pair is "worst", > 0 */
+} hcmvs_geo_params;
+/* off, 0.25, 0.15, 150, 160, 2 (the reference's defaults, DensifyPointCloud.cpp:176-183), 3.0 */
+void hcmvs_default_geo_params(hcmvs_geo_params* p);
+/* for the estimates that follow.  Refused, with nothing changed: a weight outside [0, 1] or not finite, a threshold that is not finite,
+ * max_px not finite and > 0, photo2geo < 0. */
+int hcmvs_set_geo_params(hcmvs_ctx* ctx, const hcmvs_geo_params* p);
+/* counters of the term of the last estimate (summed over the items of a batch); synchronises */
+typedef struct {
+	uint64_t evals_geo;  /* evaluations that blended the term (they are part of hcmvs_stats::evals) */
+	uint64_t pixels_geo; /* estimated pixels with a weight > 0 of the items for which the term was active */
+} hcmvs_geo_stats;
+int hcmvs_get_geo_stats(hcmvs_ctx* ctx, hcmvs_geo_stats* out);
 
 /* ---- plane priors (DepthMapsData::GenerateDepthPrior, SceneDensify.cpp:1550-1950, restated without CGAL) ------------------------------
  * Planes are fitted inside a labelled region of a half-finished depth map and rendered into a prior depth map, which pulls the
