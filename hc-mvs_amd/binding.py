@@ -117,6 +117,25 @@ class PlanePriorParams(C.Structure):
     _fields_ = [("region_label", C.c_int32), ("conf_max", C.c_float), ("planarity_min", C.c_float), ("n_neighbors", C.c_int32), ("probability", C.c_float),
                 ("min_points_div", C.c_float), ("epsilon_mul", C.c_float), ("normal_threshold", C.c_float), ("max_rounds", C.c_int32), ("seed", C.c_uint64),
                 ("cluster_mul", C.c_float)]
+    # int32_t refit_iters, which the C struct appends, lies in the four bytes of tail padding behind cluster_mul (the size of the struct is
+    # what it was).  The field list above stays the one callers and tests of the layout were written against; the new member is a
+    # property over those four bytes.  A fresh instance is all zeros: no refit
+    REFIT_ITERS_OFFSET = 52
+
+    @property
+    def refit_iters(self):
+        return C.c_int32.from_buffer(self, self.REFIT_ITERS_OFFSET).value
+
+    @refit_iters.setter
+    def refit_iters(self, v):
+        C.c_int32.from_buffer(self, self.REFIT_ITERS_OFFSET).value = v
+
+
+assert PlanePriorParams.cluster_mul.offset + 4 == PlanePriorParams.REFIT_ITERS_OFFSET and C.sizeof(PlanePriorParams) == PlanePriorParams.REFIT_ITERS_OFFSET + 4
+
+
+class PlanePriorRefitStats(C.Structure):
+    _fields_ = [("refit_rounds", C.c_int32), ("refit_steps", C.c_int32)]
 
 
 class PriorPlane(C.Structure):
@@ -166,7 +185,8 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_default_prior_params", "hcmvs_set_prior_params", "hcmvs_set_depth_prior", "hcmvs_set_depth_prior_device",
            "hcmvs_estimate_sweeps_batch_device", "hcmvs_get_prior_stats",
            "hcmvs_default_plane_prior_params", "hcmvs_set_prior_region", "hcmvs_get_prior_region", "hcmvs_generate_plane_prior_device",
-           "hcmvs_get_plane_prior_trace", "hcmvs_get_plane_prior_cluster_trace"]
+           "hcmvs_get_plane_prior_trace", "hcmvs_get_plane_prior_cluster_trace", "hcmvs_get_plane_prior_refit_trace",
+           "hcmvs_get_plane_prior_refit_stats"]
 
 
 def triangulate_points(w, h, K, R, Cc, points_xyz, avg_depth=0.0, add_corners=True):
@@ -346,6 +366,8 @@ def lib():
                                                         C.POINTER(PlanePriorStats)]
         L.hcmvs_get_plane_prior_trace.argtypes = [vp, u8p, i32p, i32p, C.c_int32, i32p]
         L.hcmvs_get_plane_prior_cluster_trace.argtypes = [vp, i32p, C.c_int32, i32p]
+        L.hcmvs_get_plane_prior_refit_trace.argtypes = [vp, i32p, fp, C.c_int32, i32p]
+        L.hcmvs_get_plane_prior_refit_stats.argtypes = [vp, C.POINTER(PlanePriorRefitStats)]
         _lib = L
     return _lib
 
@@ -371,7 +393,8 @@ def default_prior_params(**kw):
 
 def default_plane_prior_params(**kw):
     """hcmvs_default_plane_prior_params: the reference's values (255, 0.18, 0.3, 10, 0.01, 80, 2, 0.25), 256 rounds, seed 1, cluster_mul 0 (a
-    plane's inliers are not clustered into connected components; > 0: the cell edge in average spacings, --ransac-cluster); then the overrides"""
+    plane's inliers are not clustered into connected components; > 0: the cell edge in average spacings, --ransac-cluster), refit_iters 0 (a
+    round's winner is not refitted; 1 .. 16: least-squares steps over its inliers in the eps / 4 band, --plane-refit); then the overrides"""
     p = PlanePriorParams()
     lib().hcmvs_default_plane_prior_params(C.byref(p))
     for k, v in kw.items():
@@ -676,7 +699,11 @@ class Context:
                                                           C.c_void_p(d_prior_normal_ptr) if d_prior_normal_ptr else None, tab, C.byref(st)))
         planes = [dict(normal=np.array(list(t.normal), np.float32), n_inliers=int(t.n_inliers), centre=np.array(list(t.centre), np.float64),
                        quad=np.array(list(t.quad), np.float64).reshape(4, 2), box_fallback=int(t.box_fallback)) for t in tab[:st.planes]]
-        return planes, {k: getattr(st, k) for k, _ in PlanePriorStats._fields_}
+        rs = PlanePriorRefitStats()                      # the refit's counters are a struct of their own in the C-ABI; here they join the dict
+        self._chk(lib().hcmvs_get_plane_prior_refit_stats(self._h, C.byref(rs)))
+        out = {k: getattr(st, k) for k, _ in PlanePriorStats._fields_}
+        out.update(refit_rounds=int(rs.refit_rounds), refit_steps=int(rs.refit_steps))
+        return planes, out
 
     def plane_prior_trace(self, vid):
         """the decisions of the last generate_plane_prior_device (of view vid's size): dict(stage (h, w) u8: 0 outside the region, 1 region,
@@ -698,6 +725,17 @@ class Context:
         rows = np.zeros((max(n.value, 1), 4), np.int32)
         self._chk(lib().hcmvs_get_plane_prior_cluster_trace(self._h, rows.ctypes.data_as(i32p), n.value, C.byref(n)))
         return rows[:n.value]
+
+    def get_plane_prior_refit_trace(self):
+        """what the refit (refit_iters) decided in every round of the last generate_plane_prior_device: (steps (n, 6) i32 -- steps solved,
+        steps kept, cnt_0 .. cnt_3 of the round's final plane --, planes (n, 4) f32 -- the final n, d); zeros for a round without a winner,
+        0, 0, the candidate's counts and the candidate's plane with refit_iters = 0"""
+        n = C.c_int32()
+        i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        self._chk(lib().hcmvs_get_plane_prior_refit_trace(self._h, None, None, 0, C.byref(n)))
+        steps = np.zeros((max(n.value, 1), 6), np.int32); planes = np.zeros((max(n.value, 1), 4), np.float32)
+        self._chk(lib().hcmvs_get_plane_prior_refit_trace(self._h, steps.ctypes.data_as(i32p), planes.ctypes.data_as(f32p), n.value, C.byref(n)))
+        return steps[:n.value], planes[:n.value]
 
     def stats(self):
         s = Stats()

@@ -897,6 +897,7 @@ void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p) {
 	p->probability = 0.01f; p->min_points_div = 80.f; p->epsilon_mul = 2.f;                    // DensifyPointCloud.cpp --ransac-*
 	p->normal_threshold = 0.25f; p->max_rounds = 256; p->seed = 1;
 	p->cluster_mul = 0.f; // clustering off: what the call computed before it had the field
+	p->refit_iters = 0;   // no refit: likewise
 }
 int hcmvs_set_prior_region(hcmvs_ctx* c, uint32_t id, const uint16_t* labels, int32_t lw, int32_t lh, int32_t region_label) {
 	if (!c) return HCMVS_ERR_INVALID;
@@ -990,6 +991,21 @@ int hcmvs_get_plane_prior_cluster_trace(hcmvs_ctx* c, int32_t* clusters, int32_t
 	const size_t nRounds = t.clusters.size() / 4;
 	if (n_rounds) *n_rounds = (int32_t)nRounds;
 	if (clusters) memcpy(clusters, t.clusters.data(), sizeof(int32_t) * 4 * std::min(nRounds, (size_t)capacity));
+	return HCMVS_OK;
+}
+int hcmvs_get_plane_prior_refit_trace(hcmvs_ctx* c, int32_t* steps, float* planes, int32_t capacity, int32_t* n_rounds) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const PriorGenTrace& t = c->priorTrace;
+	if ((steps || planes) && capacity < 0) return fail(c, HCMVS_ERR_INVALID, "get_plane_prior_refit_trace: negative capacity");
+	const size_t nRounds = t.refits.size() / 6;
+	if (n_rounds) *n_rounds = (int32_t)nRounds;
+	if (steps) memcpy(steps, t.refits.data(), sizeof(int32_t) * 6 * std::min(nRounds, (size_t)capacity));
+	if (planes) memcpy(planes, t.refitPlanes.data(), sizeof(float) * 4 * std::min(nRounds, (size_t)capacity));
+	return HCMVS_OK;
+}
+int hcmvs_get_plane_prior_refit_stats(hcmvs_ctx* c, hcmvs_plane_prior_refit_stats* out) {
+	if (!c || !out) return HCMVS_ERR_INVALID;
+	*out = c->priorTrace.refitStats;
 	return HCMVS_OK;
 }
 

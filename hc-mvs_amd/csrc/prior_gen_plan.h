@@ -1,6 +1,7 @@
 /* hc-mvs_amd/csrc/prior_gen_plan.h -- the host half of hcmvs_generate_plane_prior_device: what the call
  * refuses before any work, the inverse of K, the level table, min_points and the stop rule of the plane detection, the decoding of the
- * fixed-point sums, the frame and image quad of a plane from its reduced values (tiny, double precision), and the scratch layout.
+ * fixed-point sums, the frame and image quad of a plane from its reduced values (tiny, double precision), the scratch layout, and the
+ * least-squares refit of a round's winner (S4r): its scale, its solver and its decision sequence.
  * Plain C++ (no HIP); every product is rounded on its own (built with -ffp-contract=off, as the library is). */
 #ifndef HCMVS_PRIOR_GEN_PLAN_H
 #define HCMVS_PRIOR_GEN_PLAN_H
@@ -8,6 +9,7 @@
 #include <stdint.h>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include "../../include/hcmvs_hip.h"
 #include "carve.h"
@@ -21,6 +23,10 @@ constexpr int kPriorSpacingShift = 40;  // a spacing is summed as round(s * 2^40
 constexpr int kPriorCoordShift = 32;    // a coordinate is summed as round(P * 2^32), |P| saturated below 2^30
 constexpr int kPriorAccWords = 16;      // unsigned long long words a plane reduces into (prior_kernels.hip)
 constexpr uint32_t kPriorClusterCellCap = 1u << 30; // S4c: a cell coordinate is min(floor((u - u0) / cell), this); the cells at the cap merge (degenerate)
+constexpr int kPriorMaxRefitIters = 16; // S4r: refit_iters at the most
+constexpr int kPriorRefitFirstShift = 24;  // S4r: a first moment is summed as rint(s * 2^24), s = (P - O) / 2^E saturated inside (-2^20, 2^20)
+constexpr int kPriorRefitSecondShift = 20; // S4r: a second moment is summed as rint((s_a * s_b) * 2^20)
+constexpr int kPriorRefitWords = 24;       // unsigned long long words of the refit record: 0..3 cnt_0 .. cnt_3, 4..21 hi / lo of the nine sums (x y z xx xy xz yy yz zz)
 
 struct PriorGenArgs {
 	uintptr_t depth, normal, conf, prior, priorNormal; // device addresses as integers (the checks do not read them); priorNormal may be 0
@@ -64,6 +70,7 @@ inline std::string prior_gen_check(const PriorGenArgs& a) {
 	if (p.max_rounds < 1 || p.max_rounds > kPriorMaxRounds) { snprintf(buf, sizeof buf, "max_rounds %d outside 1..%d", p.max_rounds, kPriorMaxRounds); return buf; }
 	if (p.conf_max != p.conf_max || p.planarity_min != p.planarity_min || p.normal_threshold != p.normal_threshold) return "a threshold is NaN";
 	if (!(p.cluster_mul >= 0.f) || !std::isfinite(p.cluster_mul)) { snprintf(buf, sizeof buf, "cluster_mul %g is not a finite number >= 0", (double)p.cluster_mul); return buf; }
+	if (p.refit_iters < 0 || p.refit_iters > kPriorMaxRefitIters) { snprintf(buf, sizeof buf, "refit_iters %d outside 0..%d", p.refit_iters, kPriorMaxRefitIters); return buf; }
 	const uint64_t px = (uint64_t)a.w * a.h;
 	const struct { uintptr_t at; uint64_t bytes; const char* what; } in[3] = {{a.depth, px * 4, "depth"}, {a.normal, px * 12, "normal"}, {a.conf, px * 4, "conf"}};
 	for (const auto& m : in) {
@@ -209,6 +216,127 @@ inline PriorClusterScratch prior_gen_cluster_scratch(const PriorGenLayout& l, si
 	c.sortTmp = {l.knn.sort, l.knn.sortBytes};
 	c.rec = {l.words, 16 * 8};
 	return c;
+}
+
+// ---- S4r: the least-squares refit of a round's winner ----
+// The record of a refit launch lives in `acc`, which is idle during S4 (S5 initialises it before it reads it) and is none of the pieces
+// S4c borrows
+struct PriorRefitScratch { PriorScratchPiece rec; };
+inline PriorRefitScratch prior_gen_refit_scratch(const PriorGenLayout& l) {
+	PriorRefitScratch r;
+	r.rec = {l.acc, (size_t)kPriorRefitWords * 8};
+	return r;
+}
+// E of eps = f * 2^E, f in [0.5, 1); 0 for an eps that is not a finite number > 0
+inline int prior_gen_refit_scale(float eps) {
+	if (!(eps > 0.f) || !std::isfinite(eps)) return 0;
+	int e = 0;
+	(void)std::frexp((double)eps, &e);
+	return e;
+}
+// The eigenvector of the smallest eigenvalue of the symmetric C = (c00 c01 c02 c11 c12 c22): cyclic Jacobi over the pairs (0,1) (0,2) (1,2),
+// a pair whose off-diagonal is exactly 0 skipped, at most 16 sweeps, ending when all three off-diagonals are 0; the smallest diagonal
+// entry wins, the lowest index on ties.  Every operation is rounded on its own, in the order written.  Returns the sweeps used
+inline int prior_gen_refit_eigvec(const double C[6], double vec[3]) {
+	double a[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+	double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+	static const int pairs[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+	int sweeps = 0;
+	while (sweeps < 16 && !(a[0][1] == 0.0 && a[0][2] == 0.0 && a[1][2] == 0.0)) {
+		++sweeps;
+		for (const auto& pq : pairs) {
+			const int p = pq[0], q = pq[1], r = 3 - p - q;
+			const double apq = a[p][q];
+			if (apq == 0.0) continue;
+			const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+			const double t = std::copysign(1.0, theta) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+			const double c = 1.0 / std::sqrt(t * t + 1.0);
+			const double s = t * c;
+			a[p][p] = a[p][p] - t * apq;
+			a[q][q] = a[q][q] + t * apq;
+			a[p][q] = a[q][p] = 0.0;
+			const double arp = a[r][p], arq = a[r][q];
+			a[r][p] = a[p][r] = c * arp - s * arq;
+			a[r][q] = a[q][r] = s * arp + c * arq;
+			for (int k = 0; k < 3; ++k) {
+				const double vkp = v[k][p], vkq = v[k][q];
+				v[k][p] = c * vkp - s * vkq;
+				v[k][q] = s * vkp + c * vkq;
+			}
+		}
+	}
+	int k = 0;
+	if (a[1][1] < a[k][k]) k = 1;
+	if (a[2][2] < a[k][k]) k = 2;
+	for (int q = 0; q < 3; ++q) vec[q] = v[q][k];
+	return sweeps;
+}
+// mu (3) and C (6: 00 01 02 11 12 22) of the m band samples from the nine sums as they come back: words[2 i] / words[2 i + 1] the high /
+// low parts of sum i (x y z xx xy xz yy yz zz)
+inline void prior_gen_refit_cov(const unsigned long long words[18], uint64_t m, double mu[3], double C[6]) {
+	static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {0, 1, 2, 1, 2, 2};
+	for (int q = 0; q < 3; ++q) mu[q] = prior_gen_mean((int64_t)words[2 * q], words[2 * q + 1], m, kPriorRefitFirstShift);
+	for (int i = 0; i < 6; ++i) C[i] = prior_gen_mean((int64_t)words[6 + 2 * i], words[7 + 2 * i], m, kPriorRefitSecondShift) - mu[pa[i]] * mu[pb[i]];
+}
+// Step 4: the plane (n, d) of the m band samples about the anchor O at the scale E, its normal on the side of prev's.  False: the length
+// is zero or not finite, or d is not finite
+inline bool prior_gen_refit_solve(const unsigned long long words[18], uint64_t m, const double O[3], int E, const float prev[4], float out[4]) {
+	double mu[3], C[6], vec[3];
+	prior_gen_refit_cov(words, m, mu, C);
+	(void)prior_gen_refit_eigvec(C, vec);
+	float x = (float)vec[0], y = (float)vec[1], z = (float)vec[2];
+	const float len = std::sqrt((x * x + y * y) + z * z);
+	if (!(len > 0.f) || !std::isfinite(len)) return false;
+	x = x / len; y = y / len; z = z / len;
+	if ((x * prev[0] + y * prev[1]) + z * prev[2] < 0.f) { x = -x; y = -y; z = -z; }
+	double c[3];
+	for (int q = 0; q < 3; ++q) c[q] = O[q] + std::ldexp(mu[q], E);
+	const float d = (float)(((double)x * c[0] + (double)y * c[1]) + (double)z * c[2]);
+	if (!std::isfinite(d)) return false;
+	out[0] = x; out[1] = y; out[2] = z; out[3] = d;
+	return true;
+}
+
+// The decision sequence of S4r for one round.  The host loop launches the refit kernel for `launch` (at first the winner's plane), reads its
+// record -- the four counts of that plane over the free samples and the nine sums of its e2 band -- and hands it to prior_refit_step, which
+// says whether `launch` now holds a plane to count: R + 1 launches at the most.  Afterwards plane / cnt are the last kept step's (the
+// winner's when none was kept)
+enum PriorRefitStop { kRefitGoesOn = -1, kRefitIters = 0, kRefitBand = 1, kRefitDegenerate = 2, kRefitFixed = 3, kRefitCount = 4 };
+struct PriorRefit {
+	int R = 0, E = 0;
+	int64_t minPoints = 0;
+	double O[3] = {0, 0, 0};
+	float plane[4] = {0, 0, 0, 0}, launch[4] = {0, 0, 0, 0};
+	uint32_t cnt[4] = {0, 0, 0, 0};
+	int solved = 0, kept = 0;
+	bool trial = false; // `launch` is a step's plane that waits for its counts
+	int stop = kRefitGoesOn;
+};
+inline PriorRefit prior_refit_begin(int R, int64_t minPoints, const double O[3], int E, const float winner[4], const int32_t counts[4]) {
+	PriorRefit r;
+	r.R = R; r.E = E; r.minPoints = minPoints;
+	for (int q = 0; q < 3; ++q) r.O[q] = O[q];
+	for (int q = 0; q < 4; ++q) { r.plane[q] = r.launch[q] = winner[q]; r.cnt[q] = (uint32_t)counts[q]; }
+	return r;
+}
+// rec: the kPriorRefitWords words of the launch for r.launch.  True: r.launch holds the next plane to launch for
+inline bool prior_refit_step(PriorRefit& r, const unsigned long long* rec) {
+	if (r.trial) { // step 6
+		if ((int64_t)rec[0] < r.minPoints) { r.stop = kRefitCount; return false; }
+		for (int q = 0; q < 4; ++q) { r.plane[q] = r.launch[q]; r.cnt[q] = (uint32_t)rec[q]; }
+		++r.kept;
+		r.trial = false;
+	}
+	if (r.solved >= r.R) { r.stop = kRefitIters; return false; }
+	const uint64_t m = rec[2]; // step 1: the band is what cnt_2 counts
+	if (m < 3) { r.stop = kRefitBand; return false; }
+	float next[4];
+	if (!prior_gen_refit_solve(rec + 4, m, r.O, r.E, r.plane, next)) { r.stop = kRefitDegenerate; return false; }
+	++r.solved;
+	if (memcmp(next, r.plane, sizeof next) == 0) { r.stop = kRefitFixed; return false; } // step 5
+	for (int q = 0; q < 4; ++q) r.launch[q] = next[q];
+	r.trial = true;
+	return true;
 }
 
 } // namespace hcmvs

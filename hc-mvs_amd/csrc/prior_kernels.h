@@ -17,12 +17,15 @@ struct PriorGenTrace {
 	PriorGenLayout lay;
 	std::vector<int32_t> rounds; // 6 per round: winner or -1, cnt_0 .. cnt_3, valid candidates
 	std::vector<int32_t> clusters; // 4 per round (S4c): occupied cells, components, size of the largest, accepted; zeros without a winner
+	std::vector<int32_t> refits;   // 6 per round (S4r): steps solved, steps kept, cnt_0 .. cnt_3 of the final plane; zeros without a winner
+	std::vector<float> refitPlanes; // 4 per round: the final n, d; zeros without a winner
+	hcmvs_plane_prior_refit_stats refitStats = {0, 0}; // what hcmvs_get_plane_prior_refit_stats reads
 };
 
 // DESIGN.md section 5, D13.  region: the view's region mask as the ignore-mask kernel writes it (u8 per pixel, 0 = INSIDE the region), or
 // null (no region).  The arguments have passed prior_gen_check.  All device pointers; planes (64 entries, or null) and st are the host's.
-// Waits for the stream several times (stage sizes, one winner per round -- with clustering one more per round that has a winner --, the
-// plane reductions).  0 = ok, 2 = device failure (err says which)
+// Waits for the stream several times (stage sizes, one winner per round -- with clustering one more per round that has a winner, with
+// refit_iters > 0 up to refit_iters + 1 more --, the plane reductions).  0 = ok, 2 = device failure (err says which)
 int generate_plane_prior_device(int w, int h, const double K[9], const uint8_t* region, const float* depth, const float* normal, const float* conf,
                                 const hcmvs_plane_prior_params& p, float* prior, float* priorNormal, hcmvs_prior_plane* planes, hcmvs_plane_prior_stats& st,
                                 DevBuf& scratch, PriorGenTrace& trace, hipStream_t s, std::string& err);

@@ -15,6 +15,9 @@
  *     lane in registers and walks the 4 KiB candidate table, which is uniform across the wave (scalar loads): four ballots and
  *     popcounts per candidate, added by one lane into LDS counters of the workgroup, then one integer global atomic per non-zero
  *     counter and workgroup.  One workgroup ranks the counters; only the winner (a few words) travels to the host.
+ * S4r (refit_iters > 0) the winner is refitted by total least squares over its inliers in the eps / 4 band: one kernel gives a plane's four
+ *     counts and the nine moment sums of its band as exact integers (registers, wave shuffles, LDS, integer atomics), the host solves the
+ *     3 x 3 eigenproblem (prior_gen_plan.h) and the next plane goes back as kernel arguments; at most refit_iters + 1 launches a round.
  * S4c (cluster_mul > 0) the winner's inliers keep their largest connected component on a grid of cells in the plane: cell keys, a radix
  *     sort (hipcub), the distinct cells, a union-find over them (neighbours by binary search), integer sizes, one packed maximum; the
  *     arrays live in the scratch of the neighbour search, which is idle during S4.  A 16-byte record travels to the host.
@@ -42,9 +45,9 @@ __host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long 
 	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
 	return z ^ (z >> 31);
 }
-__device__ __forceinline__ double draw(unsigned long long a, unsigned long long k) { return (double)(mix64(a + k * 0xD1B54A32D192ED03ull) >> 11) * 0x1p-53; }
+__host__ __device__ __forceinline__ double draw(unsigned long long a, unsigned long long k) { return (double)(mix64(a + k * 0xD1B54A32D192ED03ull) >> 11) * 0x1p-53; }
 // floor(U * n) kept below n
-__device__ __forceinline__ unsigned long long draw_below(unsigned long long a, unsigned long long k, unsigned long long n) {
+__host__ __device__ __forceinline__ unsigned long long draw_below(unsigned long long a, unsigned long long k, unsigned long long n) {
 	const unsigned long long v = (unsigned long long)(draw(a, k) * (double)n);
 	return v < n ? v : n - 1;
 }
@@ -298,6 +301,65 @@ __global__ __launch_bounds__(kBlockSize) void assign_kernel(unsigned n0, const f
 		const float* N = nrm + 3 * (size_t)i; const float* P = xyz + 3 * (size_t)i;
 		if (fabsf(dot3(nx, ny, nz, N[0], N[1], N[2])) >= normalThr && fabsf(dot3(nx, ny, nz, P[0], P[1], P[2]) - d) <= eps) assigned[i] = plane;
 	}
+}
+
+// ---- S4r ----
+// One pass over the fitting set for one plane: its four counts, as score_kernel counts them, and the nine moment sums of its e2 band about
+// the anchor O at the scale 2^-E, as exact integers (two words each: high and low part of every addend).  Registers, wave shuffles of
+// 64-bit integers, LDS, one integer global atomic per non-zero word and workgroup: the result does not depend on the order.
+// rec: kPriorRefitWords words -- 0..3 cnt_0 .. cnt_3, 4..21 hi / lo of the sums x y z xx xy xz yy yz zz, 22 / 23 the anchor as the host
+// reads it (the float32 bits of x | y << 32, of z): the host knows the anchor's index from the counter stream, not its position.
+// inv = 2^-E
+constexpr int kRefitUsed = 22;
+__global__ void refit_reset_kernel(unsigned long long* rec) {
+	if (threadIdx.x < kPriorRefitWords) rec[threadIdx.x] = 0ull;
+}
+__global__ __launch_bounds__(kBlockSize) void refit_moments_kernel(unsigned n0, const float* __restrict__ xyz, const float* __restrict__ nrm, const int32_t* __restrict__ assigned,
+                                                                   float4 pl, float normalThr, float eps, unsigned anchor, double inv, unsigned long long* rec) {
+	__shared__ unsigned long long sh[kRefitUsed];
+	if (threadIdx.x < kRefitUsed) sh[threadIdx.x] = 0ull;
+	__syncthreads();
+	const float ax = xyz[3 * (size_t)anchor], ay = xyz[3 * (size_t)anchor + 1], az = xyz[3 * (size_t)anchor + 2]; // anchor < n0 (draw_below)
+	const double o[3] = {(double)ax, (double)ay, (double)az};
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		rec[22] = (unsigned long long)__float_as_uint(ax) | (unsigned long long)__float_as_uint(ay) << 32;
+		rec[23] = (unsigned long long)__float_as_uint(az);
+	}
+	const float e0 = eps, e1 = eps * 0.5f, e2 = eps * 0.25f, e3 = eps * 0.125f;
+	unsigned long long acc[kRefitUsed];
+#pragma unroll
+	for (int q = 0; q < kRefitUsed; ++q) acc[q] = 0ull;
+	for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += gridDim.x * blockDim.x) {
+		if (assigned[i] >= 0) continue;
+		const float* N = nrm + 3 * (size_t)i; const float* P = xyz + 3 * (size_t)i;
+		if (!(fabsf(dot3(pl.x, pl.y, pl.z, N[0], N[1], N[2])) >= normalThr)) continue;
+		const float r = fabsf(dot3(pl.x, pl.y, pl.z, P[0], P[1], P[2]) - pl.w);
+		if (!(r <= e0)) continue;
+		acc[0] += 1ull; acc[1] += r <= e1 ? 1ull : 0ull; acc[3] += r <= e3 ? 1ull : 0ull;
+		if (!(r <= e2)) continue;
+		acc[2] += 1ull;
+		double sv[3];
+#pragma unroll
+		for (int q = 0; q < 3; ++q) {
+			const double v = ((double)P[q] - o[q]) * inv;
+			sv[q] = v < 1048576.0 ? (v > -1048576.0 ? v : -1048575.0) : 1048575.0; // saturated inside (-2^20, 2^20)
+			const long long fx = (long long)rint(sv[q] * 0x1p24);
+			acc[4 + 2 * q] += (unsigned long long)(fx >> 32); acc[5 + 2 * q] += (unsigned long long)fx & 0xffffffffull;
+		}
+		const double pr[6] = {sv[0] * sv[0], sv[0] * sv[1], sv[0] * sv[2], sv[1] * sv[1], sv[1] * sv[2], sv[2] * sv[2]};
+#pragma unroll
+		for (int q = 0; q < 6; ++q) {
+			const long long fx = (long long)rint(pr[q] * 0x1p20); // |s_a s_b| < 2^40: below 2^60
+			acc[10 + 2 * q] += (unsigned long long)(fx >> 32); acc[11 + 2 * q] += (unsigned long long)fx & 0xffffffffull;
+		}
+	}
+#pragma unroll
+	for (int q = 0; q < kRefitUsed; ++q) {
+		const unsigned long long v = wave_sum(acc[q]);
+		if ((threadIdx.x & 63) == 0 && v) atomicAdd(&sh[q], v);
+	}
+	__syncthreads();
+	if (threadIdx.x < kRefitUsed && sh[threadIdx.x]) atomicAdd(&rec[threadIdx.x], sh[threadIdx.x]);
 }
 
 __device__ __forceinline__ unsigned long long ordered(double v) {
@@ -734,32 +796,79 @@ int generate_plane_prior_device(int w, int h, const double K[9], const uint8_t* 
 		if (hipGetLastError() != hipSuccess) return false;
 		return hipMemcpyAsync(row, cRec + kClusterRecOut, 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
 	};
+	// S4r: with refit_iters > 0 the winner is refitted before S4c and before anything is assigned: at most refit_iters + 1 launches of the
+	// refit kernel and as many waits per round that has a winner, then the final plane goes into the winner record and the round ends as it
+	// does without (assign_kernel, or the chain of S4c).  With refit_iters = 0 nothing of this is launched
+	const int refitIters = p.refit_iters;
+	const int refitE = prior_gen_refit_scale(eps);
+	unsigned long long* rRec = (unsigned long long*)(b + prior_gen_refit_scratch(lay).rec.off);
+	std::vector<float> finalPlanes; // what the winner record is overwritten from: alive until the stream has been waited for
+	if (refitIters > 0) finalPlanes.resize((size_t)4 * p.max_rounds);
+	auto refit_round = [&](int round, const int32_t hwin[12], PriorRefit& rf) {
+		float wp[4];
+		memcpy(wp, hwin + 8, 16);
+		const unsigned anchor = (unsigned)draw_below(mix64((unsigned long long)p.seed ^ mix64((unsigned long long)round * kPriorCandidates + (unsigned long long)hwin[0])), 0, n0);
+		const double none[3] = {0, 0, 0}; // (the anchor's position comes back with every record, the first included)
+		rf = prior_refit_begin(refitIters, minPoints, none, refitE, wp, hwin + 1);
+		const double inv = std::ldexp(1.0, -refitE);
+		unsigned long long rec[kPriorRefitWords];
+		for (;;) {
+			hipLaunchKernelGGL(refit_reset_kernel, dim3(1), dim3(64), 0, s, rRec);
+			hipLaunchKernelGGL(refit_moments_kernel, dim3(blocks_for(n0, kScoreMaxBlocks)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, assigned,
+			                   make_float4(rf.launch[0], rf.launch[1], rf.launch[2], rf.launch[3]), p.normal_threshold, eps, anchor, inv, rRec);
+			if (hipGetLastError() != hipSuccess) return false;
+			if (hipMemcpyAsync(rec, rRec, sizeof rec, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+			const uint32_t ob[3] = {(uint32_t)rec[22], (uint32_t)(rec[22] >> 32), (uint32_t)rec[23]};
+			for (int q = 0; q < 3; ++q) { float v; memcpy(&v, &ob[q], 4); rf.O[q] = (double)v; }
+			if (!prior_refit_step(rf, rec)) break;
+		}
+		if (rf.kept > 0) { // the record holds the candidate's plane: the rest of the round reads the final one
+			float* fp = finalPlanes.data() + 4 * (size_t)round;
+			memcpy(fp, rf.plane, 16);
+			if (hipMemcpyAsync((float*)winner + 8, fp, 16, hipMemcpyHostToDevice, s) != hipSuccess) return false;
+		}
+		return true;
+	};
+	const bool deferred = chain || refitIters > 0; // the round's winner is waited for before anything is assigned
 	while (unassigned >= minPoints && (int)found.size() < HCMVS_MAX_PRIOR_PLANES && rounds < p.max_rounds && fails < failLimit) {
 		hipLaunchKernelGGL(candidate_kernel, dim3(1), dim3(kPriorCandidates), 0, s, (unsigned)rounds, (unsigned long long)p.seed, n0, w, h, dLevels, nLevels, xyzA, nrmA, pixA,
 		                   sampleAt, assigned, p.normal_threshold, cand, counts);
 		hipLaunchKernelGGL(score_kernel, dim3(blocks_for(n0, kScoreMaxBlocks)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, assigned, cand, p.normal_threshold, eps, counts);
 		hipLaunchKernelGGL(winner_kernel, dim3(1), dim3(kPriorCandidates), 0, s, cand, counts, (unsigned long long)minPoints, winner);
-		if (!chain) hipLaunchKernelGGL(assign_kernel, dim3(blocks_for(n0, 2048)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, winner, p.normal_threshold, eps, (int32_t)found.size(), assigned);
+		if (!deferred) hipLaunchKernelGGL(assign_kernel, dim3(blocks_for(n0, 2048)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, winner, p.normal_threshold, eps, (int32_t)found.size(), assigned);
 		int32_t hwin[12];
 		if (hipMemcpyAsync(hwin, winner, sizeof hwin, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("a round failed");
 		for (int q = 0; q < 6; ++q) trace.rounds.push_back(hwin[q]);
 		st.candidates_valid += (uint64_t)hwin[5];
-		++rounds;
+		const int round = rounds++;
 		int32_t row[4] = {0, 0, 0, 0}; // occupied cells, components, the largest size, accepted
+		int32_t rrow[6] = {0, 0, 0, 0, 0, 0}; // S4r: steps solved, steps kept, the final plane's counts
+		float fin[4] = {0.f, 0.f, 0.f, 0.f};  // the round's final plane
 		if (hwin[0] >= 0) {
-			row[1] = clustering ? 1 : 0; row[2] = hwin[1]; row[3] = 1; // unclustered: all inliers are the plane
-			float wn[3];
-			memcpy(wn, hwin + 8, 12);
-			if (chain && !cluster_round(wn, (int32_t)found.size(), row)) return fail("clustering a round's winner failed");
+			memcpy(fin, hwin + 8, 16);
+			for (int q = 0; q < 4; ++q) rrow[2 + q] = hwin[1 + q];
+			if (refitIters > 0) {
+				PriorRefit rf;
+				if (!refit_round(round, hwin, rf)) return fail("refitting a round's winner failed");
+				memcpy(fin, rf.plane, 16);
+				rrow[0] = rf.solved; rrow[1] = rf.kept;
+				for (int q = 0; q < 4; ++q) rrow[2 + q] = (int32_t)rf.cnt[q];
+				if (rf.kept > 0) { ++trace.refitStats.refit_rounds; trace.refitStats.refit_steps += rf.kept; }
+			}
+			row[1] = clustering ? 1 : 0; row[2] = rrow[2]; row[3] = 1; // unclustered: all inliers are the plane
+			if (chain) { if (!cluster_round(fin, (int32_t)found.size(), row)) return fail("clustering a round's winner failed"); }
+			else if (deferred) hipLaunchKernelGGL(assign_kernel, dim3(blocks_for(n0, 2048)), dim3(kBlockSize), 0, s, n0, xyzA, nrmA, winner, p.normal_threshold, eps, (int32_t)found.size(), assigned);
 		}
 		for (int q = 0; q < 4; ++q) trace.clusters.push_back(row[q]);
+		for (int q = 0; q < 6; ++q) trace.refits.push_back(rrow[q]);
+		for (int q = 0; q < 4; ++q) trace.refitPlanes.push_back(fin[q]);
 		if (row[3]) {
 			Found f;
-			memcpy(f.n, hwin + 8, 12);
+			memcpy(f.n, fin, 12);
 			f.cnt0 = (uint32_t)row[2];
 			found.push_back(f);
 			unassigned -= row[2];
-			st.cluster_left += (uint64_t)(hwin[1] - row[2]);
+			st.cluster_left += (uint64_t)(rrow[2] - row[2]);
 			fails = 0;
 		} else {
 			if (hwin[0] >= 0) ++st.cluster_rejects;

@@ -18,7 +18,8 @@
  * the estimates of its source views' own maps from outer iteration 1 on (DepthMap.cpp:1504-1608; default 0 here, 1 in the reference, so
  * that existing command lines keep their results; one device); --plane-priors 1 generates depth priors from planes fitted inside the
  * label 255 of seman/<stem>.quad.pgm|ppm on outer iteration n - 2 (--export-priors <dir> writes them; --plane-clusters 1 keeps the largest
- * connected component of a plane's inliers, on cells of --ransac-cluster average spacings);
+ * connected component of a plane's inliers, on cells of --ransac-cluster average spacings; --plane-refit n refits the winning plane of
+ * every round by n least-squares steps);
  * --geo-consistency 1 blends every view score with a reprojection term against the source views' maps of the previous outer iteration
  * (fed by --n-para_tapa, --n-para_tapa2, --n-txthreshold, --n-txthreshold2, --n-photo2geo, --geo-max-px; one device; D14);
  * optical flow, --use-semantic, --n-usegeoconsistency and SGM modes are not available and the corresponding flags are accepted and ignored with a note.
@@ -602,6 +603,11 @@ bool generate_plane_prior(Run& r, hcmvs_ctx* dctx, ImageData& im, const hcmvs_ba
 	if (r.o.verbosity > 1 && pp.cluster_mul > 0.f)
 		printf("Plane clusters of image %3u: %d planes, %d rounds rejected, %llu inliers left (cell %g)\n", im.id, st.planes, st.cluster_rejects,
 		       (unsigned long long)st.cluster_left, (double)st.cluster_eps);
+	if (r.o.verbosity > 1 && pp.refit_iters > 0) {
+		hcmvs_plane_prior_refit_stats rs = {0, 0};
+		(void)hcmvs_get_plane_prior_refit_stats(dctx, &rs);
+		printf("Plane refit of image %3u: %d of %d rounds refitted, %d steps kept\n", im.id, rs.refit_rounds, st.rounds, rs.refit_steps);
+	}
 	if (!r.o.exportPriors.empty()) {
 		DmapImage hd = im.file_header();
 		if (!save_dmap(export_prior_path(r.o, im.id), hd, im.prior.data(), nullptr, nullptr)) { err = "can not write '" + export_prior_path(r.o, im.id) + "'"; return false; }
@@ -1100,6 +1106,7 @@ bool set_prior_regions(Run& r) {
 		printf("Plane priors: %zu of %zu images to estimate have a label image; probability %g, epsilon %g, min-points %g, seed %llu\n", nRegions, r.work.size(),
 		       (double)o.ransacProbability, (double)o.ransacEpsilon, (double)o.ransacMinPoints, o.sampleSeed);
 	if (o.verbosity > 1 && o.planeClusters) printf("Plane clusters: a plane keeps the largest connected component of its inliers, cells of %g average spacings\n", (double)o.ransacCluster);
+	if (o.verbosity > 1 && o.planeRefit) printf("Plane refit: the winning plane of a round is refitted by %d least-squares steps over its inliers in a quarter of the band\n", o.planeRefit);
 	return true;
 }
 // --depth-priors <folder>: <folder>/depth%04u.prior.dmap per image that is estimated, a raw 'DR' depth map of the image's size at the run's

@@ -74,6 +74,8 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	int planeClusters = 0;        // --plane-clusters 1 (with --plane-priors 1): a plane keeps the largest connected component of its inliers, on cells of
 	                              // --ransac-cluster average spacings; 0 keeps the results of command lines written before it
 	float ransacCluster = 10.f;   // --ransac-cluster (the reference's default; the authors run 7): read and unused without --plane-clusters 1
+	int planeRefit = 0;           // --plane-refit n (with --plane-priors 1), 0 .. 16: least-squares steps on the winner of every round of the plane detection, over
+	                              // its inliers in the eps / 4 band; 0 keeps the results of command lines written before it
 	int device = 0, batch = 32;   // reference images per launch: 32 is the measured optimum (profiles/r02_knobs.txt); lowered when HBM is short
 	std::vector<int> devices;     // --devices 0,1,...: one context + host thread per entry; reference images sharded over them by their position in
 	                              // the fusion order (k mod N); post-filters and fusion on the first (an ordinal may repeat: two contexts on one GPU)
@@ -107,6 +109,8 @@ static const char* const kPlaneClusterOptions[] = {"--plane-clusters"};
 // ... and the geometric-consistency term's own (a fourth table; --n-para_tapa, --n-para_tapa2, --n-txthreshold, --n-txthreshold2 and
 // --n-photo2geo, which feed it, are the reference's and stand in kKnownOptions)
 static const char* const kGeoOptions[] = {"--geo-consistency", "--geo-max-px"};
+// ... and the refit of the winning plane of the generated priors (a fifth table, for the same reason as the third)
+static const char* const kPlaneRefitOptions[] = {"--plane-refit"};
 
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
@@ -130,6 +134,9 @@ static const char* const kUsage =
 	"       --plane-clusters 0|1 with --plane-priors 1: a plane keeps only the largest connected component of its inliers, on a grid of cells of\n"
 	"                            --ransac-cluster average spacings (default 10) in the plane, so that two coplanar surfaces with something else between\n"
 	"                            them become two planes (default 0: --ransac-cluster is read and unused, the results of earlier command lines)\n"
+	"       --plane-refit n      with --plane-priors 1: the winning plane of every round of the detection is refitted by n least-squares steps over its\n"
+	"                            inliers within a quarter of the --ransac-epsilon band, before its inliers are assigned or clustered (0 .. 16; default 0:\n"
+	"                            the plane is the best of the candidates spanned by three samples, the results of earlier command lines)\n"
 	"       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
 	"                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 	"                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
@@ -157,6 +164,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		for (const char* k : kPriorOptions) known = known || a == k;
 		for (const char* k : kPlaneClusterOptions) known = known || a == k;
 		for (const char* k : kGeoOptions) known = known || a == k;
+		for (const char* k : kPlaneRefitOptions) known = known || a == k;
 		if (!known) { err = "unrecognised option '" + a + "'"; return PARSE_ERROR; }
 		if (!haveVal) { // the value is the next argument, whatever it starts with (negative numbers are values)
 			if (i + 1 >= argc) { err = "the required argument for option '" + a + "' is missing"; return PARSE_ERROR; }
@@ -186,6 +194,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (kv.count("--export-priors")) o.exportPriors = kv["--export-priors"];
 	getf("--ransac-probability", o.ransacProbability); getf("--ransac-epsilon", o.ransacEpsilon); getf("--ransac-min-points", o.ransacMinPoints);
 	geti("--plane-clusters", o.planeClusters); getf("--ransac-cluster", o.ransacCluster);
+	geti("--plane-refit", o.planeRefit);
 	geti("--geo-consistency", o.geoConsistency); getf("--geo-max-px", o.geoMaxPx);
 	getf("--n-para_tapa", o.paraTapa); getf("--n-para_tapa2", o.paraTapa2); getf("--n-txthreshold", o.txThreshold); getf("--n-txthreshold2", o.txThreshold2);
 	geti("--device", o.device); geti("--batch", o.batch);
@@ -220,6 +229,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (!o.exportPriors.empty() && !o.planePriors) { err = "--export-priors writes the priors that --plane-priors 1 generates: give both"; return PARSE_ERROR; }
 	if (o.planeClusters != 0 && o.planeClusters != 1) { err = "--plane-clusters expects 0 or 1"; return PARSE_ERROR; }
 	if (o.planeClusters && !o.planePriors) { err = "--plane-clusters 1 clusters the inliers of the planes that --plane-priors 1 fits: give both"; return PARSE_ERROR; }
+	if (o.planeRefit < 0 || o.planeRefit > 16) { err = "--plane-refit expects a number of steps from 0 to 16"; return PARSE_ERROR; }
+	if (o.planeRefit && !o.planePriors) { err = "--plane-refit refits the planes that --plane-priors 1 fits: give both"; return PARSE_ERROR; }
 	if (o.planePriors) {
 		if (!o.depthPriors.empty()) { err = "--plane-priors 1 is not combined with --depth-priors (an image has one prior: generated or supplied)"; return PARSE_ERROR; }
 		if (o.restoreHypothesis) { err = "--plane-priors 1 is not combined with --restore-hypothesis 1 (the prior term does not come with the hint)"; return PARSE_ERROR; }
@@ -555,6 +566,7 @@ inline std::string export_prior_path(const Options& o, uint32_t id) { return sce
 inline hcmvs_plane_prior_params plane_prior_params(const Options& o, hcmvs_plane_prior_params p) {
 	p.region_label = 255; p.probability = o.ransacProbability; p.epsilon_mul = o.ransacEpsilon; p.min_points_div = o.ransacMinPoints; p.seed = o.sampleSeed;
 	p.cluster_mul = o.planePriors && o.planeClusters ? o.ransacCluster : 0.f; // --plane-clusters 1: --ransac-cluster is the cell edge in average spacings
+	p.refit_iters = o.planePriors ? o.planeRefit : 0;                         // --plane-refit n: least-squares steps on every round's winner
 	return p;
 }
 inline std::string prior_path(const Options& o, uint32_t id) { return sceneio::map_path(o.depthPriors, "/depth%04u.prior.dmap", id); }

@@ -296,6 +296,9 @@ typedef struct {
 	uint64_t seed;          /* of the counter-based candidate stream */
 	float cluster_mul;      /* 0 (off), --ransac-cluster: a plane keeps the largest connected component of its inliers on a grid of cells of
 	                           average spacing * cluster_mul in the plane; finite and >= 0 */
+	int32_t refit_iters;    /* 0 (off), --plane-refit, 0 .. 16: total-least-squares steps on the winner of a round over its inliers in the
+	                           eps / 4 band, before the clustering and before anything is assigned.  It lies in
+	                           what was the struct's tail padding: the size of the struct is what it was */
 } hcmvs_plane_prior_params;
 void hcmvs_default_plane_prior_params(hcmvs_plane_prior_params* p);
 /* The region of view `id` in which planes are fitted: the pixels whose label equals region_label, from a 16-bit label image of any
@@ -305,7 +308,7 @@ int hcmvs_set_prior_region(hcmvs_ctx* ctx, uint32_t id, const uint16_t* labels, 
 /* region: w*h bytes, 1 = inside (all 0 without a region) */
 int hcmvs_get_prior_region(hcmvs_ctx* ctx, uint32_t id, uint8_t* region);
 typedef struct {
-	float normal[3];       /* unit normal, camera frame, as the candidate had it */
+	float normal[3];       /* unit normal, camera frame: the final normal of its round -- the candidate's, with refit_iters > 0 the last kept step's */
 	uint32_t n_inliers;    /* the samples assigned to the plane: cnt_0, with clustering the size of the component that was kept */
 	double centre[3];      /* centroid of the inliers, camera frame */
 	double quad[8];        /* image quad x0 y0 .. x3 y3: lower-left, lower-right, upper-right, upper-left of the plane frame */
@@ -328,6 +331,12 @@ typedef struct {
 	int32_t cluster_rejects;   /* rounds whose winner was rejected: its largest component was smaller than min_points */
 	uint64_t cluster_left;     /* inliers that clustering left unassigned, summed over the accepted rounds */
 } hcmvs_plane_prior_stats;
+/* The counters of the refit (refit_iters, S4r).  They are a struct of their own, read with hcmvs_get_plane_prior_refit_stats:
+ * hcmvs_plane_prior_stats keeps the size and the last field its callers were built against. */
+typedef struct {
+	int32_t refit_rounds;      /* rounds with at least one kept refit step (0 with refit_iters = 0) */
+	int32_t refit_steps;       /* kept refit steps, summed over the rounds */
+} hcmvs_plane_prior_refit_stats;
 /* The prior of view `id` from its maps in DEVICE memory in the state an estimate leaves between outer iterations (d_conf = the score,
  * lower is better), which are read and never written: every pixel of d_prior (w*h floats) is written, 0 outside the region and where
  * no plane applies; d_prior_normal (w*h*3 floats, or NULL) gets the plane normal turned towards the camera, 0 where the prior is 0.
@@ -337,7 +346,8 @@ typedef struct {
  * Success with an all-zero prior and no plane: no region registered, no region pixel, fewer than n_neighbors + 1 samples at any stage.
  * HCMVS_ERR_INVALID before anything reaches the device: a null pointer, an unknown view, a K whose last row is not 0 0 1 or that
  * cannot be inverted, probability outside (0, 1), min_points_div / epsilon_mul not > 0 and finite, n_neighbors outside 3 .. 31,
- * max_rounds outside 1 .. 4096, cluster_mul negative, NaN or infinite, an output overlapping an input map or the other output. */
+ * max_rounds outside 1 .. 4096, cluster_mul negative, NaN or infinite, refit_iters outside 0 .. 16, an output overlapping an input map
+ * or the other output. */
 int hcmvs_generate_plane_prior_device(hcmvs_ctx* ctx, uint32_t id, const float* d_depth, const float* d_normal, const float* d_conf,
                                       const hcmvs_plane_prior_params* params, float* d_prior, float* d_prior_normal,
                                       hcmvs_prior_plane* planes, hcmvs_plane_prior_stats* stats);
@@ -354,6 +364,13 @@ int hcmvs_get_plane_prior_trace(hcmvs_ctx* ctx, uint8_t* stage, int32_t* assignm
  * *n_rounds = the rounds run.  A round without a winner is all zeros; with clustering off a round with a winner is 0, 0, cnt_0, 1 (and
  * 0, 1, cnt_0, 1 when the cell edge is not a finite number > 0: all inliers are one component). */
 int hcmvs_get_plane_prior_cluster_trace(hcmvs_ctx* ctx, int32_t* clusters, int32_t capacity, int32_t* n_rounds);
+/* TEST SURFACE.  What the refit (refit_iters, S4r) decided in every round of the same call, into HOST buffers (each may be NULL): steps, 6
+ * int32 per round run -- steps solved, steps kept, cnt_0 .. cnt_3 of the round's final plane --, and planes, 4 floats per round run -- the
+ * final n, d; at most `capacity` rounds are written, *n_rounds = the rounds run.  A round without a winner is all zeros; with
+ * refit_iters = 0 a round with a winner is 0, 0, the candidate's counts and the candidate's plane. */
+int hcmvs_get_plane_prior_refit_trace(hcmvs_ctx* ctx, int32_t* steps, float* planes, int32_t capacity, int32_t* n_rounds);
+/* the refit's counters of the last hcmvs_generate_plane_prior_device of the context (zeros before the first call and after a failed one) */
+int hcmvs_get_plane_prior_refit_stats(hcmvs_ctx* ctx, hcmvs_plane_prior_refit_stats* out);
 
 /* SceneDensify.cpp:783-808: splat n_points sparse world points (xyz f32) seen by view `id` as 5x5 blocks
  * into host maps depth (w*h) / normal (w*h*3); returns the depth range (min*0.9, max*1.1). Host-side helper. */
