@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhcmvs_hip.so")
 
-OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_TIMEOUT, ERR_CAPACITY = range(6)
+OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_TIMEOUT, ERR_CAPACITY, ERR_INTERNAL = range(7)
 
 
 class Params(C.Structure):
@@ -86,6 +86,18 @@ class HandoffStats(C.Structure):
     _fields_ = [("n_pixels", C.c_uint64), ("n_valid", C.c_uint64), ("n_clamped", C.c_uint64), ("n_rescaled", C.c_uint64),
                 ("n_items", C.c_int32), ("n_empty", C.c_int32), ("ms_device", C.c_float)]
 
+
+class SpeckleItem(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("d_depth", C.c_void_p), ("d_normal", C.c_void_p), ("d_conf", C.c_void_p),
+                ("d_labels", C.c_void_p)]
+
+
+class SpeckleStats(C.Structure):
+    _fields_ = [("n_valid", C.c_uint64), ("n_removed", C.c_uint64), ("n_segments", C.c_uint64), ("n_small", C.c_uint64),
+                ("largest", C.c_uint32), ("ms_device", C.c_float), ("device_bytes", C.c_uint64)]
+
+
+SPECKLE_DIFF = float(np.float32(0.01) * np.float32(0.7))   # upstream's threshold: 0.01f * 0.7f, the product taken in float
 
 HANDOFF_INIT, HANDOFF_HINT = 0, 1           # hcmvs_handoff_maps*: mode
 HANDOFF_OK, HANDOFF_EMPTY = 0, 1            # ... an item's status
@@ -179,6 +191,7 @@ SYMBOLS = ["hcmvs_default_params", "hcmvs_create", "hcmvs_destroy", "hcmvs_last_
            "hcmvs_estimate_point_normals", "hcmvs_point_cloud_filter", "hcmvs_sample_mesh", "hcmvs_default_view_select_params", "hcmvs_select_views",
            "hcmvs_postfilter", "hcmvs_postfilter_sequence", "hcmvs_resize_area_up",
            "hcmvs_handoff_maps", "hcmvs_handoff_maps_device", "hcmvs_get_handoff_stats",
+           "hcmvs_remove_speckles", "hcmvs_remove_speckles_batch_device",
            "hcmvs_set_ignore_mask", "hcmvs_set_ignore_mask_device", "hcmvs_get_ignore_mask",
            "hcmvs_set_viewspread", "hcmvs_set_spread_maps_device", "hcmvs_get_spread_stats",
            "hcmvs_default_geo_params", "hcmvs_set_geo_params", "hcmvs_get_geo_stats",
@@ -267,6 +280,39 @@ def handoff_maps(maps, mode):
     return res
 
 
+def _speckle_stats(st):
+    return {k: getattr(st, k) for k, _ in SpeckleStats._fields_}
+
+
+def remove_speckles_raw(w, h, depth, normal, conf, labels, thr, speckle_size):
+    """hcmvs_remove_speckles on addresses of HOST buffers (0 / None: not given).  Returns (status of the call, stats dict); nothing raises,
+    so a refusal can be looked at"""
+    st = SpeckleStats()
+    rc = lib().hcmvs_remove_speckles(int(w), int(h), depth or None, normal or None, conf or None, labels or None, C.c_float(thr), int(speckle_size),
+                                     C.byref(st))
+    return rc, _speckle_stats(st)
+
+
+def remove_speckles(depth, normal=None, conf=None, thr=None, speckle_size=100, want_labels=True):
+    """hcmvs_remove_speckles: the speckle filter on host arrays, no context (pure host code; what the device form is pinned to).  Segments
+    of valid depths (4-neighbours joined when similar within thr from both sides) with fewer than speckle_size pixels lose depth, normal
+    and conf.  thr None: upstream's 0.01f * 0.7f.  The arrays given are left alone; returns dict(depth, normal, conf (None where not
+    given), labels (the canonical label of every pixel before the removal, -1 where not valid; None when not wanted), stats)"""
+    d = np.array(depth, np.float32, order="C")
+    if d.ndim != 2:
+        raise ValueError("remove_speckles: depth (h, w) expected")
+    n = None if normal is None else np.array(normal, np.float32, order="C")
+    c = None if conf is None else np.array(conf, np.float32, order="C")
+    if (n is not None and n.shape != d.shape + (3,)) or (c is not None and c.shape != d.shape):
+        raise ValueError("remove_speckles: normal (h, w, 3) and conf (h, w) expected")
+    lab = np.empty(d.shape, np.int32) if want_labels else None
+    rc, st = remove_speckles_raw(d.shape[1], d.shape[0], d.ctypes.data, None if n is None else n.ctypes.data, None if c is None else c.ctypes.data,
+                                 None if lab is None else lab.ctypes.data, SPECKLE_DIFF if thr is None else thr, speckle_size)
+    if rc != 0:
+        raise HcmvsError(rc, "remove_speckles: refused (size, threshold or overlapping buffers)")
+    return dict(depth=d, normal=n, conf=c, labels=lab, stats=st)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -344,6 +390,8 @@ def lib():
         L.hcmvs_handoff_maps.argtypes = [C.POINTER(HandoffItem), C.c_int32, C.c_int32]
         L.hcmvs_handoff_maps_device.argtypes = [vp, C.POINTER(HandoffItem), C.c_int32, C.c_int32]
         L.hcmvs_get_handoff_stats.argtypes = [vp, C.POINTER(HandoffStats)]
+        L.hcmvs_remove_speckles.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_uint32, C.POINTER(SpeckleStats)]
+        L.hcmvs_remove_speckles_batch_device.argtypes = [vp, C.POINTER(SpeckleItem), C.c_int32, C.c_float, C.c_uint32, C.POINTER(SpeckleStats)]
         L.hcmvs_set_viewspread.argtypes = [vp, C.c_int32]
         L.hcmvs_set_spread_maps_device.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.hcmvs_get_spread_stats.argtypes = [vp, C.POINTER(SpreadStats)]
@@ -585,6 +633,22 @@ class Context:
         arr = _handoff_items(items)
         self._chk(lib().hcmvs_handoff_maps_device(self._h, arr, len(items), _handoff_mode(mode)))
         return _handoff_results(arr, len(items))
+
+    def remove_speckles_device(self, items, thr=None, speckle_size=100):
+        """hcmvs_remove_speckles_batch_device: the speckle filter (binding.remove_speckles states the rule) over a batch of 1..64 maps of any
+        mix of sizes in DEVICE memory, in place, in one set of launches on the context's stream.  items: list of dicts(width, height,
+        d_depth[, d_normal, d_conf, d_labels]): addresses, e.g. tensor.data_ptr(); d_labels (int32, width * height) receives the canonical
+        labels as before the removal.  thr None: upstream's 0.01f * 0.7f.  The call waits for the stream once.  Returns the stats of the
+        call, summed over its maps, as a dict"""
+        arr = (SpeckleItem * max(len(items), 1))()
+        for a, it in zip(arr, items):
+            a.width, a.height = int(it["width"]), int(it["height"])
+            a.d_depth = it.get("d_depth") or None; a.d_normal = it.get("d_normal") or None
+            a.d_conf = it.get("d_conf") or None; a.d_labels = it.get("d_labels") or None
+        st = SpeckleStats()
+        self._chk(lib().hcmvs_remove_speckles_batch_device(self._h, arr if items is not None else None, len(items), C.c_float(SPECKLE_DIFF if thr is None else thr),
+                                                           int(speckle_size), C.byref(st)))
+        return _speckle_stats(st)
 
     def handoff_stats(self):
         """hcmvs_get_handoff_stats: counters of the last handoff_maps_device call, summed over its items, and its device time"""

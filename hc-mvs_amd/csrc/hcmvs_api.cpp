@@ -21,6 +21,9 @@
 #include "init_kernels.h"
 #include "handoff_kernels.h"
 #include "handoff_host.h"
+#include "speckle_plan.h"
+#include "speckle_host.h"
+#include "speckle_kernels.h"
 #include "prior_kernels.h"
 #include "dev_buf.h"
 
@@ -138,6 +141,12 @@ struct hcmvs_ctx final : Reclaimer {
 	Event handoffEv[2]; // timing: around the kernels
 	hcmvs_handoff_stats handoffStats = {};
 	bool haveHandoffStats = false;
+	// hcmvs_remove_speckles_batch_device: the result, the items, the tile table, the partials and the 8 B per pixel of a call
+	// (speckle_plan.h SpeckleLayout) on the device, and the page-locked staging of the first three, through which the result also comes
+	// back; the call synchronises, so nothing of it is in flight afterwards
+	DevBuf speckleBuf{this};
+	PinnedBuf specklePinned;
+	Event speckleEv[2]; // timing: around the kernels
 	// hcmvs_generate_plane_prior_device: the scratch of a call, kept for hcmvs_get_plane_prior_trace
 	// (the reclaimer gives it back when memory is short: the trace is then gone, the next generate call allocates again)
 	DevBuf priorGenKept{this};
@@ -1358,6 +1367,75 @@ int hcmvs_get_handoff_stats(hcmvs_ctx* c, hcmvs_handoff_stats* out) {
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipEventElapsedTime(&c->handoffStats.ms_device, c->handoffEv[0].get(), c->handoffEv[1].get())); // the call synchronised: both events have passed
 	*out = c->handoffStats;
+	return HCMVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the speckle filter (speckle_plan.h states the rule, the checks and the plan; speckle_host.h the CPU form)
+
+static std::vector<SpeckleArgs> speckle_args(const hcmvs_speckle_item* items, int32_t n) {
+	std::vector<SpeckleArgs> a;
+	if (!items || n < 1 || n > kSpeckleMaxItems) return a; // speckle_check reports it
+	a.resize((size_t)n);
+	for (int i = 0; i < n; ++i)
+		a[(size_t)i] = {(uintptr_t)items[i].d_depth, (uintptr_t)items[i].d_normal, (uintptr_t)items[i].d_conf, (uintptr_t)items[i].d_labels, items[i].width, items[i].height};
+	return a;
+}
+static void speckle_report(const SpeckleResult& r, hcmvs_speckle_stats* st) {
+	st->n_valid = r.valid; st->n_removed = r.removed; st->n_segments = r.segments; st->n_small = r.small; st->largest = r.largest;
+}
+
+int hcmvs_remove_speckles(int32_t w, int32_t h, float* depth, float* normal, float* conf, int32_t* labels, float thr, uint32_t speckle_size, hcmvs_speckle_stats* stats) {
+	const SpeckleArgs a = {(uintptr_t)depth, (uintptr_t)normal, (uintptr_t)conf, (uintptr_t)labels, w, h};
+	if (!speckle_check(&a, 1, thr).empty()) return HCMVS_ERR_INVALID;
+	SpeckleResult r = SpeckleResult();
+	speckle_host(w, h, depth, normal, conf, labels, thr, speckle_size, r);
+	if (stats) { *stats = hcmvs_speckle_stats(); speckle_report(r, stats); }
+	return HCMVS_OK;
+}
+
+int hcmvs_remove_speckles_batch_device(hcmvs_ctx* c, const hcmvs_speckle_item* items, int32_t n, float thr, uint32_t speckle_size, hcmvs_speckle_stats* stats) {
+	if (!c) return HCMVS_ERR_INVALID;
+	const std::vector<SpeckleArgs> args = speckle_args(items, n);
+	const SpeckleArgs none = SpeckleArgs(); // items given, n_items out of range: the check reports the count and reads nothing
+	const std::string why = speckle_check(!args.empty() ? args.data() : items ? &none : nullptr, n, thr);
+	if (!why.empty()) return fail(c, HCMVS_ERR_INVALID, "remove_speckles_batch_device: %s", why.c_str());
+	const SpeckleTiles tiles = speckle_tiles(args.data(), n);
+	if (!speckle_grid_fits(tiles)) return fail(c, HCMVS_ERR_INVALID, "remove_speckles_batch_device: the batch has 2^31 tiles or more");
+	HIPCHK(c, hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	const int nTiles = (int)tiles.first[(size_t)n];
+	const SpeckleLayout l = speckle_layout(n, (size_t)nTiles, (size_t)tiles.pixel0[(size_t)n]);
+	for (Event& e : c->speckleEv) HIPCHK(c, e.ensure());
+	if (c->specklePinned.reserve(speckle_layout(kSpeckleMaxItems, 0, 0).staged) != hipSuccess) return fail(c, HCMVS_ERR_HIP, "remove_speckles_batch_device: no page-locked staging");
+	HIPCHK(c, c->speckleBuf.reserve(l.bytes, s));
+	char* h = c->specklePinned.get();
+	char* d = c->speckleBuf.get();
+	SpeckleResult* hr = (SpeckleResult*)(h + l.result);
+	SpeckleItem* hi = (SpeckleItem*)(h + l.items);
+	int32_t* hf = (int32_t*)(h + l.first);
+	*hr = SpeckleResult(); // the error word starts clear
+	for (int i = 0; i < n; ++i) {
+		hi[i] = {items[i].d_depth, items[i].d_normal, items[i].d_conf, items[i].d_labels, (int32_t*)(d + l.labels) + tiles.pixel0[(size_t)i],
+		         (int32_t*)(d + l.sizes) + tiles.pixel0[(size_t)i], items[i].width, items[i].height, speckle_tiles_x(items[i].width), 0};
+		hf[i] = (int32_t)tiles.first[(size_t)i];
+	}
+	hf[n] = nTiles;
+	HIPCHK(c, hipMemcpyAsync(d, h, l.staged, hipMemcpyHostToDevice, s));
+	HIPCHK(c, hipEventRecord(c->speckleEv[0].get(), s));
+	launch_speckle((const SpeckleItem*)(d + l.items), (const int32_t*)(d + l.first), n, nTiles, thr, speckle_size, (SpecklePartial*)(d + l.partials),
+	               (SpeckleResult*)(d + l.result), s);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(c->speckleEv[1].get(), s));
+	HIPCHK(c, hipMemcpyAsync(hr, d + l.result, sizeof(SpeckleResult), hipMemcpyDeviceToHost, s));
+	HIPCHK(c, hipStreamSynchronize(s)); // the one synchronisation of the call: the counters and the error word
+	if (hr->error) return fail(c, HCMVS_ERR_INTERNAL, "remove_speckles_batch_device: a union-find loop ran past its bound; the maps of the call are not to be used");
+	if (stats) {
+		*stats = hcmvs_speckle_stats();
+		speckle_report(*hr, stats);
+		HIPCHK(c, hipEventElapsedTime(&stats->ms_device, c->speckleEv[0].get(), c->speckleEv[1].get()));
+		stats->device_bytes = l.bytes;
+	}
 	return HCMVS_OK;
 }
 

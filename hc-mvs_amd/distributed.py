@@ -133,7 +133,7 @@ def _handoff(ctx, dev, mode, jobs, w, h):
 def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, device=None, batch=32, capacity=None,
                   fuse_kw=None, n_external_iters=1, postfilter=False, pf_kw=None, interleave=False, masks=None, viewspread=False,
                   geometric_filter=None, gf_kw=None, hints=None, fuse=True, priors=None, prior_params=None,
-                  plane_priors=None, plane_prior_params=None, geo=None):
+                  plane_priors=None, plane_prior_params=None, geo=None, speckle_size=0, speckle_diff=None):
     """The multi-rank scene path (BASELINE.json configs[3]) over the C-ABI binding, with the reference's outer
     iterations (SceneDensify.cpp:3684) and the fork's post-filters after outer iterations 1 and 2 (SceneDensify.cpp:3939-3958):
 
@@ -218,6 +218,12 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                Replicated on every rank like the fusion -- every rank filters identical gathered maps with a deterministic kernel, and a
                second all-gather of the filtered maps would cost more than the filter; gf_kw: max_neighbors, n_min_views,
                n_min_views_adjust, depth_diff_threshold.  The returned `maps` are the filtered ones, `filter` the stage's counters
+    speckle_size: above 0, the speckle filter (binding.Context.remove_speckles_device): right after the end pass of
+               the last outer iteration the finished maps of every batch lose their segments of fewer than speckle_size pixels (upstream's
+               nSpeckleSize is 100), on the rank that estimated them and before anything else reads them -- the post-filters of that
+               iteration, geometric_filter, the fusion, the returned `maps`.  speckle_diff: the relative depth difference below which two
+               neighbours are of one segment (None: upstream's 0.01f * 0.7f).  `speckle` in the result: the counters, summed over this
+               rank's calls.  0 (default): off
     Returns the fused cloud dict of binding.Context.fuse plus `maps`: {id: (depth, normal, conf) device tensors}."""
     import copy
     import numpy as np
@@ -349,6 +355,18 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
         if extra:
             ctx.estimate_sweeps_batch_device(extra, p, p.n_estimation_iters, 2)
 
+    speckle_size = int(speckle_size)
+    if speckle_size < 0:
+        raise ValueError("densify_scene: speckle_size is a number of pixels >= 0, not %d" % speckle_size)
+    speckle_stats = {}
+
+    def remove_speckles(items):     # the finished maps of `items`, behind their estimate on the context's stream
+        st = ctx.remove_speckles_device([dict(width=w, height=h, d_depth=x["d_depth"], d_normal=x["d_normal"], d_conf=x["d_conf"]) for x in items],
+                                        speckle_diff, speckle_size)
+        for k, v in st.items():
+            speckle_stats[k] = max(speckle_stats.get(k, 0), v) if k in ("largest", "device_bytes") else speckle_stats.get(k, 0) + v
+
+    last_it = int(n_external_iters) - 1
     geo_kw = None
     if geo:
         geo_kw = dict(geo) if isinstance(geo, dict) else {}
@@ -389,6 +407,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                     ctx.estimate_batch_device([item_of(img, allm[row].data_ptr())], p)
                     if it == prior_it:
                         extra_sweeps([item_of(img, allm[row].data_ptr())])
+                    if speckle_size > 0 and it == last_it:
+                        remove_speckles([item_of(img, allm[row].data_ptr())])
                     ctx.synchronize()
                 if world > 1:
                     if allm.is_cuda and dist.get_backend(group) == "gloo":      # one-GPU rehearsal: gloo moves host tensors
@@ -419,6 +439,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
                 ctx.estimate_batch_device(items[b0:b0 + batch], p)
                 if it == prior_it:
                     extra_sweeps(items[b0:b0 + batch])
+                if speckle_size > 0 and it == last_it:
+                    remove_speckles(items[b0:b0 + batch])
         ctx.synchronize()
         if filt:
             allm = allgather_maps(slabs, group, out=gathered)  # every rank: every image's current maps
@@ -444,6 +466,8 @@ def densify_scene(ctx, views, srcs, neighbors, order, init, params, group=None, 
         cloud["maps"] = maps
         if filter_stats is not None:
             cloud["filter"] = filter_stats
+        if speckle_size > 0:
+            cloud["speckle"] = speckle_stats
         if viewspread:
             ctx.set_viewspread(False)
         if geo_kw is not None:

@@ -322,6 +322,7 @@ struct Run {
 	hcmvs_params prm;
 	std::mutex errMu; std::string loadError;
 	double tLoaded = 0, tInit = 0, tPostfilter = 0, tEstimated = 0, tCopied = 0;
+	std::mutex speckleMu; hcmvs_speckle_stats speckle = {}; // --speckle-size: the counters of the run, summed over its calls (one per batch and device)
 	// threads and device objects, destroyed in the reverse order: the workers stop first, the context creation is joined last
 	JoinedThread creator;
 	std::unique_ptr<Loader> loader;
@@ -648,6 +649,20 @@ bool estimate_images(Run& r, int d, const std::vector<uint32_t>& ids, const hcmv
 			err = std::string("the extra sweeps with the depth priors failed (") + hcmvs_last_error(dctx) + ")";
 			return false;
 		}
+	}
+	// --speckle-size: these are the finished maps of the batch (the end pass of the last outer iteration has run): small segments go, before
+	// anything reads the maps -- the saver, the post-filters of this iteration, --n-filter, the fusion
+	if (r.o.speckleSize > 0 && pr.it_external == r.o.estimationItersExternal - 1) {
+		std::vector<hcmvs_speckle_item> sp;
+		for (const auto& itx : items) sp.push_back({r.images[itx.ref_id].w, r.images[itx.ref_id].h, itx.d_depth, itx.d_normal, itx.d_conf, nullptr});
+		hcmvs_speckle_stats ss;
+		if (hcmvs_remove_speckles_batch_device(dctx, sp.data(), (int32_t)sp.size(), r.o.speckleDiff, (uint32_t)r.o.speckleSize, &ss) != HCMVS_OK) {
+			err = std::string("the speckle filter failed (") + hcmvs_last_error(dctx) + ")";
+			return false;
+		}
+		std::lock_guard<std::mutex> g(r.speckleMu);
+		r.speckle.n_valid += ss.n_valid; r.speckle.n_removed += ss.n_removed; r.speckle.n_segments += ss.n_segments; r.speckle.n_small += ss.n_small;
+		r.speckle.largest = std::max(r.speckle.largest, ss.largest); r.speckle.ms_device += ss.ms_device;
 	}
 	if (r.o.verbosity > 2)
 		for (const auto& itx : items)
@@ -1227,6 +1242,10 @@ bool finish_estimates(Run& r) {
 		       "loading + view selection %.2f s, set-up %.2f s\n",
 		       r.work.size(), r.todo.size() - r.work.size(), o.estimationItersExternal, o.estimationIters, r.tEstimated - r.tInit,
 		       pixels * o.estimationItersExternal / std::max(1e-9, r.tEstimated - r.tInit - r.tPostfilter) / 1e6, r.tPostfilter, r.tLoaded - r.tStart, r.tInit - r.tLoaded);
+	if (o.verbosity > 1 && o.speckleSize > 0)
+		printf("Speckle filter (segments below %d pixels, depth difference below %g): %llu segments, %llu small, %llu of %llu pixels removed, %.3f ms on the device\n",
+		       o.speckleSize, (double)o.speckleDiff, (unsigned long long)r.speckle.n_segments, (unsigned long long)r.speckle.n_small,
+		       (unsigned long long)r.speckle.n_removed, (unsigned long long)r.speckle.n_valid, r.speckle.ms_device);
 	return true;
 }
 // --n-filter: the filter stage (Scene::DenseReconstructionFilter, SceneDensify.cpp:4100-4185 -- the block the fork switched off at :3721-3756):

@@ -76,6 +76,9 @@ struct Options { // DensifyPointCloud.cpp:139-198 (defaults from there)
 	float ransacCluster = 10.f;   // --ransac-cluster (the reference's default; the authors run 7): read and unused without --plane-clusters 1
 	int planeRefit = 0;           // --plane-refit n (with --plane-priors 1), 0 .. 16: least-squares steps on the winner of every round of the plane detection, over
 	                              // its inliers in the eps / 4 band; 0 keeps the results of command lines written before it
+	int speckleSize = 0;          // --speckle-size n: after the end pass of the last outer iteration the segments of fewer than n pixels are removed from every
+	                              // finished depth map (hcmvs_remove_speckles_batch_device); upstream's nSpeckleSize is 100; 0 is off
+	float speckleDiff = 0.01f * 0.7f; // --speckle-diff f: two neighbouring depths belong to one segment when they differ by less than f of either
 	int device = 0, batch = 32;   // reference images per launch: 32 is the measured optimum (profiles/r02_knobs.txt); lowered when HBM is short
 	std::vector<int> devices;     // --devices 0,1,...: one context + host thread per entry; reference images sharded over them by their position in
 	                              // the fusion order (k mod N); post-filters and fusion on the first (an ordinal may repeat: two contexts on one GPU)
@@ -111,6 +114,8 @@ static const char* const kPlaneClusterOptions[] = {"--plane-clusters"};
 static const char* const kGeoOptions[] = {"--geo-consistency", "--geo-max-px"};
 // ... and the refit of the winning plane of the generated priors (a fifth table, for the same reason as the third)
 static const char* const kPlaneRefitOptions[] = {"--plane-refit"};
+// ... and the speckle filter's two (a sixth table, for the same reason)
+static const char* const kSpeckleOptions[] = {"--speckle-size", "--speckle-diff"};
 
 static const char* const kUsage =
 	"usage: DensifyPointCloud -i scene.mvs [-o out.mvs] [-w dir] [--resolution-level n] [--number-views n] "
@@ -137,6 +142,10 @@ static const char* const kUsage =
 	"       --plane-refit n      with --plane-priors 1: the winning plane of every round of the detection is refitted by n least-squares steps over its\n"
 	"                            inliers within a quarter of the --ransac-epsilon band, before its inliers are assigned or clustered (0 .. 16; default 0:\n"
 	"                            the plane is the best of the candidates spanned by three samples, the results of earlier command lines)\n"
+	"       --speckle-size n     the speckle filter: after the last outer iteration every finished depth map loses its segments of fewer than n pixels\n"
+	"                            (4-neighbours are of one segment when their depths differ by less than --speckle-diff of either, default 0.01 x 0.7);\n"
+	"                            upstream OpenMVS runs it with nSpeckleSize 100.  The .dmap files, --n-filter and the fusion see the filtered maps\n"
+	"                            (default 0: off, the results of earlier command lines)\n"
 	"       --n-filter 0|1|2     the depth-map filter stage before the fusion: every depth map against up to 8 neighbours' maps (0 off, the default;\n"
 	"                            1 adjust: consistent depths are averaged, 2 strict: kept as they are); the final .dmap files hold the filtered maps\n"
 	"                            (with --resume 1 a second run loads those filtered maps and filters them again, as the reference would)\n"
@@ -165,6 +174,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 		for (const char* k : kPlaneClusterOptions) known = known || a == k;
 		for (const char* k : kGeoOptions) known = known || a == k;
 		for (const char* k : kPlaneRefitOptions) known = known || a == k;
+		for (const char* k : kSpeckleOptions) known = known || a == k;
 		if (!known) { err = "unrecognised option '" + a + "'"; return PARSE_ERROR; }
 		if (!haveVal) { // the value is the next argument, whatever it starts with (negative numbers are values)
 			if (i + 1 >= argc) { err = "the required argument for option '" + a + "' is missing"; return PARSE_ERROR; }
@@ -195,6 +205,7 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	getf("--ransac-probability", o.ransacProbability); getf("--ransac-epsilon", o.ransacEpsilon); getf("--ransac-min-points", o.ransacMinPoints);
 	geti("--plane-clusters", o.planeClusters); getf("--ransac-cluster", o.ransacCluster);
 	geti("--plane-refit", o.planeRefit);
+	geti("--speckle-size", o.speckleSize); getf("--speckle-diff", o.speckleDiff);
 	geti("--geo-consistency", o.geoConsistency); getf("--geo-max-px", o.geoMaxPx);
 	getf("--n-para_tapa", o.paraTapa); getf("--n-para_tapa2", o.paraTapa2); getf("--n-txthreshold", o.txThreshold); getf("--n-txthreshold2", o.txThreshold2);
 	geti("--device", o.device); geti("--batch", o.batch);
@@ -229,6 +240,8 @@ inline ParseResult parse_options(int argc, char** argv, Options& o, std::string&
 	if (!o.exportPriors.empty() && !o.planePriors) { err = "--export-priors writes the priors that --plane-priors 1 generates: give both"; return PARSE_ERROR; }
 	if (o.planeClusters != 0 && o.planeClusters != 1) { err = "--plane-clusters expects 0 or 1"; return PARSE_ERROR; }
 	if (o.planeClusters && !o.planePriors) { err = "--plane-clusters 1 clusters the inliers of the planes that --plane-priors 1 fits: give both"; return PARSE_ERROR; }
+	if (o.speckleSize < 0) { err = "--speckle-size expects a number of pixels >= 0 (0 is off; upstream's nSpeckleSize is 100)"; return PARSE_ERROR; }
+	if (!(o.speckleDiff > 0.f) || !(o.speckleDiff < INFINITY)) { err = "--speckle-diff expects a finite value > 0"; return PARSE_ERROR; }
 	if (o.planeRefit < 0 || o.planeRefit > 16) { err = "--plane-refit expects a number of steps from 0 to 16"; return PARSE_ERROR; }
 	if (o.planeRefit && !o.planePriors) { err = "--plane-refit refits the planes that --plane-priors 1 fits: give both"; return PARSE_ERROR; }
 	if (o.planePriors) {

@@ -46,7 +46,8 @@ enum {
 	HCMVS_ERR_INVALID = 2,     /* bad argument (null pointer, unknown view id, size mismatch, V out of range) */
 	HCMVS_ERR_HIP = 3,         /* a HIP call failed */
 	HCMVS_ERR_TIMEOUT = 4,     /* a sweep worker gave up waiting on its predecessor row (never expected) */
-	HCMVS_ERR_CAPACITY = 5     /* output buffer too small (fuse) */
+	HCMVS_ERR_CAPACITY = 5,    /* output buffer too small (fuse) */
+	HCMVS_ERR_INTERNAL = 6     /* a bounded loop of a kernel ran past its bound (the speckle filter's union-find; never expected) */
 };
 
 typedef struct hcmvs_ctx hcmvs_ctx;
@@ -477,6 +478,43 @@ int hcmvs_handoff_maps(hcmvs_handoff_item* items, int32_t n_items, int32_t mode)
  * the device.  HCMVS_OK when every item ran; an item without a valid depth is reported in its status only. */
 int hcmvs_handoff_maps_device(hcmvs_ctx* ctx, hcmvs_handoff_item* items, int32_t n_items, int32_t mode);
 int hcmvs_get_handoff_stats(hcmvs_ctx* ctx, hcmvs_handoff_stats* out);
+
+/* ---- the speckle filter: small depth segments of a finished map are removed ---------------------------------
+ * Upstream's speckle removal (nSpeckleSize, default 100; SceneDensify.cpp:1956-2042, compiled out in the fork) with a symmetric edge:
+ *   a pixel is valid when depth > 0 (a NaN is not; an infinite depth is, and is similar to nothing);
+ *   two valid 4-neighbours p, q are joined when fabsf(dp - dq) / dp < thr AND fabsf(dp - dq) / dq < thr, in float32, IEEE division;
+ *   a segment is a connected component of valid pixels under those edges, its canonical label the smallest raster index y * w + x in it;
+ *   a segment of fewer than speckle_size pixels is removed: depth = 0, normal = (0, 0, 0), conf = 0.  Everything else is left bit for
+ *   bit as it was.  speckle_size 0 or 1 removes nothing.  thr: upstream's is 0.01f * 0.7f.
+ * The filter is idempotent and deterministic (sizes are integers).  Both forms below compute the same bits. */
+typedef struct {
+	int32_t width, height;
+	float* d_depth;     /* width * height, in / out */
+	float* d_normal;    /* width * height * 3, in / out, or NULL */
+	float* d_conf;      /* width * height, in / out, or NULL */
+	int32_t* d_labels;  /* width * height, or NULL: out, the canonical label of every pixel, -1 where the depth is not valid, as BEFORE the removal */
+} hcmvs_speckle_item;
+/* counters of a call, summed over its maps */
+typedef struct {
+	uint64_t n_valid;      /* valid pixels before the removal */
+	uint64_t n_removed;    /* pixels removed */
+	uint64_t n_segments;
+	uint64_t n_small;      /* segments removed */
+	uint32_t largest;      /* pixels of the largest segment */
+	float ms_device;       /* device form: HIP events around the kernels; host form: 0 */
+	uint64_t device_bytes; /* device form: the scratch of the call (8 B per pixel of the batch and a little); host form: 0 */
+} hcmvs_speckle_stats;
+/* Every map in DEVICE memory (the items array itself is a host array), 1 <= n_items <= HCMVS_MAX_BATCH maps of any mix of sizes: ONE
+ * set of five launches for the whole batch, however many maps and whatever they hold, enqueued on the context's stream; the call then
+ * synchronises with the stream once, to read the counters and the error word.  HCMVS_ERR_INVALID, before anything reaches the device:
+ * null items, n_items out of range, a size below 1 or width * height >= 2^31, a null depth, a depth_diff_threshold that is not a finite
+ * number > 0, two buffers of the call that overlap.  HCMVS_ERR_INTERNAL when a union-find loop ran past its bound (never expected;
+ * no loop of the kernels is unbounded). */
+int hcmvs_remove_speckles_batch_device(hcmvs_ctx* ctx, const hcmvs_speckle_item* items, int32_t n_items, float depth_diff_threshold, uint32_t speckle_size,
+                                       hcmvs_speckle_stats* stats_or_null);
+/* HOST buffers, host code, no context (callable from any thread): the rule as a sequential flood fill.  The same refusals. */
+int hcmvs_remove_speckles(int32_t w, int32_t h, float* depth, float* normal_or_null, float* conf_or_null, int32_t* labels_or_null, float depth_diff_threshold,
+                          uint32_t speckle_size, hcmvs_speckle_stats* stats_or_null);
 
 /* ---- filter and fuse: work on the estimated maps registered per view ------------------------------------ */
 
