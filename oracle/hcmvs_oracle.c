@@ -29,6 +29,7 @@
 #include <float.h>
 #include <math.h>
 #include <stdatomic.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -244,16 +245,22 @@ void hcor_resize_size(int w, int h, float scale, int* dw, int* dh) {
 	*dw = (int)lrint((double)w * (double)scale);
 	*dh = (int)lrint((double)h * (double)scale);
 }
-typedef struct { int idx[8]; float alpha[8]; int n; } area_tab; /* one destination cell; factor < 6 -> at most 8 entries */
+/* one destination cell of computeResizeAreaTab.  A cell of `scale` source pixels holds at most a leading partial cell, floor(scale)
+ * whole cells and a trailing partial cell: tables of area_cell_cap(scale) = ceil(scale) + 2 entries hold every cell of any factor. */
+static int area_cell_cap(double scale) { return (int)ceil(scale) + 2; }
 static void area_cell(int d, double scale, int ssize, int* idx, float* alpha, int* n, int cap) {
 	const double fsx1 = d * scale, fsx2 = fsx1 + scale;
 	const double cellWidth = fmin(scale, ssize - fsx1);
 	int sx1 = (int)ceil(fsx1), sx2 = (int)floor(fsx2), k = 0;
 	if (sx2 > ssize - 1) sx2 = ssize - 1;
 	if (sx1 > sx2) sx1 = sx2;
-	if (sx1 - fsx1 > 1e-3 && k < cap) { idx[k] = sx1 - 1; alpha[k++] = (float)((sx1 - fsx1) / cellWidth); }
-	for (int sx = sx1; sx < sx2 && k < cap; ++sx) { idx[k] = sx; alpha[k++] = (float)(1.0 / cellWidth); }
-	if (fsx2 - sx2 > 1e-3 && k < cap) { idx[k] = sx2; alpha[k++] = (float)(fmin(fmin(fsx2 - sx2, 1.), cellWidth) / cellWidth); }
+	if ((sx1 - fsx1 > 1e-3) + (sx2 - sx1) + (fsx2 - sx2 > 1e-3) > cap) { /* a table too short is a bug of the caller: never a silent stop */
+		fprintf(stderr, "hcmvs_oracle: area_cell: cell %d of factor %g needs more than %d table entries\n", d, scale, cap);
+		abort();
+	}
+	if (sx1 - fsx1 > 1e-3) { idx[k] = sx1 - 1; alpha[k++] = (float)((sx1 - fsx1) / cellWidth); }
+	for (int sx = sx1; sx < sx2; ++sx) { idx[k] = sx; alpha[k++] = (float)(1.0 / cellWidth); }
+	if (fsx2 - sx2 > 1e-3) { idx[k] = sx2; alpha[k++] = (float)(fmin(fmin(fsx2 - sx2, 1.), cellWidth) / cellWidth); }
 	*n = k;
 }
 static void cubic_w(float x, float* c) {
@@ -345,12 +352,17 @@ void hcor_resize_gray(const float* src, int sw, int sh, float scale, float* dst,
 			}
 		return;
 	}
+	const int cap = area_cell_cap(sc); /* the tables are sized by the factor: hcmvs_rescale_view shrinks by any factor that leaves 16 x 16 */
+	int* const tabi = (int*)malloc(sizeof(int) * 2 * (size_t)cap);
+	float* const taba = (float*)malloc(sizeof(float) * 2 * (size_t)cap);
+	if (!tabi || !taba) { fprintf(stderr, "hcmvs_oracle: hcor_resize_gray: out of memory\n"); abort(); }
+	int *const yi = tabi, *const xi = tabi + cap;
+	float *const yb = taba, *const xa = taba + cap;
 	for (int y = 0; y < dh; ++y) {
-		int yi[16], ny; float yb[16];
-		area_cell(y, sc, sh, yi, yb, &ny, 16);
+		int ny, nx;
+		area_cell(y, sc, sh, yi, yb, &ny, cap);
 		for (int x = 0; x < dw; ++x) {
-			int xi[16], nx; float xa[16];
-			area_cell(x, sc, sw, xi, xa, &nx, 16);
+			area_cell(x, sc, sw, xi, xa, &nx, cap);
 			float sum = 0;
 			for (int j = 0; j < ny; ++j) {
 				float buf = 0;
@@ -360,6 +372,7 @@ void hcor_resize_gray(const float* src, int sw, int sh, float scale, float* dst,
 			dst[(size_t)y * dw + x] = sum;
 		}
 	}
+	free(tabi); free(taba);
 }
 
 void hcor_splat_init(const hcor_view* ref, const float* pts, int n, float* depth, float* normal,

@@ -213,6 +213,28 @@ def gradient_map(gray_f32):
     return gra
 
 
+def gray_f32_to_u8(gray_f32):
+    g = np.ascontiguousarray(gray_f32, np.float32)
+    out = np.empty(g.shape, np.uint8)
+    lib().hcor_gray_f32_to_u8(fptr(g), g.shape[1], g.shape[0], u8ptr(out))
+    return out
+
+
+def bgr2gray_u8(bgr):
+    b = np.ascontiguousarray(bgr, np.uint8)
+    out = np.empty(b.shape[:2], np.uint8)
+    lib().hcor_bgr2gray_u8(u8ptr(b), b.shape[1], b.shape[0], u8ptr(out))
+    return out
+
+
+def gradient_u8(g8):
+    """InitGraMap's Sobel / convertScaleAbs / addWeighted on an 8-bit image"""
+    g = np.ascontiguousarray(g8, np.uint8)
+    out = np.empty(g.shape, np.uint8)
+    lib().hcor_gradient_map(u8ptr(g), g.shape[1], g.shape[0], u8ptr(out))
+    return out
+
+
 def resize_gray(gray, scale):
     """ViewData::ScaleImage on an f32 image: returns the resampled image"""
     L = lib()
